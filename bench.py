@@ -29,7 +29,13 @@ vocoder on the generated features (post-processing + Vocos decode + clamp, ``:37
 and one RCCL all-gather over xGMI reassembles the output wav batch on every rank.
 Inputs are resident in HBM before the timed region.
 
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--dump-outputs
+DIR`` also writes what the last timed step returned (the wav batch and its lengths) as
+``DIR/<name>.npy``; ``--full`` adds the legs that take runs of their own: the per-kernel roofline
+pass, the fp32 / fp16 modes (C2 / C3 in bf16) and the CPU baseline.
+
 Launch: python bench.py [--gpus N --steps K --warmup W --config C2|C3|C4|C5 --precision P]
+                        [--dump-outputs DIR] [--full]
         (N > 1 under torch.distributed.run, one process per GPU).
 """
 import argparse
@@ -200,7 +206,9 @@ class Job:
         return generate_batch_dp(self.items, self.compute, self.costs)
 
 
-def timed(job, steps, warmup, world):
+def timed(job, steps, warmup, world, keep=None):
+    """Seconds per step over `steps` timed steps after `warmup` untimed ones.  With a list
+    `keep`, what the last timed step returned is appended to it."""
     import torch.distributed as dist
     for _ in range(warmup):
         job.step()
@@ -208,8 +216,9 @@ def timed(job, steps, warmup, world):
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         job.step()
+    last = job.step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -218,7 +227,30 @@ def timed(job, steps, warmup, world):
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if keep is not None:
+        keep.append(last)
     return dt / steps
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, wav, lens):
+    """What a caller of the timed step receives from its last run, as float32 .npy files: `wav`
+    (the (B, n) batch, or (B, n, C)) and `lens` (samples per utterance).  A wav batch over the
+    size limit is written as `wav_sample`, its flattened elements at the sorted positions
+    `wav_sample_index` (a fixed seeded draw, stored as float64: exact for these indices), so that
+    two runs with the same arguments store the same elements."""
+    os.makedirs(path, exist_ok=True)
+    wav = wav.detach().float().cpu().numpy()
+    np.save(os.path.join(path, "lens.npy"), lens.detach().cpu().numpy().astype(np.float32))
+    if wav.nbytes <= DUMP_LIMIT_BYTES - 2 ** 20:    # (1 MB left for lens and the .npy headers)
+        np.save(os.path.join(path, "wav.npy"), np.ascontiguousarray(wav))
+        return
+    n = DUMP_LIMIT_BYTES // 32                      # 8 MB of float32 values + 16 MB of indices
+    idx = np.sort(np.random.default_rng(2024).integers(0, wav.size, n))
+    np.save(os.path.join(path, "wav_sample.npy"), wav.reshape(-1)[idx])
+    np.save(os.path.join(path, "wav_sample_index.npy"), idx.astype(np.float64))
 
 
 def _kernel_roofline(name, r, total_ms):
@@ -349,9 +381,16 @@ def main():
     ap.add_argument("--config", default="C2", choices=sorted(CONFIGS))
     ap.add_argument("--precision", default=None, choices=["bf16", "fp32", "fp16", "fp8"],
                     help="compute mode (default: the config's, bf16; C5 fp8 as BASELINE names it)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-mode", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (wav, lens) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel roofline pass, the fp32 / "
+                         "fp16 legs (C2 / C3, bf16) and the CPU baseline, and add them to the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip that leg")
+    ap.add_argument("--no-fp32-mode", action="store_true", help="with --full: skip the fp32 / fp16 legs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     conf = CONFIGS[args.config]
     if args.precision is None:
         args.precision = conf["precision"]
@@ -369,7 +408,8 @@ def main():
     model = build(conf["variant"], args.precision, device)
     vocoder = build_vocoder(device)
     job = Job(conf, model, vocoder, n_items, device)
-    ms = timed(job, args.steps, args.warmup, world) * 1e3
+    last = [] if args.dump_outputs else None
+    ms = timed(job, args.steps, args.warmup, world, keep=last) * 1e3
     T_GEN = conf["t_gen"]
     frames = n_items * T_GEN
     value = frames / (ms * 1e-3)
@@ -398,8 +438,11 @@ def main():
                                           "(SURVEY.md §6) x rows x steps + 27 MFLOP/frame vocoder"},
     }
     if rank == 0:
-        result["roofline"] = roofline(job)
-        if world == 1 and not args.no_fp32_mode and args.precision == "bf16" and args.config in ("C2", "C3"):
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, *last.pop()[:2])
+        if args.full:
+            result["roofline"] = roofline(job)
+        if args.full and world == 1 and not args.no_fp32_mode and args.precision == "bf16" and args.config in ("C2", "C3"):
             del job, model
             torch.cuda.empty_cache()
             m32 = build(conf["variant"], "fp32", device)
@@ -434,7 +477,7 @@ def main():
             # the fp8 mode (BASELINE configs[4]) is not a leg of this line since round 4: on the fused
             # tree it runs within 2-4 % of bf16 (the explicit stop); its C5 timing is
             # tools/config_bench.py's, its accuracy tests/test_gpu_fp8.py
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(conf)
         print(json.dumps(result), flush=True)
     if world > 1:
