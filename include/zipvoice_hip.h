@@ -36,6 +36,8 @@
  *   zv_fbank_*         VocosFbank.extract (zipvoice/utils/feature.py:36-120) and
  *                      BigVGANFbank.extract (:133-204, _bigvgan_mel_feature.py:42-111): the prompt
  *                      log-mel front end feeding prompt_features (infer_zipvoice.py:328-337)
+ *   zv_resample_*      torchaudio.transforms.Resample on the loaded prompt
+ *                      (infer_zipvoice.py:332-338, infer_zipvoice_dialog.py:270-277, :417-422)
  */
 #ifndef ZIPVOICE_HIP_H
 #define ZIPVOICE_HIP_H
@@ -334,6 +336,32 @@ void zv_fbank_destroy(zv_fbank_handle f);
 int zv_fbank_configure(zv_fbank_handle f, int frame_offset, float mag_eps, float log_floor);
 int zv_fbank_extract(zv_fbank_handle f, const float* wav, int64_t wav_ld, const int32_t* lens,
                      int B, int T_out, float* out, int64_t out_ld, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Prompt resampler: torchaudio.transforms.Resample(orig_freq, new_freq) with its
+ * defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99), the step the
+ * reference applies to a loaded prompt whose rate is not the model's
+ * (zipvoice/bin/infer_zipvoice.py:332-338; zipvoice/bin/infer_zipvoice_dialog.py:270-277
+ * and :417-422).  fp32 arithmetic, taps summed in ascending order.
+ *
+ * The filter comes from the host in compact form (zipvoice_amd/feature.py resample_plan):
+ * o = orig / gcd, n = new / gcd; output i*n + j = sum_{k < S} host_table[j, k] *
+ * x[i*o + host_start[j] + k], samples outside [0, len) counting as 0.  host_start [n]
+ * must be non-decreasing with host_start[n-1] - host_start[0] <= o; host_table is [n, S].
+ * create rejects o == n (equal rates: use the input), non-positive sizes, S > 512,
+ * n * S > 16 Mi entries, and o / n so large that the input span of 256 outputs exceeds
+ * 64 KiB.  Device memory is the compact table only (zv_resample_device_bytes).
+ * ---------------------------------------------------------------------- */
+typedef struct zv_resample* zv_resample_handle;
+zv_resample_handle zv_resample_create(int o, int n, int S, const int32_t* host_start,
+                                      const float* host_table);
+void zv_resample_destroy(zv_resample_handle h);
+/* wav: [R, wav_ld] fp32 device samples, lens: [R] int32 device sample counts (<= wav_ld);
+ * out: [R, out_ld], columns [0, out_cols): row r receives ceil(n * lens[r] / o) samples
+ * (at most out_cols), then zeros.  A row's result does not depend on the other rows. */
+int zv_resample_apply(zv_resample_handle h, const float* wav, int64_t wav_ld, const int32_t* lens,
+                      int R, float* out, int64_t out_ld, int64_t out_cols, void* stream);
+int64_t zv_resample_device_bytes(zv_resample_handle h);
 
 #ifdef __cplusplus
 }

@@ -1816,6 +1816,7 @@ struct zv_engine {
 #include "zv_vocoder.inc"
 #include "zv_bigvgan.inc"
 #include "zv_fbank.inc"
+#include "zv_resample.inc"
 
 // ===========================================================================
 // C ABI
@@ -2603,6 +2604,36 @@ int zv_fbank_extract(zv_fbank_handle f, const float* wav, int64_t wav_ld, const 
   f->extract(wav, (long)wav_ld, lens, B, T_out, out, (long)out_ld, (hipStream_t)stream);
   ZV_API_END
 }
+
+zv_resample_handle zv_resample_create(int o, int n, int S, const int32_t* host_start,
+                                      const float* host_table) {
+  zv_resample* h = nullptr;
+  try {
+    ZV_REQUIRE(host_start && host_table, "null host_start / host_table");
+    h = new zv_resample();
+    h->init(o, n, S, host_start, host_table);
+    return h;
+  } catch (const std::exception& e) {
+    delete h;
+    g_last_error = e.what();
+    return nullptr;
+  }
+}
+
+void zv_resample_destroy(zv_resample_handle h) { delete h; }
+
+int zv_resample_apply(zv_resample_handle h, const float* wav, int64_t wav_ld, const int32_t* lens,
+                      int R, float* out, int64_t out_ld, int64_t out_cols, void* stream) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(h != nullptr, "null resample handle");
+  ZV_REQUIRE(R > 0 && R <= 65535 && wav && lens && out, "bad arguments (R must be in [1, 65535])");
+  ZV_REQUIRE(out_cols > 0 && out_ld >= out_cols, "out_cols must be in [1, out_ld]");
+  ZV_REQUIRE(out_cols <= (int64_t)h->E * 0x7fffffff, "out_cols too large");
+  h->apply(wav, (long)wav_ld, lens, R, out, (long)out_ld, (long)out_cols, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int64_t zv_resample_device_bytes(zv_resample_handle h) { return h ? (int64_t)h->bytes : 0; }
 
 int64_t zv_vocoder_device_bytes(zv_vocoder_handle v) {
   if (!v) return 0;

@@ -105,6 +105,11 @@ SIGNATURES = {
     "zv_fbank_destroy": (None, [_P]),
     "zv_fbank_extract": (_I, [_P, _P, ctypes.c_int64, _P, _I, _I, _P, ctypes.c_int64, _P]),
     "zv_fbank_configure": (_I, [_P, _I, _F, _F]),
+    # prompt resampler (zipvoice_amd/feature.py Resample)
+    "zv_resample_create": (_P, [_I, _I, _I, _P, _P]),
+    "zv_resample_destroy": (None, [_P]),
+    "zv_resample_apply": (_I, [_P, _P, ctypes.c_int64, _P, _I, _P, ctypes.c_int64, ctypes.c_int64, _P]),
+    "zv_resample_device_bytes": (ctypes.c_int64, [_P]),
 }
 
 _libs: Dict[str, ctypes.CDLL] = {}

@@ -22,6 +22,10 @@ is the same kernel configured for NVIDIA's BigVGAN mel: reflect pad
 the Slaney mel filterbank of ``librosa.filters.mel`` (restated in
 ``slaney_mel_fbanks``; librosa is not installed here), ``log(clamp(1e-5))``,
 and replicate padding of the last STFT frame up to the lhotse frame count.
+
+``Resample`` is the step before both: ``torchaudio.transforms.Resample`` on a
+loaded prompt whose rate is not the model's (``infer_zipvoice.py:332-338``), as
+the engine's ``zv_resample_*`` kernel with the filter table of ``resample_plan``.
 """
 from __future__ import annotations
 
@@ -260,3 +264,151 @@ class BigVGANFbank(VocosFbank):
         self._h = None
         self._lib = None
 
+
+
+@dataclass
+class ResamplePlan:
+    """Compact polyphase form of torchaudio's resampling kernel (``resample_plan``)."""
+    o: int                  # orig_freq / gcd
+    n: int                  # new_freq / gcd
+    width: int              # torchaudio's padding: ceil(lowpass_filter_width * o / base)
+    S: int                  # taps per output
+    start: np.ndarray       # (n,) int32: first tap's sample offset from i * o, per phase
+    table: np.ndarray       # (n, S) float32
+
+    def out_len(self, length: int) -> int:
+        """ceil(n * length / o) in integer arithmetic (torchaudio's target_length)."""
+        return (self.n * int(length) + self.o - 1) // self.o
+
+
+def resample_plan(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
+                  rolloff: float = 0.99) -> ResamplePlan:
+    """torchaudio.functional.resample's kernel (``_get_sinc_resample_kernel``,
+    resampling_method "sinc_interp_hann") in compact form; torchaudio itself is not
+    installed here.
+
+    torchaudio reduces the rates by their gcd to o and n, sets base = min(o, n) * rolloff
+    and width = ceil(lowpass_filter_width * o / base), and builds in float64 the dense
+    table K[j, k], j in [0, n), k in [0, 2 width + o):
+    t = clamp((-j / n + (k - width) / o) * base, -lw, lw),
+    K = sinc(pi t) * cos(pi t / (2 lw))**2 * (base / o), rounded to float32.  The input,
+    padded with ``width`` zeros in front and ``width + o`` behind, is convolved with K at
+    stride o: y[i n + j] = sum_k K[j, k] xpad[i o + k], cut to ceil(n L / o) samples.
+
+    Only taps with |t| < lw matter (at the clamp cos(pi / 2)**2 is ~4e-33, nothing in
+    float32), so phase j needs the samples i o + start[j] + [0, S) with
+    start[j] = floor(j o / n - lw o / base) and S = ceil(2 lw o / base) + 2.  ``table``
+    holds those taps (same float64 operations, then float32), exactly 0 where |t| >= lw.
+    The dense table grows with o * n (4.5 GB for 48001 -> 24000); this form with n * S."""
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq <= 0 or new_freq <= 0:
+        raise ValueError("Original frequency and desired frequecy should be positive")
+    if lowpass_filter_width <= 0:
+        raise ValueError("Low pass filter width should be positive.")
+    g = math.gcd(orig_freq, new_freq)
+    o, n = orig_freq // g, new_freq // g
+    lw = lowpass_filter_width
+    base = min(o, n) * rolloff
+    width = math.ceil(lw * o / base)
+    S = math.ceil(2 * lw * o / base) + 2
+    j = torch.arange(n, dtype=torch.float64)
+    start = torch.floor(j * o / n - lw * o / base)
+    m = start[:, None] + torch.arange(S, dtype=torch.float64)[None]     # sample offset from i * o
+    t = (-j)[:, None] / n + m / o
+    t = t * base
+    inside = t.abs() < lw
+    t = t.clamp(-lw, lw)
+    window = torch.cos(t * math.pi / lw / 2) ** 2
+    t = t * math.pi
+    k = torch.where(t == 0, torch.ones_like(t), t.sin() / t) * (window * (base / o))
+    k = torch.where(inside, k, torch.zeros_like(k))
+    return ResamplePlan(o=o, n=n, width=width, S=S,
+                        start=np.ascontiguousarray(start.numpy().astype(np.int32)),
+                        table=np.ascontiguousarray(k.to(torch.float32).numpy()))
+
+
+class Resample:
+    """Mirror of ``torchaudio.transforms.Resample(orig_freq, new_freq)`` (defaults
+    sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) on the GPU: the step the
+    reference applies to a loaded prompt (infer_zipvoice.py:332-338,
+    infer_zipvoice_dialog.py:270-277, :417-422).  The filter is ``resample_plan``'s; the
+    compute runs in the engine's ``zv_resample_*`` kernel."""
+
+    def __init__(self, orig_freq: int = 16000, new_freq: int = 16000,
+                 lowpass_filter_width: int = 6, rolloff: float = 0.99,
+                 device: Optional[Union[str, torch.device]] = None):
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.lowpass_filter_width, self.rolloff = lowpass_filter_width, rolloff
+        self.plan = (None if self.orig_freq == self.new_freq else
+                     resample_plan(orig_freq, new_freq, lowpass_filter_width, rolloff))
+        self._device = torch.device(device) if device is not None else None
+        self._h = None
+        self._lib = None
+
+    def _handle(self, device: torch.device):
+        if not torch.cuda.is_available():
+            raise RuntimeError("zipvoice_amd feature extraction needs a ROCm GPU; no CPU fallback")
+        if self._h is None:
+            self._lib = _eng.load_library()
+            p = self.plan
+            with torch.cuda.device(device):
+                h = self._lib.zv_resample_create(p.o, p.n, p.S, p.start.ctypes.data_as(ctypes.c_void_p),
+                                                 p.table.ctypes.data_as(ctypes.c_void_p))
+            if not h:
+                raise RuntimeError(self._lib.zv_last_error().decode())
+            self._h = h
+            self._device = device
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._lib is not None:
+            try:
+                torch.cuda.synchronize(self._device)
+            except Exception:
+                pass
+            self._lib.zv_resample_destroy(self._h)
+            self._h = None
+
+    def device_bytes(self) -> int:
+        """Device memory the handle holds (the compact table), 0 before the first call."""
+        return int(self._lib.zv_resample_device_bytes(self._h)) if self._h else 0
+
+    def resample_batch(self, wavs: torch.Tensor, lens) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Ragged rows on device: wavs (B, N) fp32 (padded), lens (B,) sample counts ->
+        (out (B, max out_len), out_lens (B,)).  Row b holds ceil(new * lens[b] / orig)
+        samples, then zeros, and equals that row resampled alone bit for bit."""
+        assert wavs.dim() == 2, wavs.shape
+        lens_cpu = [int(v) for v in torch.as_tensor(lens).cpu().tolist()]
+        assert len(lens_cpu) == wavs.shape[0], (len(lens_cpu), wavs.shape)
+        if max(lens_cpu) > wavs.shape[1] or min(lens_cpu) < 0:
+            raise ValueError("lens exceed the padded waveform length")
+        if self.plan is None:
+            return wavs, torch.tensor(lens_cpu, dtype=torch.int64, device=wavs.device)
+        dev = wavs.device if wavs.is_cuda else (self._device or torch.device("cuda"))
+        h = self._handle(dev)
+        wavs = wavs.to(dev, torch.float32).contiguous()
+        B, N = wavs.shape
+        olens = [self.plan.out_len(v) for v in lens_cpu]
+        cols = max(max(olens), 1)
+        out = torch.empty((B, cols), dtype=torch.float32, device=dev)
+        ln = torch.tensor(lens_cpu, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _eng._check(self._lib.zv_resample_apply(h, _eng._ptr(wavs), N, _eng._ptr(ln), B,
+                                                    _eng._ptr(out), cols, cols, _eng._stream()))
+        out = out[:, :max(olens)]
+        return out, torch.tensor(olens, dtype=torch.int64, device=dev)
+
+    def __call__(self, waveform: Union[np.ndarray, torch.Tensor]) -> Union[np.ndarray, torch.Tensor]:
+        """(..., N) -> (..., ceil(new_freq * N / orig_freq)) on the device (numpy in,
+        numpy out); the input itself when the rates are equal."""
+        if self.plan is None:
+            return waveform
+        is_numpy = not isinstance(waveform, torch.Tensor)
+        x = torch.from_numpy(np.asarray(waveform)) if is_numpy else waveform
+        shape = x.shape
+        x = x.reshape(-1, shape[-1]).float()
+        out, _ = self.resample_batch(x, [shape[-1]] * x.shape[0])
+        out = out.reshape(*shape[:-1], out.shape[-1])
+        return out.cpu().numpy() if is_numpy else out
+
+    forward = __call__

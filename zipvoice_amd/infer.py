@@ -2,14 +2,16 @@
 (``zipvoice/bin/infer_zipvoice.py:276-403``) from token ids to waveform, and a
 batched form for serving.
 
-Steps, as the reference: prompt RMS normalisation to ``target_rms`` (:340-342)
--> VocosFbank / BigVGANFbank prompt features (:345-347, :583-590) -> ``(feat + feat_bias) * feat_scale``
+Steps, as the reference: prompt resampling to the model's rate (torchaudio
+``Resample``, :335-338; ``feature.Resample`` on the device) -> prompt RMS
+normalisation to ``target_rms`` (:340-342) -> VocosFbank / BigVGANFbank prompt features (:345-347, :583-590) -> ``(feat + feat_bias) * feat_scale``
 (:349) -> ``model.sample(duration="predict")`` (:355-371) -> ``pred /
 feat_scale - feat_bias`` -> vocoder decode -> ``clamp(-1, 1)`` (:374-378) ->
 RTF metrics (:381-396) -> RMS restore (:399-400).  Text normalisation /
-tokenisation (jieba, pypinyin, piper) and audio file I/O + resampling
-(torchaudio) are outside the ported path: callers pass token ids and 24 kHz
-samples.
+tokenisation (jieba, pypinyin, piper) and audio file I/O (torchaudio.load) are
+outside the ported path: callers pass token ids and the prompt's samples with
+their rate.  ``prepare_prompt`` assembles the dialog / stereo prompts the way
+``infer_zipvoice_dialog.py`` does after loading.
 """
 from __future__ import annotations
 
@@ -38,6 +40,71 @@ def _prompt_rms_normalise(wav: torch.Tensor, target_rms: float) -> Tuple[torch.T
     return wav, rms
 
 
+_resamplers: Dict[Tuple[int, int], object] = {}
+
+
+def _resampler(orig_freq: int, new_freq: int):
+    """One ``feature.Resample`` (filter table + engine handle) per rate pair."""
+    from .feature import Resample
+    key = (int(orig_freq), int(new_freq))
+    if key not in _resamplers:
+        _resamplers[key] = Resample(*key)
+    return _resamplers[key]
+
+
+@torch.inference_mode()
+def prepare_prompt(wavs, rates, mode: str = "mono", sampling_rate: int = 24000, silence=None,
+                   device=None) -> torch.Tensor:
+    """The reference's prompt loading after ``torchaudio.load``: every wav (C, N) (or (N,)),
+    with its own rate, is resampled per channel to ``sampling_rate`` on the device, then
+    assembled into the (C, N) tensor ``feature_extractor.extract`` takes.
+
+    "mono"   (infer_zipvoice.py:332-338): one wav; a two-channel prompt keeps its channels
+             (the extractor averages them, as now).
+    "dialog" (infer_zipvoice_dialog.py:268-282): one or two wavs, each averaged to one
+             channel, concatenated in time.
+    "stereo" (:415-442): one two-channel wav; or two two-channel wavs concatenated in
+             time; or two one-channel wavs, the first on channel 0 over [0, n0) and the
+             second on channel 1 over [n0, n0 + n1), on a background of ``silence``
+             ((2, >= n0 + n1) samples at ``sampling_rate``, cut to n0 + n1) or zeros."""
+    if mode not in ("mono", "dialog", "stereo"):
+        raise ValueError(f"mode must be mono, dialog or stereo, not {mode!r}")
+    if torch.is_tensor(wavs) or isinstance(wavs, np.ndarray):
+        wavs = [wavs]
+    if isinstance(rates, int):
+        rates = [rates] * len(wavs)
+    assert len(wavs) == len(rates) and 1 <= len(wavs) <= (1 if mode == "mono" else 2)
+    dev = torch.device(device if device is not None else "cuda")
+    loaded = []
+    for w, rate in zip(wavs, rates):
+        w = torch.as_tensor(np.asarray(w) if not torch.is_tensor(w) else w, dtype=torch.float32)
+        w = (w.unsqueeze(0) if w.dim() == 1 else w).to(dev)
+        assert w.dim() == 2 and w.shape[0] in (1, 2), w.shape
+        if rate != sampling_rate:
+            w = _resampler(rate, sampling_rate)(w)
+        if mode == "dialog" and w.size(0) != 1:
+            w = w.mean(0, keepdim=True)
+        loaded.append(w)
+    if mode == "stereo" and len(loaded) == 1:
+        assert loaded[0].size(0) == 2, "Merged prompt wav must be stereo for stereo dialogue generation"
+    if len(loaded) == 1:
+        return loaded[0]
+    if mode == "dialog" or loaded[0].size(0) == 2:
+        assert loaded[0].size(0) == loaded[1].size(0), (loaded[0].shape, loaded[1].shape)
+        return torch.cat(loaded, dim=1)
+    assert loaded[0].size(0) == 1 and loaded[1].size(0) == 1
+    n0, n1 = loaded[0].size(1), loaded[1].size(1)
+    if silence is None:
+        out = torch.zeros((2, n0 + n1), dtype=torch.float32, device=dev)
+    else:
+        out = torch.as_tensor(np.asarray(silence) if not torch.is_tensor(silence) else silence,
+                              dtype=torch.float32).to(dev)[:, :n0 + n1].clone()
+        assert out.shape == (2, n0 + n1), f"silence must be (2, >= {n0 + n1}), got {tuple(out.shape)}"
+    out[0, :n0] = loaded[0][0]
+    out[1, n0:] = loaded[1][0]
+    return out
+
+
 @torch.inference_mode()
 def generate_sentence(tokens: List[int], prompt_tokens: List[int], prompt_wav, model, vocoder,
                       feature_extractor, num_step: int = 16, guidance_scale: float = 1.0,
@@ -47,14 +114,13 @@ def generate_sentence(tokens: List[int], prompt_tokens: List[int], prompt_wav, m
                       ) -> Tuple[torch.Tensor, Dict[str, float]]:
     """One sentence (infer_zipvoice.py:276-403).  Returns (wav (1, N) on the
     device, metrics with the reference's keys)."""
-    if prompt_sampling_rate != sampling_rate:
-        raise NotImplementedError("resample the prompt to 24 kHz before calling (torchaudio "
-                                  "Resample is outside the ported path)")
     dev = model.device
     w = torch.as_tensor(np.asarray(prompt_wav) if not torch.is_tensor(prompt_wav) else prompt_wav,
                         dtype=torch.float32)
     if w.dim() == 1:
         w = w.unsqueeze(0)
+    if prompt_sampling_rate != sampling_rate:                      # :335-338, before the RMS
+        w = _resampler(prompt_sampling_rate, sampling_rate)(w.to(dev))
     w, prompt_rms = _prompt_rms_normalise(w, target_rms)
     feats = feature_extractor.extract(w.to(dev), sampling_rate=sampling_rate)
     prompt_features = ((feats.unsqueeze(0) + feat_bias) * feat_scale).to(dev)
@@ -83,19 +149,35 @@ def generate_sentence(tokens: List[int], prompt_tokens: List[int], prompt_wav, m
 
 
 @torch.inference_mode()
-def generate_batch(items: Sequence[Tuple[List[int], List[int], np.ndarray]], model, vocoder,
+def generate_batch(items: Sequence[tuple], model, vocoder,
                    feature_extractor, num_step: int = 16, guidance_scale: float = 1.0,
                    speed: float = 1.0, t_shift: float = 0.5, target_rms: float = 0.1,
                    feat_scale: float = 0.1, feat_bias: float = 0.0, x0=None
                    ) -> Tuple[List[torch.Tensor], Dict[str, float]]:
-    """Batched serving form: items = [(tokens, prompt_tokens, prompt_wav_24k), ...].
+    """Batched serving form: items = [(tokens, prompt_tokens, prompt_wav), ...] with 24 kHz
+    prompts, or (tokens, prompt_tokens, prompt_wav, prompt_sampling_rate); prompts at
+    other rates are resampled on the device, one batched call per distinct rate.
     Each output equals what ``generate_sentence`` would produce for that item with
     the same initial noise (per-utterance lengths and masks throughout)."""
     dev = model.device
     B = len(items)
+    sampling_rate = feature_extractor.config.sampling_rate
+    prompts = [torch.as_tensor(np.asarray(it[2]), dtype=torch.float32).reshape(-1) for it in items]
+    by_rate: Dict[int, List[int]] = {}
+    for i, it in enumerate(items):
+        if len(it) > 3 and int(it[3]) != sampling_rate:
+            by_rate.setdefault(int(it[3]), []).append(i)
+    for rate, idx in by_rate.items():
+        lens = [len(prompts[i]) for i in idx]
+        rb = torch.zeros((len(idx), max(lens)), dtype=torch.float32)
+        for r, i in enumerate(idx):
+            rb[r, :lens[r]] = prompts[i]
+        out, olens = _resampler(rate, sampling_rate).resample_batch(rb.to(dev), lens)
+        out = out.cpu()             # RMS + padding below are the 24 kHz items' host path
+        for r, i in enumerate(idx):
+            prompts[i] = out[r, :int(olens[r])]
     wavs, rms = [], []
-    for _, _, pw in items:
-        w = torch.as_tensor(np.asarray(pw), dtype=torch.float32).reshape(-1)
+    for w in prompts:
         w, r = _prompt_rms_normalise(w, target_rms)
         wavs.append(w)
         rms.append(r)
