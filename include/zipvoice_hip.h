@@ -154,10 +154,91 @@ int zv_attn2_check(int kernel, int form, int B, int L, int H, int nv, const floa
  * (C += ..., fp32, plus a bf16 copy), 3 = SwooshL -> bf16. */
 int zv_bench_gemm(int M, int N, int K, int variant, int iters, int out_mode, float* ms_out);
 
-/* GEMM self-check (test infrastructure): tile variant `variant` (20-23: the
- * 256x256 phased kernel) against the 128x128 kernel on the same random operands,
- * fp32 C; mode 0 plain, 1 SwooshL, 2 residual.  Writes max |diff| and max |ref|. */
+/* GEMM self-check (test infrastructure): tile variant `variant` (30: 4-stage ring with a
+ * 32-deep K step, 40: deferred stores, 70 / 71 / 72: the counted residual / residual + bypass /
+ * plain epilogues; any other value is rejected) against the general 128x128 kernel on the same
+ * random operands; mode 0 plain, 1 SwooshL, 2 residual.  Writes max |diff| and max |ref|. */
 int zv_gemm_selftest(int M, int N, int K, int variant, int mode, float* maxdiff, float* maxref);
+
+/* One linear through the engine's own dispatch, on host arrays (test infrastructure: pins
+ * csrc/zv_gemm.inc and zv_gemm256.inc against a float64 reference in tests/test_gpu_linear_ref.py;
+ * no reference counterpart; synchronous).  The weight W (N, K) and bias (N) are in the reference's
+ * layout and become a device linear exactly as the engine's weights do (hi / lo halves, rows padded
+ * to 128, columns to 64, zero fill; the NA / GLU forms permute the rows as the engine does).  A
+ * (M, K) is laid out as the engine lays out an activation: rounded to the operand format (bf16, or
+ * fp16 in libzipvoice_hip_f16.so), with its lo half when split = 3, row stride K rounded up to 64,
+ * zero beyond K.  split: 1 = 16-bit product, 3 = hi/lo split products of both operands, 2 = the
+ * weight-split product (ZV_LIN_PLAIN without activation, and ZV_LIN_TRANS).  The launch is the one
+ * the engine would make for that shape and form, not a chosen instantiation; `launch` receives which
+ * one it was: {BM, BN, SPLIT, EPI, ROLE, 256x256 kernel, grid blocks, STAGES * 16 + OCC}.
+ *
+ * Outputs keep their padding: the caller passes every output buffer it wants with guard rows before
+ * row 0 and after the last row and a row stride larger than the width (ldc % 4 == 0, ldch % 8 == 0),
+ * pre-filled with a canary; the buffer goes to the device as it is (the residual forms place resid
+ * in the interior of C, which is updated in place as the engine updates its stream), comes back
+ * whole, and the caller checks that nothing outside the output changed.
+ *   C   fp32 (guard + M + guard, ldc);  Ch / Cl  16-bit hi / lo (guard + M + guard, ldch)
+ *   Cth / Ctl  transposed 16-bit output of ZV_LIN_TRANS / ZV_LIN_NA:
+ *              (guard + B * rows_t + guard, ldct), B = ceil(M / rpb), rows_t = N (TRANS) or N / 3
+ *              (NA); element [b][n][l] is row b * rpb + l, column n. */
+enum zv_linear_form {
+  ZV_LIN_PLAIN = 0,        /* bias (+ SwooshL when act = 1) -> Ch (/ Cl) */
+  ZV_LIN_PLAIN_F32 = 1,    /* bias (+ SwooshL) -> C */
+  ZV_LIN_RESID = 2,        /* C = resid + (A W^T + bias), and its copy Ch (/ Cl) when given */
+  ZV_LIN_RESID_BYP = 3,    /* ... then C = orig + (C - orig) * byp */
+  ZV_LIN_RESID_RV = 4,     /* C = resid + (A W^T + bias) + rowvec[row / rows_per_group] */
+  ZV_LIN_RESID_RV_COPY = 5,/* the same value to Ch only (no fp32 output; resid read from `resid`) */
+  ZV_LIN_TRANS = 6,        /* bias -> Cth (/ Ctl), transposed per utterance of rpb rows */
+  ZV_LIN_NA = 7,           /* W rows [s | x | y] (chunk(3)): x * tanh(s) -> Cth, y -> Ch, N / 3 wide */
+  ZV_LIN_GLU = 8           /* W rows [x | s] (chunk(2)): x * sigmoid(s), 0 where rowmask -> Ch, N / 2 wide */
+};
+typedef struct {
+  int M, N, K, split, form, act;
+  int rows_per_group;      /* row-vector forms */
+  int rpb;                 /* TRANS / NA: rows per utterance */
+  int guard;               /* guard rows on each side of every output */
+  const float* A; const float* W; const float* bias;
+  const float* resid;      /* (M, N) */
+  const float* orig;       /* (M, N) */
+  const float* byp;        /* (N) */
+  const float* rowvec;     /* (ceil(M / rows_per_group), N) */
+  const uint8_t* rowmask;  /* (M) or NULL */
+  float* C; int64_t ldc;
+  uint16_t* Ch; uint16_t* Cl; int64_t ldch;
+  uint16_t* Cth; uint16_t* Ctl; int64_t ldct;
+  int launch[8];           /* out */
+  int num_cus;             /* out: the CU count the dispatch thresholds used */
+} zv_linear_check_args;
+int zv_linear_check(zv_linear_check_args* a);
+
+/* The fused FeedForward kernel alone, on host arrays (test infrastructure: pins csrc/zv_ffn.inc
+ * against float64 in tests/test_gpu_ffn_ref.py; no reference counterpart; synchronous).  x (M, 512)
+ * is rounded to the operand format; W1 (H, 512), b1, W2 (512, H), b2 are in the reference's layout
+ * and are packed as the engine packs them.  form 0: C = resid + FF(x) (in place: resid starts in the
+ * interior of C), with the 16-bit copy Ch when given; 1: + rowvec[row / rows_per_group] (Ch
+ * required); 2: then the bypass C = orig + (C - orig) * byp (Ch required); 3: the BiasNorm epilogue,
+ * v = resid + FF(x); out = orig + (v * rsqrt(mean((v - nb)^2)) * exp(log_scale) - orig) * byp -> C
+ * (in place over orig, which starts in the interior of C), Ch (required), Cl, and out (+ rowvec
+ * when given) -> C2h / C2l where given.  part_slots 0: one row block per block; > 0: the
+ * persistent line schedule on that many blocks (at most the CU count).  Output buffers as
+ * zv_linear_check: (guard + M + guard) rows of ldc (fp32) / ldch (16-bit) elements, canary-filled by
+ * the caller.  launch: {128, 512, 1, RV | ORIG << 1 | COPY << 2 | TP << 3, NORM, 0, blocks, chunk
+ * steps per block}.  Fails if the device error word is set after the launch. */
+typedef struct {
+  int M, H, form, rows_per_group, part_slots, guard;
+  float log_scale;
+  const float* x; const float* W1; const float* b1; const float* W2; const float* b2;
+  const float* resid;      /* (M, 512) */
+  const float* rowvec;     /* (ceil(M / rows_per_group), 512) or NULL */
+  const float* orig;       /* (M, 512) */
+  const float* byp;        /* (512) */
+  const float* nb;         /* (512) */
+  float* C; int64_t ldc;
+  uint16_t* Ch; uint16_t* Cl; uint16_t* C2h; uint16_t* C2l; int64_t ldch;
+  int launch[8];
+  int num_cus;
+} zv_ffn_check_args;
+int zv_ffn_check(zv_ffn_check_args* a);
 
 /* Attention plan (host only, no GPU; test infrastructure): the LDS bytes of the fused
  * attention consumers a layer of sequence length L would launch — SelfAttention (sa_plo < 0:

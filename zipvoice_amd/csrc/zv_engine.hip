@@ -1072,6 +1072,69 @@ struct zv_engine {
     launch_gemm<128, 64, 2, 2, 2, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, "gemm_wsplit_n96", true, gridx_plain);
   }
 
+  // The layer's fused-epilogue launch choices on a prepared GemmParams (shared with zv_linear_check).
+  // NonlinAttention in-projection (EPI_NA: rows permuted by perm_na)
+  template <int SPLIT>
+  void launch_na_in(const GemmParams& p, hipStream_t s) {
+    const bool split = SPLIT == 3;
+    bool done = false;
+    // counted NA epilogue: 16-bit modes (in the split mode it differs from the general one
+    // by up to 1.1e-4 in the decoder output, tools/counted_bisect.py; not bitwise: kept off)
+    if (done) {}
+    else if ((res_counted & 4) && SPLIT == 1 && occ_fused == 2 && p.bias && p.N % 48 == 0 && p.ldch % 4 == 0) {
+      // (64-row tiles at 3 blocks per CU at every size: 32.5 -> 31.4 ms per C2 step against 128-row
+      // tiles for the large launches, round 6, profiles/r06_ffn_rows_na_tile_ab.txt; bitwise equal)
+      if (SPLIT == 1)
+        launch_gemm<64, 96, 2, 2, SPLIT, EPI_NA, 2, 3, GEMM_BK, 0, 0, 0, 3>(p, 1, s, "gemm_bf16_na", true, gridx_fused);
+      else
+        launch_gemm<128, 96, 2, 2, SPLIT, EPI_NA, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, split ? "gemm_fp32_na" : "gemm_bf16_na", true, gridx_fused);
+    }
+    else if (occ_fused == 2) launch_gemm<128, 96, 2, 2, SPLIT, EPI_NA, 2, 2>(p, 1, s, split ? "gemm_fp32_na" : "gemm_bf16_na", true, gridx_fused);
+    else launch_gemm<128, 96, 2, 2, SPLIT, EPI_NA, 2, 1>(p, 1, s, split ? "gemm_fp32_na" : "gemm_bf16_na", true, gridx_fused);
+  }
+  // SelfAttention value projection (EPI_TRANS); sa_split: the fp16 parity mode's a . (w_hi + w_lo)
+  template <int SPLIT>
+  void launch_value_t(const GemmParams& p, bool sa_split, bool has_lo, hipStream_t s) {
+    const bool split = SPLIT == 3;
+    // N = 48 (64 padded): 64-row tiles give 2x the blocks of a 128-row grid (one tile column)
+    if (sa_split) {                    // fp16 parity mode: a . (w_hi + w_lo)
+      ZV_REQUIRE(has_lo && (res_counted & 16), "weight-split value projection");
+      launch_gemm<64, 64, 2, 2, 2, EPI_TRANS, ZV_WSPLIT_T_STAGES, ZV_WSPLIT_T_STAGES < 4 ? 2 : 1, GEMM_BK, 0, 0, 0, 3>(
+          p, 1, s, "gemm_wsplit_t", true, -1);
+    } else if (skinny_tiles && (res_counted & 16))
+      // (a 4-deep K ring: one 64-row tile per block has 8 K steps and little else in flight;
+      // 2 -> 4 stages: 24.0 -> 18.9 ms per C2 step, profiles/r05_vt_stages_ab.txt)
+      launch_gemm<64, 64, 2, 2, SPLIT, EPI_TRANS, 4, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, split ? "gemm_fp32_t" : "gemm_bf16_t", true, -1);
+    else if (skinny_tiles) launch_gemm<64, 64, 2, 2, SPLIT, EPI_TRANS>(p, 1, s, split ? "gemm_fp32_t" : "gemm_bf16_t", true, -1);
+    else launch_gemm<128, 64, 2, 2, SPLIT, EPI_TRANS>(p, 1, s, split ? "gemm_fp32_t" : "gemm_bf16_t");
+  }
+  // ConvolutionModule in-projection (EPI_GLU: rows permuted by perm_glu); g8: MX-fp8 operands
+  template <int SPLIT>
+  void launch_glu_in(const GemmParams& p, bool g8, hipStream_t s) {
+    const bool split = SPLIT == 3;
+    bool done = false;
+    if (g8) {
+      ZV_REQUIRE(p.bias && p.N % 32 == 0 && p.ldch % 8 == 0, "fp8 GLU linear layout");
+      launch_gemm<128, 128, 2, 2, 8, EPI_GLU, 2, 2, MX8_KSTEP, 0, 0, 0, 3>(p, 1, s, "gemm_fp8_glu", true, gridx_fused);
+      done = true;
+    }
+    if constexpr (SPLIT == 1)
+      if (!done && (res_counted & 8) && p.bias && p.N % 32 == 0 && p.ldch % 8 == 0 && use_gemm256(p)) {
+        launch_gemm256<EPI_GLU, 3>(p, s, "gemm_bf16_glu", gemm256 == 1);
+        done = true;
+      }
+    if (done) {}
+    else if ((res_counted & 8) && occ_fused == 2 && p.bias && p.N % 32 == 0 && p.ldch % 8 == 0) {
+      // (fewer than 1.5 128 x 128 tiles per CU: 64 x 128, 3 blocks per CU, as launch_resid)
+      if (SPLIT == 1 && (long)cdiv(p.M, 128) * cdiv(p.N, 128) < zv_num_cus() * 3 / 2)
+        launch_gemm<64, 128, 2, 2, SPLIT, EPI_GLU, 2, 3, GEMM_BK, 0, 0, 0, 3>(p, 1, s, "gemm_bf16_glu", true, gridx_fused);
+      else
+        launch_gemm<128, 128, 2, 2, SPLIT, EPI_GLU, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, split ? "gemm_fp32_glu" : "gemm_bf16_glu", true, gridx_fused);
+    }
+    else if (occ_fused == 2) launch_gemm<128, 128, 2, 2, SPLIT, EPI_GLU, 2, 2>(p, 1, s, split ? "gemm_fp32_glu" : "gemm_bf16_glu", true, gridx_fused);
+    else launch_gemm<128, 128, 2, 2, SPLIT, EPI_GLU, 2, 1>(p, 1, s, split ? "gemm_fp32_glu" : "gemm_bf16_glu", true, gridx_fused);
+  }
+
   // ---------------------------------------------------------------- one layer
   // Zipformer2EncoderLayer.forward at inference (zipformer.py:489-642).
   // src/src_a: layer input (kept as src_orig, overwritten with the output);
@@ -1185,20 +1248,7 @@ struct zv_engine {
       GemmParams p = gp_linear(W.na_in, cur_a, M);
       p.Ch = y.h; p.Cl = y.l; p.ldch = y.ld;
       p.Cth = xt.h; p.Ctl = xt.l; p.ldct = Lpad; p.rpb = L; p.sCt = (long)hid * Lpad;
-      bool done = false;
-      // counted NA epilogue: 16-bit modes (in the split mode it differs from the general one
-      // by up to 1.1e-4 in the decoder output, tools/counted_bisect.py; not bitwise: kept off)
-      if (done) {}
-      else if ((res_counted & 4) && SPLIT == 1 && occ_fused == 2 && p.bias && W.na_in.N % 48 == 0 && p.ldch % 4 == 0) {
-        // (64-row tiles at 3 blocks per CU at every size: 32.5 -> 31.4 ms per C2 step against 128-row
-        // tiles for the large launches, round 6, profiles/r06_ffn_rows_na_tile_ab.txt; bitwise equal)
-        if (SPLIT == 1)
-          launch_gemm<64, 96, 2, 2, SPLIT, EPI_NA, 2, 3, GEMM_BK, 0, 0, 0, 3>(p, 1, s, "gemm_bf16_na", true, gridx_fused);
-        else
-          launch_gemm<128, 96, 2, 2, SPLIT, EPI_NA, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, split ? "gemm_fp32_na" : "gemm_bf16_na", true, gridx_fused);
-      }
-      else if (occ_fused == 2) launch_gemm<128, 96, 2, 2, SPLIT, EPI_NA, 2, 2>(p, 1, s, split ? "gemm_fp32_na" : "gemm_bf16_na", true, gridx_fused);
-      else launch_gemm<128, 96, 2, 2, SPLIT, EPI_NA, 2, 1>(p, 1, s, split ? "gemm_fp32_na" : "gemm_bf16_na", true, gridx_fused);
+      launch_na_in<SPLIT>(p, s);
       Act nao = ws.na_o.get(M, round_up(hid, 64), split, f8, hid);
       if (materialize) {
         GemmParams q{};
@@ -1260,17 +1310,7 @@ struct zv_engine {
       if (kcat) { o = dwo; o.h += D; }               // columns [D, D + HV) of [dw | o]
       GemmParams p = gp_linear(W.sa_in[a], cur_a, M);
       p.Cth = vt.h; p.Ctl = vt.l; p.ldct = Lpad; p.rpb = L; p.sCt = (long)VR * Lpad;
-      // N = 48 (64 padded): 64-row tiles give 2x the blocks of a 128-row grid (one tile column)
-      if (sa_split) {                    // fp16 parity mode: a . (w_hi + w_lo)
-        ZV_REQUIRE(W.sa_in[a].lo && (res_counted & 16), "weight-split value projection");
-        launch_gemm<64, 64, 2, 2, 2, EPI_TRANS, ZV_WSPLIT_T_STAGES, ZV_WSPLIT_T_STAGES < 4 ? 2 : 1, GEMM_BK, 0, 0, 0, 3>(
-            p, 1, s, "gemm_wsplit_t", true, -1);
-      } else if (skinny_tiles && (res_counted & 16))
-        // (a 4-deep K ring: one 64-row tile per block has 8 K steps and little else in flight;
-        // 2 -> 4 stages: 24.0 -> 18.9 ms per C2 step, profiles/r05_vt_stages_ab.txt)
-        launch_gemm<64, 64, 2, 2, SPLIT, EPI_TRANS, 4, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, split ? "gemm_fp32_t" : "gemm_bf16_t", true, -1);
-      else if (skinny_tiles) launch_gemm<64, 64, 2, 2, SPLIT, EPI_TRANS>(p, 1, s, split ? "gemm_fp32_t" : "gemm_bf16_t", true, -1);
-      else launch_gemm<128, 64, 2, 2, SPLIT, EPI_TRANS>(p, 1, s, split ? "gemm_fp32_t" : "gemm_bf16_t");
+      launch_value_t<SPLIT>(p, sa_split, W.sa_in[a].lo != nullptr, s);
       if (materialize) {
         GemmParams q{};
         q.M = L; q.N = vd; q.K = L; q.nz2 = B; q.Brows = vd;
@@ -1344,27 +1384,7 @@ struct zv_engine {
       Act g = ws.glu.get(M, D, split);
       GemmParams p = g8 ? gp_linear8(W.conv_in[c], cur_a, M) : gp_linear(W.conv_in[c], cur_a, M);
       p.Ch = g.h; p.Cl = g.l; p.ldch = g.ld; p.rowmask = pad;
-      bool done = false;
-      if (g8) {
-        ZV_REQUIRE(p.bias && W.conv_in[c].N % 32 == 0 && p.ldch % 8 == 0, "fp8 GLU linear layout");
-        launch_gemm<128, 128, 2, 2, 8, EPI_GLU, 2, 2, MX8_KSTEP, 0, 0, 0, 3>(p, 1, s, "gemm_fp8_glu", true, gridx_fused);
-        done = true;
-      }
-      if constexpr (SPLIT == 1)
-        if (!done && (res_counted & 8) && p.bias && W.conv_in[c].N % 32 == 0 && p.ldch % 8 == 0 && use_gemm256(p)) {
-          launch_gemm256<EPI_GLU, 3>(p, s, "gemm_bf16_glu", gemm256 == 1);
-          done = true;
-        }
-      if (done) {}
-      else if ((res_counted & 8) && occ_fused == 2 && p.bias && W.conv_in[c].N % 32 == 0 && p.ldch % 8 == 0) {
-        // (fewer than 1.5 128 x 128 tiles per CU: 64 x 128, 3 blocks per CU, as launch_resid)
-        if (SPLIT == 1 && (long)cdiv(p.M, 128) * cdiv(p.N, 128) < zv_num_cus() * 3 / 2)
-          launch_gemm<64, 128, 2, 2, SPLIT, EPI_GLU, 2, 3, GEMM_BK, 0, 0, 0, 3>(p, 1, s, "gemm_bf16_glu", true, gridx_fused);
-        else
-          launch_gemm<128, 128, 2, 2, SPLIT, EPI_GLU, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, split ? "gemm_fp32_glu" : "gemm_bf16_glu", true, gridx_fused);
-      }
-      else if (occ_fused == 2) launch_gemm<128, 128, 2, 2, SPLIT, EPI_GLU, 2, 2>(p, 1, s, split ? "gemm_fp32_glu" : "gemm_bf16_glu", true, gridx_fused);
-      else launch_gemm<128, 128, 2, 2, SPLIT, EPI_GLU, 2, 1>(p, 1, s, split ? "gemm_fp32_glu" : "gemm_bf16_glu", true, gridx_fused);
+      launch_glu_in<SPLIT>(p, g8, s);
       Act dw = kcat ? dwo : ws.dw.get(M, D, split, f8, D);
       const bool dq = f8 && (fp8_fuse & 2);
       launch_dwconv(g.h, g.l, g.ld, W.dw_w[c], W.dw_b[c], dw.h, dw.l, dw.ld, B, L, D, W.ks, s,
@@ -1402,7 +1422,6 @@ struct zv_engine {
       q.byp = W.bypass; q.nb = W.norm_bias; q.log_scale = W.norm_log_scale;
       g.rowvec = temb; q.rowvec_ld = D; q.rows_per_group = L;
       g.C2h = has_next ? cur_a.h : nullptr; g.C2l = has_next ? cur_a.l : nullptr;
-      g.C2 = nullptr;
       ffn_site(q, ws, s, "ffn_norm_bf16");
     } else {                                          // FF3: only the fp32 stream feeds BiasNorm
       Out e = res;                                    // (which rewrites both copies): no bf16 copy
@@ -2354,6 +2373,271 @@ int zv_gemm_selftest(int M, int N, int K, int variant, int mode, float* maxdiff,
   *maxdiff = h[0]; *maxref = h[1];
   for (void* q : {(void*)A, (void*)W, (void*)C0, (void*)C1, (void*)R, (void*)res}) ZV_CHECK(ZV_BLOCKING(hipFree(q)));
   if (extra) ZV_CHECK(ZV_BLOCKING(hipFree(extra)));
+  ZV_API_END
+}
+
+// ---------------------------------------------------------------------------
+// zv_linear_check / zv_ffn_check (test infrastructure): one linear through the engine's dispatch,
+// and the fused FeedForward alone, on host arrays with canary-guarded outputs
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+struct ChkDev {   // the device buffers of one check call, freed when it returns or throws
+  std::vector<void*> ptrs;
+  void* raw(size_t bytes) {
+    void* p = nullptr;
+    ZV_CHECK(ZV_BLOCKING(hipMalloc(&p, bytes + 256)));
+    ptrs.push_back(p);
+    return p;
+  }
+  template <typename T> T* up(const T* host, size_t n) {
+    T* d = reinterpret_cast<T*>(raw(n * sizeof(T)));
+    ZV_CHECK(ZV_BLOCKING(hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice)));
+    return d;
+  }
+  template <typename T> void down(T* host, const T* dev, size_t n) {
+    ZV_CHECK(ZV_BLOCKING(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost)));
+  }
+  ~ChkDev() { for (void* p : ptrs) (void)ZV_BLOCKING(hipFree(p)); }
+};
+// an activation as the engine's producers write it: (rows, ld) 16-bit hi (+ lo), zero beyond cols
+void chk_act(const float* x, long rows, int cols, long ld, bool lo, std::vector<bf16>& h, std::vector<bf16>& l) {
+  h.assign((size_t)rows * ld, (bf16)0.f);
+  if (lo) l.assign((size_t)rows * ld, (bf16)0.f);
+  for (long r = 0; r < rows; ++r)
+    for (int c = 0; c < cols; ++c) {
+      const float v = x[r * cols + c];
+      const bf16 hv = (bf16)v;
+      h[(size_t)r * ld + c] = hv;
+      if (lo) l[(size_t)r * ld + c] = (bf16)(v - (float)hv);
+    }
+}
+// a (rows, cols) fp32 host array re-laid with row stride ld (zero padding)
+std::vector<float> chk_pad(const float* x, long rows, int cols, long ld) {
+  std::vector<float> v((size_t)rows * ld, 0.f);
+  for (long r = 0; r < rows; ++r) memcpy(&v[(size_t)r * ld], x + r * cols, (size_t)cols * sizeof(float));
+  return v;
+}
+void chk_record(int* launch, int* num_cus) {
+  const ZvLaunchRec& r = g_zv_last_launch;
+  const int v[8] = {r.BM, r.BN, r.SPLIT, r.EPI, r.ROLE, r.k256, r.grid, r.aux};
+  memcpy(launch, v, sizeof(v));
+  *num_cus = zv_num_cus();
+}
+}  // namespace
+}  // extern "C++"
+
+int zv_linear_check(zv_linear_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && a->M > 0 && a->N > 0 && a->K > 0 && a->A && a->W && a->bias && a->guard >= 0 &&
+                 (a->split == 1 || a->split == 2 || a->split == 3) && a->form >= ZV_LIN_PLAIN &&
+                 a->form <= ZV_LIN_GLU,
+             "zv_linear_check: bad arguments");
+  const int M = a->M, N = a->N, K = a->K, form = a->form, G = a->guard;
+  const bool split3 = a->split == 3;
+  const bool fused = form >= ZV_LIN_TRANS;
+  const bool resid = form >= ZV_LIN_RESID && form <= ZV_LIN_RESID_RV_COPY;
+  const bool rv = form == ZV_LIN_RESID_RV || form == ZV_LIN_RESID_RV_COPY;
+  const bool wantC = form == ZV_LIN_PLAIN_F32 || (resid && form != ZV_LIN_RESID_RV_COPY);
+  const bool wantT = form == ZV_LIN_TRANS || form == ZV_LIN_NA;
+  ZV_REQUIRE(a->split != 2 || (form == ZV_LIN_PLAIN && !a->act) || form == ZV_LIN_TRANS,
+             "zv_linear_check: split 2 is the plain form without activation, or TRANS");
+  ZV_REQUIRE(wantC == (a->C != nullptr) && (!a->C || a->ldc >= N) && (!resid || a->resid) &&
+                 (form != ZV_LIN_RESID_BYP || (a->orig && a->byp)) &&
+                 (!rv || (a->rowvec && a->rows_per_group > 0)) && (form != ZV_LIN_RESID_RV_COPY || a->ldc >= N),
+             "zv_linear_check: the form's fp32 operands");
+  const int wch = form == ZV_LIN_NA ? N / 3 : form == ZV_LIN_GLU ? N / 2 : N;   // width of Ch
+  const bool needCh = form == ZV_LIN_PLAIN || form == ZV_LIN_RESID_RV_COPY || form == ZV_LIN_NA || form == ZV_LIN_GLU;
+  ZV_REQUIRE((!needCh || a->Ch) && (form != ZV_LIN_PLAIN_F32 || !a->Ch) && (form != ZV_LIN_TRANS || !a->Ch) &&
+                 (!a->Ch || a->ldch >= wch) && (a->Cl != nullptr) == (split3 && a->Ch != nullptr),
+             "zv_linear_check: the form's 16-bit outputs (Cl with split 3 only)");
+  ZV_REQUIRE(wantT == (a->Cth != nullptr) && (!wantT || (a->rpb > 0 && a->ldct >= a->rpb)) &&
+                 (a->Ctl != nullptr) == (split3 && wantT),
+             "zv_linear_check: the transposed outputs");
+  ZV_REQUIRE((form != ZV_LIN_NA || N % 48 == 0) && (form != ZV_LIN_GLU || N % 32 == 0), "zv_linear_check: NA / GLU widths");
+
+  zv_config c{};
+  c.precision = split3 ? ZV_FP32 : (a->split == 2 ? ZV_MIXED : ZV_BF16);
+  zv_engine eng(c);                       // a bare engine: its dispatch policy and weight builder
+  eng.staged["chk.weight"].assign(a->W, a->W + (size_t)N * K);
+  eng.staged["chk.bias"].assign(a->bias, a->bias + N);
+  std::vector<int> perm;
+  if (form == ZV_LIN_NA) perm = zv_engine::perm_na(N / 3);
+  if (form == ZV_LIN_GLU) perm = zv_engine::perm_glu(N / 2);
+  const Linear Lw = eng.make_linear("chk", N, K, true, false, perm.empty() ? nullptr : &perm);
+
+  ChkDev dev;
+  hipStream_t s = nullptr;
+  Act A;
+  {
+    std::vector<bf16> h, l;
+    A.ld = round_up(K, 64);
+    chk_act(a->A, M, K, A.ld, split3, h, l);
+    A.h = dev.up(h.data(), h.size());
+    if (split3) A.l = dev.up(l.data(), l.size());
+  }
+  const long rows = (long)M + 2 * G;
+  float* dC = nullptr;
+  bf16 *dCh = nullptr, *dCl = nullptr, *dCth = nullptr, *dCtl = nullptr;
+  const int nutt = wantT ? cdiv(M, a->rpb) : 0, rows_t = form == ZV_LIN_NA ? N / 3 : N;
+  const long trows = wantT ? (long)nutt * rows_t + 2 * G : 0;
+  if (a->C) {
+    std::vector<float> hc(a->C, a->C + (size_t)rows * a->ldc);
+    if (resid)
+      for (long m = 0; m < M; ++m)
+        memcpy(&hc[(size_t)(G + m) * a->ldc], a->resid + m * N, (size_t)N * sizeof(float));
+    dC = dev.up(hc.data(), hc.size());
+  }
+  if (a->Ch) dCh = reinterpret_cast<bf16*>(dev.up(a->Ch, (size_t)rows * a->ldch));
+  if (a->Cl) dCl = reinterpret_cast<bf16*>(dev.up(a->Cl, (size_t)rows * a->ldch));
+  if (a->Cth) dCth = reinterpret_cast<bf16*>(dev.up(a->Cth, (size_t)trows * a->ldct));
+  if (a->Ctl) dCtl = reinterpret_cast<bf16*>(dev.up(a->Ctl, (size_t)trows * a->ldct));
+  const uint8_t* dmask = a->rowmask ? dev.up(a->rowmask, (size_t)M) : nullptr;
+
+  if (!fused) {
+    zv_engine::Out o;
+    o.act_fn = a->act;
+    if (dC) { o.C = dC + (size_t)G * a->ldc; o.ldc = a->ldc; }
+    if (dCh) { o.act.h = dCh + (size_t)G * a->ldch; o.act.ld = a->ldch; }
+    if (dCl) o.act.l = dCl + (size_t)G * a->ldch;
+    if (resid) {
+      if (o.C) {
+        o.resid = o.C;                     // in place, as the engine updates its stream
+      } else {
+        o.ldc = a->ldc;
+        std::vector<float> r = chk_pad(a->resid, M, N, a->ldc);
+        o.resid = dev.up(r.data(), r.size());
+      }
+    }
+    if (form == ZV_LIN_RESID_BYP) {
+      std::vector<float> og = chk_pad(a->orig, M, N, a->ldc);
+      o.orig = dev.up(og.data(), og.size());
+      o.byp = dev.up(a->byp, (size_t)N);
+    }
+    if (rv) {
+      o.rowvec = dev.up(a->rowvec, (size_t)cdiv(M, a->rows_per_group) * N);
+      o.rowvec_ld = N; o.rows_per_group = a->rows_per_group;
+    }
+    if (a->split == 2) eng.attn_in_wsplit(Lw, A, M, o, s);
+    else if (split3) eng.linear16<3>(Lw, A, M, o, s);
+    else eng.linear16<1>(Lw, A, M, o, s);
+  } else {
+    GemmParams p = zv_engine::gp_linear(Lw, A, M);
+    if (a->split == 2) p.Al = nullptr;
+    if (dCh) { p.Ch = dCh + (size_t)G * a->ldch; p.ldch = a->ldch; }
+    if (dCl) p.Cl = dCl + (size_t)G * a->ldch;
+    if (wantT) {
+      p.Cth = dCth + (size_t)G * a->ldct;
+      if (dCtl) p.Ctl = dCtl + (size_t)G * a->ldct;
+      p.ldct = a->ldct; p.rpb = a->rpb; p.sCt = (long)rows_t * a->ldct;
+    }
+    if (form == ZV_LIN_GLU) p.rowmask = dmask;
+    if (form == ZV_LIN_NA) {
+      if (split3) eng.launch_na_in<3>(p, s); else eng.launch_na_in<1>(p, s);
+    } else if (form == ZV_LIN_TRANS) {
+      if (split3) eng.launch_value_t<3>(p, false, true, s);
+      else eng.launch_value_t<1>(p, a->split == 2, Lw.lo != nullptr, s);
+    } else {
+      if (split3) eng.launch_glu_in<3>(p, false, s); else eng.launch_glu_in<1>(p, false, s);
+    }
+  }
+  ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+  chk_record(a->launch, &a->num_cus);
+  if (a->C) dev.down(a->C, dC, (size_t)rows * a->ldc);
+  if (a->Ch) dev.down(a->Ch, reinterpret_cast<uint16_t*>(dCh), (size_t)rows * a->ldch);
+  if (a->Cl) dev.down(a->Cl, reinterpret_cast<uint16_t*>(dCl), (size_t)rows * a->ldch);
+  if (a->Cth) dev.down(a->Cth, reinterpret_cast<uint16_t*>(dCth), (size_t)trows * a->ldct);
+  if (a->Ctl) dev.down(a->Ctl, reinterpret_cast<uint16_t*>(dCtl), (size_t)trows * a->ldct);
+  ZV_API_END
+}
+
+int zv_ffn_check(zv_ffn_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && a->M > 0 && a->H > 0 && a->H % (2 * FFN_HC) == 0 && a->form >= 0 && a->form <= 3 &&
+                 a->guard >= 0 && a->part_slots >= 0 && a->x && a->W1 && a->b1 && a->W2 && a->b2 &&
+                 a->resid && a->C && a->ldc >= FFN_D && (!a->Ch || a->ldch >= FFN_D),
+             "zv_ffn_check: bad arguments");
+  const int M = a->M, H = a->H, form = a->form, G = a->guard, D = FFN_D;
+  const bool norm = form == 3, byp = form == 2 || norm, rv = a->rowvec != nullptr;
+  ZV_REQUIRE((form == 1) == (rv && !norm) || norm, "zv_ffn_check: the row vector belongs to form 1 (or 3)");
+  ZV_REQUIRE((!rv || a->rows_per_group > 0) && (!byp || (a->orig && a->byp)) && (!norm || a->nb) &&
+                 (form == 0 || a->Ch) && (norm || (!a->Cl && !a->C2h && !a->C2l)) &&
+                 (!a->C2l || a->C2h),
+             "zv_ffn_check: the form's operands");
+  ZV_REQUIRE(a->part_slots <= zv_num_cus(), "zv_ffn_check: more lines than CUs");
+  zv_config c{};
+  c.precision = ZV_BF16;
+  zv_engine eng(c);
+  eng.staged["w1.weight"].assign(a->W1, a->W1 + (size_t)H * D);
+  eng.staged["w1.bias"].assign(a->b1, a->b1 + H);
+  eng.staged["w2.weight"].assign(a->W2, a->W2 + (size_t)D * H);
+  eng.staged["w2.bias"].assign(a->b2, a->b2 + D);
+  const Linear L1 = eng.make_linear("w1", H, D, true, false);
+  const Linear L2 = eng.make_linear("w2", D, H, true, false);
+  ChkDev dev;
+  hipStream_t s = nullptr;
+  const long n = (long)H * D;
+  bf16* w1f = reinterpret_cast<bf16*>(dev.raw((size_t)n * sizeof(bf16)));
+  bf16* w2f = reinterpret_cast<bf16*>(dev.raw((size_t)n * sizeof(bf16)));
+  hipLaunchKernelGGL(zv_ffn_pack_w1_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, L1.hi, (long)L1.Kpad, H, w1f);
+  hipLaunchKernelGGL(zv_ffn_pack_w2_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, L2.hi, (long)L2.Kpad, H, w2f);
+  ZV_LAUNCH_CHECK();
+  FfnParams q{};
+  q.H = H; q.nseg = 1;
+  FfnSeg& g = q.seg[0];
+  g.M = M;
+  {
+    std::vector<bf16> h, l;
+    chk_act(a->x, M, D, D, false, h, l);
+    g.X = dev.up(h.data(), h.size());
+    q.ldx = D;
+  }
+  q.W1f = w1f; q.b1 = L1.b; q.W2f = w2f; q.b2 = L2.b;
+  const long rows = (long)M + 2 * G;
+  // C: resid in its interior (in place), or for the BiasNorm epilogue orig (C == orig, resid apart)
+  std::vector<float> hc(a->C, a->C + (size_t)rows * a->ldc);
+  for (long m = 0; m < M; ++m)
+    memcpy(&hc[(size_t)(G + m) * a->ldc], (norm ? a->orig : a->resid) + m * D, (size_t)D * sizeof(float));
+  float* dC = dev.up(hc.data(), hc.size());
+  g.C = dC + (size_t)G * a->ldc; q.ldc = a->ldc;
+  auto padded = [&](const float* x) {
+    std::vector<float> v = chk_pad(x, M, D, a->ldc);
+    return dev.up(v.data(), v.size());
+  };
+  if (norm) { g.resid = padded(a->resid); g.orig = g.C; }
+  else { g.resid = g.C; if (byp) g.orig = padded(a->orig); }
+  if (byp) q.byp = dev.up(a->byp, (size_t)D);
+  if (norm) { q.nb = dev.up(a->nb, (size_t)D); q.log_scale = a->log_scale; }
+  if (rv) {
+    g.rowvec = dev.up(a->rowvec, (size_t)cdiv(M, a->rows_per_group) * D);
+    q.rowvec_ld = D; q.rows_per_group = a->rows_per_group;
+  }
+  uint16_t* host16[4] = {a->Ch, a->Cl, a->C2h, a->C2l};
+  bf16* dev16[4] = {};
+  for (int i = 0; i < 4; ++i)
+    if (host16[i]) dev16[i] = reinterpret_cast<bf16*>(dev.up(host16[i], (size_t)rows * a->ldch));
+  q.ldch = a->Ch ? a->ldch : 0;
+  auto inner = [&](bf16* p) { return p ? p + (size_t)G * a->ldch : nullptr; };
+  g.Ch = inner(dev16[0]); g.Cl = inner(dev16[1]); g.C2h = inner(dev16[2]); g.C2l = inner(dev16[3]);
+  if (a->part_slots > 0) {   // the persistent line schedule's scratch, zero-filled
+    q.part_slots = a->part_slots;
+    q.part = reinterpret_cast<float*>(dev.raw((size_t)a->part_slots * FFN_PART_FLOATS * sizeof(float)));
+    q.flag = reinterpret_cast<unsigned*>(dev.raw(((size_t)a->part_slots + 64) * sizeof(unsigned)));
+    ZV_CHECK(ZV_BLOCKING(hipMemset(q.part, 0, (size_t)a->part_slots * FFN_PART_FLOATS * sizeof(float))));
+    ZV_CHECK(ZV_BLOCKING(hipMemset(q.flag, 0, ((size_t)a->part_slots + 64) * sizeof(unsigned))));
+  }
+  ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+  launch_ffn(q, s, norm ? "ffn_norm_check" : "ffn_check");
+  ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+  chk_record(a->launch, &a->num_cus);
+  volatile unsigned* e = zv_dev_err_host();
+  if (*e != 0) {
+    *e = 0;
+    throw std::runtime_error("zv_ffn_check: the device error word was set (a C item outwaited its producer)");
+  }
+  dev.down(a->C, dC, (size_t)rows * a->ldc);
+  for (int i = 0; i < 4; ++i)
+    if (host16[i]) dev.down(host16[i], reinterpret_cast<uint16_t*>(dev16[i]), (size_t)rows * a->ldch);
   ZV_API_END
 }
 

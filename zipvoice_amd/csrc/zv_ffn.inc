@@ -79,7 +79,7 @@ struct FfnSeg {                    // one row range and its own operand pointers
   bf16* Ch;                        // the stream's 16-bit copy (or null)
   const float* rowvec;             // row vector (row r adds rowvec[r / rows_per_group])
   const float* orig;               // bypass original
-  bf16* Cl; bf16* C2h; bf16* C2l; float* C2;   // NORM outputs
+  bf16* Cl; bf16* C2h; bf16* C2l;   // NORM outputs
 };
 
 struct FfnParams {
@@ -93,7 +93,7 @@ struct FfnParams {
   // NORM epilogue (FF3 + the layer's BiasNorm + bypass, zipformer.py:610-618, scaling.py:330-355):
   // x = resid + FF(x) is never stored; out = orig + (x * rsqrt(mean((x - nb)^2)) e^log_scale - orig)
   // * byp -> C (fp32, in place over orig) and Ch / Cl (16-bit hi / lo copy); out + rowvec ->
-  // C2h / C2l (the next layer's working-stream copy) and C2 (fp32) where non-null
+  // C2h / C2l (the next layer's working-stream copy) where non-null
   const float* nb; float log_scale;
   float norm_scale;                // exp(log_scale), set by launch_ffn
   float* sink;
@@ -826,14 +826,12 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
       bf16* Clp = S.Cl;
       bf16* C2hp = S.C2h;
       bf16* C2lp = S.C2l;
-      float* C2p = S.C2;
-      asm volatile("" : "+s"(Clp), "+s"(C2hp), "+s"(C2lp), "+s"(C2p));
+      asm volatile("" : "+s"(Clp), "+s"(C2hp), "+s"(C2lp));
       const __amdgpu_buffer_rsrc_t rs_c = rsrc(Cp + (long)t0 * p.ldc, p.ldc, 4);
       const __amdgpu_buffer_rsrc_t rs_h = rsrc(Chp + (long)t0 * p.ldch, p.ldch, 2);
       const __amdgpu_buffer_rsrc_t rs_l = rsrc(Clp ? Clp + (long)t0 * p.ldch : nullptr, p.ldch, 2);
       const __amdgpu_buffer_rsrc_t rs_2h = rsrc(C2hp ? C2hp + (long)t0 * p.ldch : nullptr, p.ldch, 2);
       const __amdgpu_buffer_rsrc_t rs_2l = rsrc(C2lp ? C2lp + (long)t0 * p.ldch : nullptr, p.ldch, 2);
-      const __amdgpu_buffer_rsrc_t rs_2 = rsrc(C2p ? C2p + (long)t0 * p.ldc : nullptr, p.ldc, 4);
       const int hoff = (lr * (int)p.ldch + 4 * lc) * 2, hstep = 2 * (int)p.ldch * 2;
       // the next layer's copy adds the row vector (the wave's two row groups, staged in LDS)
       const int rv_b = nrv ? (nrv_g0 + 1) * p.rows_per_group - t0 : 1 << 30;   // first row of the second group
@@ -886,7 +884,6 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
               for (int e = 0; e < 4; ++e) l[e] = (bf16)(y[e] - (float)h[e]);
               __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, l), rs_2l, hoff, ho, 0);
             }
-            if (C2p) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32_t, y), rs_2, toff, fo, 0);
           }
           __builtin_amdgcn_sched_barrier(0);   // (the loads stay PT ahead, not hoisted en bloc)
         });
@@ -943,8 +940,7 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
       bf16* Clp = S.Cl;
       bf16* C2hp = S.C2h;
       bf16* C2lp = S.C2l;
-      float* C2p = S.C2;
-      asm volatile("" : "+s"(Clp), "+s"(C2hp), "+s"(C2lp), "+s"(C2p));
+      asm volatile("" : "+s"(Clp), "+s"(C2hp), "+s"(C2lp));
       // (a 16-bit output's per-lane address: the row's, or the sink's for rows past M)
       auto adr16 = [&](bf16* base, long oh) {
         unsigned long long a = row_ok ? (unsigned long long)(base + oh) : (unsigned long long)(p.sink + 512 + lane * 4);
@@ -999,10 +995,6 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
           if (row_ok) {
             *reinterpret_cast<bf16x8*>(C2hp + oh) = h;
             if (C2lp) *reinterpret_cast<bf16x8*>(C2lp + oh) = l;
-            if (C2p) {
-              *reinterpret_cast<f32x4*>(C2p + o) = f32x4{y[0], y[1], y[2], y[3]};
-              *reinterpret_cast<f32x4*>(C2p + o + 4) = f32x4{y[4], y[5], y[6], y[7]};
-            }
           }
         }
       });
@@ -1205,11 +1197,13 @@ static void launch_ffn_t(const FfnParams& p, int blocks, hipStream_t s, const ch
   for (int i = 0; i < p.nseg; ++i) {
     const FfnSeg& g = p.seg[i];
     M += g.M;
-    if (NORM) extra += (double)g.M * FFN_D * ((g.Cl ? 2 : 0) + (g.C2h ? 2 : 0) + (g.C2l ? 2 : 0) + (g.C2 ? 4 : 0));
+    if (NORM) extra += (double)g.M * FFN_D * ((g.Cl ? 2 : 0) + (g.C2h ? 2 : 0) + (g.C2l ? 2 : 0));
   }
   const double outs = M * FFN_D;
   const double bytes = outs * 2 + 2.0 * FFN_D * p.H * 2 +
                        (NORM ? outs * (4 + 4 + 4 + 2) + extra : outs * (8 + (COPY ? 2 : 0) + (ORIG ? 4 : 0)));
+  g_zv_last_launch = ZvLaunchRec{FFN_BM, FFN_D, 1, (int)RV | (int)ORIG << 1 | (int)COPY << 2 | (int)TP << 3, NORM,
+                                 0, blocks, p.w};
   ZvProfScope prof(tag, 4.0 * M * FFN_D * (double)p.H, bytes, s);
   hipLaunchKernelGGL((zv_ffn_kernel<RV, ORIG, COPY, ABL, NORM, TP>), dim3(blocks), dim3(256), lds, s, p);
   ZV_LAUNCH_CHECK();
@@ -1253,7 +1247,7 @@ static void launch_ffn(FfnParams p, hipStream_t s, const char* tag, int blocks_m
   p.w = sc.w;
   if (p.nb) {   // FF3 + BiasNorm + bypass
     for (int i = 0; i < p.nseg; ++i)
-      ZV_REQUIRE(p.seg[i].orig && p.seg[i].C == p.seg[i].orig && p.seg[i].Ch && (!p.seg[i].C2 || p.seg[i].C2h),
+      ZV_REQUIRE(p.seg[i].orig && p.seg[i].C == p.seg[i].orig && p.seg[i].Ch,
                  "fused FeedForward + BiasNorm operands");
     ZV_REQUIRE(p.byp, "fused FeedForward + BiasNorm bypass");
     p.norm_scale = expf(p.log_scale);

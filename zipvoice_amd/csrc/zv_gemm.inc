@@ -1330,6 +1330,14 @@ static double gemm_alg_bytes(const GemmParams& p, int nz) {
   return 0.0;
 }
 
+// Host-only record of the calling thread's last GEMM / fused FeedForward launch (test
+// infrastructure: zv_linear_check / zv_ffn_check return it, so a test can tell which instantiation
+// the engine's dispatch chose for a shape).  Written by launch_gemm, launch_gemm256 and
+// launch_ffn_t; no kernel reads it.  ffn: EPI = RV | ORIG << 1 | COPY << 2 | TP << 3, ROLE = NORM,
+// aux = chunk steps per block (w); GEMMs: aux = STAGES * 16 + OCC (0 for the 256x256 kernel)
+struct ZvLaunchRec { int BM, BN, SPLIT, EPI, ROLE, k256, grid, aux; };
+static thread_local ZvLaunchRec g_zv_last_launch = {};
+
 template <int BM, int BN, int WGM, int WGN, int SPLIT, int EPI, int STAGES = 2, int OCC = 2,
           int BK = GEMM_BK, int DEFER = 0, int RP = 0, int CONV = 0, int ROLE = 0, int MXO = 0>
 static void launch_gemm(const GemmParams& p, int nz, hipStream_t s, const char* tag,
@@ -1384,6 +1392,7 @@ static void launch_gemm(const GemmParams& p, int nz, hipStream_t s, const char* 
     snprintf(dtag, sizeof(dtag), "%s M=%d N=%d K=%d z=%d tile=%dx%d", tag, p.M, p.N, p.K, nz, BM, BN);
     tag = dtag;
   }
+  g_zv_last_launch = ZvLaunchRec{BM, BN, SPLIT, EPI, ROLE, 0, G, STAGES * 16 + OCC};
   const double bytes = gemm_alg_bytes<SPLIT, ROLE, MXO>(p, nz);
   ZvProfScope prof(tag, 2.0 * p.M * p.N * (double)p.K * nz, bytes, s);
   hipLaunchKernelGGL((zv_gemm_kernel<BM, BN, WGM, WGN, SPLIT, EPI, STAGES, OCC, BK, DEFER, RP, CONV, ROLE, ZV_GEMM_PRELOAD, MXO>), dim3(G, 1, nz),

@@ -630,6 +630,7 @@ static void launch_gemm256(const GemmParams& p, hipStream_t s, const char* tag, 
   const double fl = 2.0 * p.M * p.N * (double)p.K + (DWK ? 2.0 * DWK * p.M * (p.N / 2) : 0.0);
   const double by = DWK ? 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * (p.N / 2))
                         : gemm_alg_bytes<1, ROLE, MXO>(p, 1);
+  g_zv_last_launch = ZvLaunchRec{256, 256, 1, EPI, ROLE, 1, G, 0};
   ZvProfScope prof(tag, fl, by, s);
   hipLaunchKernelGGL((zv_gemm256_kernel<EPI, ROLE, PB, MXO, DIRECT, DRAIN, DWK>), dim3(G), dim3(512),
                      DWK ? G256_DW_LDS : G256_LDS, s, pr);

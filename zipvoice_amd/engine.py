@@ -56,6 +56,28 @@ class ZvConfig(ctypes.Structure):
     ]
 
 
+class ZvLinearCheckArgs(ctypes.Structure):
+    """zv_linear_check_args (test infrastructure; tests/test_gpu_linear_ref.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("M", "N", "K", "split", "form", "act", "rows_per_group",
+                                            "rpb", "guard")] + [
+        (n, ctypes.c_void_p) for n in ("A", "W", "bias", "resid", "orig", "byp", "rowvec", "rowmask")] + [
+        ("C", ctypes.c_void_p), ("ldc", ctypes.c_int64),
+        ("Ch", ctypes.c_void_p), ("Cl", ctypes.c_void_p), ("ldch", ctypes.c_int64),
+        ("Cth", ctypes.c_void_p), ("Ctl", ctypes.c_void_p), ("ldct", ctypes.c_int64),
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+
+
+class ZvFfnCheckArgs(ctypes.Structure):
+    """zv_ffn_check_args (test infrastructure; tests/test_gpu_ffn_ref.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("M", "H", "form", "rows_per_group", "part_slots", "guard")] + [
+        ("log_scale", ctypes.c_float)] + [
+        (n, ctypes.c_void_p) for n in ("x", "W1", "b1", "W2", "b2", "resid", "rowvec", "orig", "byp", "nb")] + [
+        ("C", ctypes.c_void_p), ("ldc", ctypes.c_int64),
+        ("Ch", ctypes.c_void_p), ("Cl", ctypes.c_void_p), ("C2h", ctypes.c_void_p), ("C2l", ctypes.c_void_p),
+        ("ldch", ctypes.c_int64),
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+
+
 # symbol name -> (restype, argtypes); must match include/zipvoice_hip.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -72,6 +94,8 @@ SIGNATURES = {
     "zv_profile": (_I, [_I]),
     "zv_bench_gemm": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
     "zv_gemm_selftest": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "zv_linear_check": (_I, [ctypes.POINTER(ZvLinearCheckArgs)]),
+    "zv_ffn_check": (_I, [ctypes.POINTER(ZvFfnCheckArgs)]),
     "zv_profile_report": (_I, [ctypes.c_char_p, _I]),
     "zv_host_block_count": (ctypes.c_int64, []),
     "zv_attn_fallbacks": (_I, [_P, _I, _P]),
