@@ -38,6 +38,7 @@
  *                      log-mel front end feeding prompt_features (infer_zipvoice.py:328-337)
  *   zv_resample_*      torchaudio.transforms.Resample on the loaded prompt
  *                      (infer_zipvoice.py:332-338, infer_zipvoice_dialog.py:270-277, :417-422)
+ *   zv_wavjoin_*       no reference counterpart (long-form join, defined below)
  */
 #ifndef ZIPVOICE_HIP_H
 #define ZIPVOICE_HIP_H
@@ -443,6 +444,51 @@ void zv_resample_destroy(zv_resample_handle h);
 int zv_resample_apply(zv_resample_handle h, const float* wav, int64_t wav_ld, const int32_t* lens,
                       int R, float* out, int64_t out_ld, int64_t out_cols, void* stream);
 int64_t zv_resample_device_bytes(zv_resample_handle h);
+
+/* ------------------------------------------------------------------------
+ * Long-form join: trim the pauses of a batch of chunk waveforms and glue the trimmed
+ * chunks into one waveform with linear cross-fades (zipvoice_amd/longform.py WavJoiner,
+ * generate_long).  These entry points have NO reference counterpart: the reference has no
+ * long-form path, so the behaviour is defined here (tests/wavjoin_ref.py restates it in
+ * float64).  fp32 arithmetic, no atomics; results are bitwise reproducible and do not
+ * depend on the launch geometry.
+ *
+ * Frames.  Chunk b has nf = ceil(lens[b] / frame) frames; frame f covers samples
+ * [f * frame, min((f + 1) * frame, lens[b])) of every channel.  Its energy e is the fp32
+ * sum of squares over those samples and all C channels, in a fixed order; the frame is
+ * quiet iff e < thr^2 * (samples in the frame * C), loud otherwise.
+ * Kept frames.  A chunk without a loud frame is empty (m_b = 0).  Otherwise, with first /
+ * last its first / last loud frame, the frames in [max(0, first - keep_edge),
+ * min(nf - 1, last + keep_edge)] are kept, except that every maximal run of r > max_gap
+ * quiet frames strictly between first and last keeps only its first ceil(max_gap / 2) and
+ * last floor(max_gap / 2) frames.  The kept frames' samples, in order, are the trimmed
+ * chunk y_b of length m_b.
+ * Join.  Over the non-empty chunks in order: the first has F = 0 and off = 0; a chunk b
+ * after the non-empty chunk p overlaps it by F_b = min(fade, m_p / 2, m_b / 2) (integer
+ * halves) and starts at off_b = off_p + m_p - F_b; an empty chunk reports off = -1, F = 0.
+ * N = off_last + m_last (0 if every chunk is empty).  For j in [0, F_b), with
+ * w = (j + 1) / (F_b + 1):
+ *   out[off_b + j] = g_p * y_p[m_p - F_b + j] * (1 - w) + g_b * y_b[j] * w;
+ * everywhere else out = g_b * y_b, and with a gain of exactly 1 the sample is a bitwise
+ * copy of its input.  Columns [N, out_cap) are zero-filled; nothing is written at or past
+ * out_cap even when N > out_cap, and out_len always receives the true N.
+ *
+ * create rejects frame < 1 and negative thr, keep_edge, max_gap or fade.  The handle owns
+ * the scratch (frame flags, per-frame destinations, the per-chunk plan), which grows on
+ * demand (zv_wavjoin_device_bytes); a warm call at an already-seen size makes no
+ * host-blocking runtime call.
+ * ---------------------------------------------------------------------- */
+typedef struct zv_wavjoin* zv_wavjoin_handle;
+zv_wavjoin_handle zv_wavjoin_create(int frame, float thr, int keep_edge, int max_gap, int fade);
+void zv_wavjoin_destroy(zv_wavjoin_handle h);
+/* wav: [B, C, wav_ld] fp32 device samples, C in {1, 2}; lens: [B] int32 device sample
+ * counts, 0 <= lens[b] <= wav_ld; gains: [B] fp32 device, or NULL for 1; out: [C, out_ld],
+ * of which columns [0, out_cap) may be written (out_cap <= out_ld); out_len: one device
+ * int64 (N); spans: [B, 3] device int32 {m_b, off_b, F_b}, or NULL.  B >= 0. */
+int zv_wavjoin_apply(zv_wavjoin_handle h, const float* wav, int64_t wav_ld, const int32_t* lens,
+                     const float* gains, int B, int C, float* out, int64_t out_ld, int64_t out_cap,
+                     int64_t* out_len, int32_t* spans, void* stream);
+int64_t zv_wavjoin_device_bytes(zv_wavjoin_handle h);
 
 #ifdef __cplusplus
 }

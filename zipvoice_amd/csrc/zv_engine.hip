@@ -1836,6 +1836,7 @@ struct zv_engine {
 #include "zv_bigvgan.inc"
 #include "zv_fbank.inc"
 #include "zv_resample.inc"
+#include "zv_wavjoin.inc"
 
 // ===========================================================================
 // C ABI
@@ -2918,6 +2919,39 @@ int zv_resample_apply(zv_resample_handle h, const float* wav, int64_t wav_ld, co
 }
 
 int64_t zv_resample_device_bytes(zv_resample_handle h) { return h ? (int64_t)h->bytes : 0; }
+
+zv_wavjoin_handle zv_wavjoin_create(int frame, float thr, int keep_edge, int max_gap, int fade) {
+  zv_wavjoin* h = nullptr;
+  try {
+    h = new zv_wavjoin();
+    h->init(frame, thr, keep_edge, max_gap, fade);
+    return h;
+  } catch (const std::exception& e) {
+    delete h;
+    g_last_error = e.what();
+    return nullptr;
+  }
+}
+
+void zv_wavjoin_destroy(zv_wavjoin_handle h) { delete h; }
+
+int zv_wavjoin_apply(zv_wavjoin_handle h, const float* wav, int64_t wav_ld, const int32_t* lens,
+                     const float* gains, int B, int C, float* out, int64_t out_ld, int64_t out_cap,
+                     int64_t* out_len, int32_t* spans, void* stream) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(h != nullptr, "null wavjoin handle");
+  ZV_REQUIRE(C == 1 || C == 2, "C must be 1 or 2");
+  ZV_REQUIRE(B >= 0, "B must be non-negative");
+  ZV_REQUIRE(out_cap <= out_ld, "out_cap exceeds out_ld");
+  ZV_REQUIRE(out_cap >= 0 && wav_ld >= 0 && wav_ld <= 0x7fffffffLL, "bad out_cap / wav_ld");
+  ZV_REQUIRE(out_len && (out || out_cap == 0) && ((wav && lens) || B == 0), "null argument");
+  static_assert(sizeof(long) == sizeof(int64_t), "64-bit positions");
+  h->apply(wav, (long)wav_ld, lens, gains, B, C, out, (long)out_ld, (long)out_cap,
+           reinterpret_cast<long*>(out_len), spans, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int64_t zv_wavjoin_device_bytes(zv_wavjoin_handle h) { return h ? (int64_t)h->bytes : 0; }
 
 int64_t zv_vocoder_device_bytes(zv_vocoder_handle v) {
   if (!v) return 0;

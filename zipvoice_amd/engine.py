@@ -134,6 +134,12 @@ SIGNATURES = {
     "zv_resample_destroy": (None, [_P]),
     "zv_resample_apply": (_I, [_P, _P, ctypes.c_int64, _P, _I, _P, ctypes.c_int64, ctypes.c_int64, _P]),
     "zv_resample_device_bytes": (ctypes.c_int64, [_P]),
+    # long-form trim and join (zipvoice_amd/longform.py WavJoiner)
+    "zv_wavjoin_create": (_P, [_I, _F, _I, _I, _I]),
+    "zv_wavjoin_destroy": (None, [_P]),
+    "zv_wavjoin_apply": (_I, [_P, _P, ctypes.c_int64, _P, _P, _I, _I, _P, ctypes.c_int64,
+                              ctypes.c_int64, _P, _P, _P]),
+    "zv_wavjoin_device_bytes": (ctypes.c_int64, [_P]),
 }
 
 _libs: Dict[str, ctypes.CDLL] = {}

@@ -1,0 +1,262 @@
+"""Long-form synthesis: text longer than the model speaks in one pass.
+
+The reference has no long-form path, so nothing here mirrors it; the behaviour is this
+module's own (and ``include/zipvoice_hip.h`` for the join).  Three parts:
+
+* ``chunk_tokens`` / ``chunk_budget``: split a token list at the caller's sentence-end ids
+  into chunks whose predicted duration fits the model (host, pure Python; the engine takes
+  token ids and knows no tokenizer).
+* ``WavJoiner``: the engine's ``zv_wavjoin_*`` kernels: trim the pauses the model puts at
+  chunk edges (and over-long pauses inside), then glue the trimmed chunks with linear
+  cross-fades, all on the device.
+* ``generate_long``: prompt -> chunks -> ``model.sample`` in batches that share the one
+  prompt -> vocoder -> one join.
+"""
+from __future__ import annotations
+
+import ctypes
+import datetime as dt
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import engine as _eng
+
+
+# ------------------------------------------------------------------------------ chunker
+def _split_after(tokens: Sequence[int], ids) -> List[List[int]]:
+    """Split after every token in ``ids`` (the break token stays with its piece)."""
+    out, cur = [], []
+    for t in tokens:
+        cur.append(t)
+        if t in ids:
+            out.append(cur)
+            cur = []
+    if cur:
+        out.append(cur)
+    return out
+
+
+def _even_parts(piece: List[int], max_tokens: int) -> List[List[int]]:
+    """k = ceil(n / max_tokens) consecutive parts whose sizes differ by at most 1."""
+    n = len(piece)
+    k = -(-n // max_tokens)
+    out, pos = [], 0
+    for i in range(k):
+        size = n // k + (1 if i < n % k else 0)
+        out.append(piece[pos:pos + size])
+        pos += size
+    return out
+
+
+def chunk_tokens(tokens: Sequence[int], break_ids, max_tokens: int,
+                 soft_break_ids=()) -> List[List[int]]:
+    """Token list -> list of chunks of at most ``max_tokens`` tokens, in order (their
+    concatenation is the input).
+
+    The text is split after every token in ``break_ids`` (sentence ends).  A sentence longer
+    than ``max_tokens`` is split the same way at ``soft_break_ids`` (commas and the like),
+    and a piece that is still too long, of length n, is cut into ceil(n / max_tokens)
+    consecutive parts whose sizes differ by at most 1.  The resulting pieces merge greedily,
+    left to right, while the merged length stays <= ``max_tokens``."""
+    max_tokens = int(max_tokens)
+    if max_tokens < 1:
+        raise ValueError("max_tokens must be at least 1")
+    hard, soft = frozenset(break_ids), frozenset(soft_break_ids)
+    pieces: List[List[int]] = []
+    for sentence in _split_after(list(tokens), hard):
+        if len(sentence) <= max_tokens:
+            pieces.append(sentence)
+            continue
+        for part in _split_after(sentence, soft):
+            pieces.extend([part] if len(part) <= max_tokens else _even_parts(part, max_tokens))
+    chunks: List[List[int]] = []
+    for p in pieces:
+        if chunks and len(chunks[-1]) + len(p) <= max_tokens:
+            chunks[-1] = chunks[-1] + p
+        else:
+            chunks.append(list(p))
+    return chunks
+
+
+def chunk_budget(prompt_tokens_len: int, prompt_seconds: float, max_seconds: float = 25.0,
+                 speed: float = 1.0) -> int:
+    """The token count whose predicted duration fills the time left beside the prompt:
+    ``common.predict_features_lens`` gives a chunk of n tokens
+    n * prompt_seconds / prompt_tokens_len / speed seconds, so
+    max(1, floor((max_seconds - prompt_seconds) * prompt_tokens_len / prompt_seconds * speed))
+    tokens fit ``max_seconds`` of prompt plus speech.  ``max_seconds`` is the caller's limit
+    for one pass (25 s is a default, not a tuned value)."""
+    if not prompt_seconds > 0 or prompt_tokens_len < 1:
+        raise ValueError("the prompt must have a positive duration and at least one token")
+    if prompt_seconds >= max_seconds:
+        raise ValueError(f"the prompt ({prompt_seconds:.2f} s) leaves no room within "
+                         f"max_seconds = {max_seconds}")
+    return max(1, math.floor((max_seconds - prompt_seconds) * prompt_tokens_len
+                             / prompt_seconds * speed))
+
+
+# ------------------------------------------------------------------------------ joiner
+class WavJoiner:
+    """Trim and join on the device (``zv_wavjoin_*``, definition in include/zipvoice_hip.h).
+
+    ``frame`` samples per energy frame (240 = 10 ms at 24 kHz); a frame is quiet below
+    ``threshold_db`` dBFS RMS; ``keep_edge`` quiet frames stay around the speech (10 =
+    100 ms); a pause inside longer than ``max_gap`` frames (50 = 500 ms) is cut to
+    ``max_gap`` frames; neighbouring chunks overlap by up to ``fade`` samples (2400 =
+    100 ms) of linear cross-fade.  One engine handle per device, freed in ``__del__``."""
+
+    def __init__(self, frame: int = 240, threshold_db: float = -42.0, keep_edge: int = 10,
+                 max_gap: int = 50, fade: int = 2400):
+        self.frame, self.threshold_db = int(frame), float(threshold_db)
+        self.keep_edge, self.max_gap, self.fade = int(keep_edge), int(max_gap), int(fade)
+        self.thr = 10.0 ** (self.threshold_db / 20.0)
+        self._lib = None
+        self._handles: Dict[torch.device, int] = {}
+
+    def _handle(self, device: torch.device):
+        if not torch.cuda.is_available():
+            raise RuntimeError("zipvoice_amd long-form join needs a ROCm GPU; no CPU fallback")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._handles:
+            self._lib = _eng.load_library()
+            h = self._lib.zv_wavjoin_create(self.frame, self.thr, self.keep_edge, self.max_gap,
+                                            self.fade)
+            if not h:
+                raise ValueError(self._lib.zv_last_error().decode())
+            self._handles[device] = h
+        return self._handles[device]
+
+    def __del__(self):
+        for dev, h in list(getattr(self, "_handles", {}).items()):
+            try:
+                torch.cuda.synchronize(dev)
+            except Exception:
+                pass
+            self._lib.zv_wavjoin_destroy(h)
+        self._handles = {}
+
+    def device_bytes(self) -> int:
+        """Scratch the handles hold (0 before the first call)."""
+        return sum(int(self._lib.zv_wavjoin_device_bytes(h)) for h in self._handles.values())
+
+    @torch.inference_mode()
+    def __call__(self, wavs: torch.Tensor, lens, gains=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """wavs (B, n) or (B, C, n) fp32 (C in {1, 2}), lens (B,) sample counts (host
+        values), gains (B,) or None -> (out (C, N) on the device, spans (B, 3) int32 on the
+        device: trimmed length m_b, start off_b in ``out`` (-1 for an empty chunk), overlap
+        F_b with the previous non-empty chunk).  Allocates cap = sum(lens) columns and waits
+        for the host once, to read N."""
+        if wavs.dim() == 2:
+            wavs = wavs.unsqueeze(1)
+        if wavs.dim() != 3 or wavs.shape[1] not in (1, 2):
+            raise ValueError(f"wavs must be (B, n) or (B, C, n) with C in (1, 2), got "
+                             f"{tuple(wavs.shape)}")
+        dev = wavs.device if wavs.is_cuda else torch.device("cuda")
+        h = self._handle(dev)
+        wavs = wavs.to(dev, torch.float32).contiguous()
+        B, C, n = wavs.shape
+        lens_host = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+        if len(lens_host) != B or (B and (min(lens_host) < 0 or max(lens_host) > n)):
+            raise ValueError("lens must hold B sample counts in [0, n]")
+        cap = sum(lens_host)
+        ln = torch.tensor(lens_host, dtype=torch.int32, device=dev)
+        g = None
+        if gains is not None:
+            g = torch.as_tensor(gains, dtype=torch.float32).to(dev).contiguous()
+            if g.shape != (B,):
+                raise ValueError("gains must have shape (B,)")
+        out = torch.empty((C, max(cap, 1)), dtype=torch.float32, device=dev)
+        out_len = torch.empty(1, dtype=torch.int64, device=dev)
+        spans = torch.empty((max(B, 1), 3), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _eng._check(self._lib.zv_wavjoin_apply(
+                h, _eng._ptr(wavs), n, _eng._ptr(ln), _eng._ptr(g), B, C, _eng._ptr(out),
+                out.shape[1], cap, _eng._ptr(out_len), _eng._ptr(spans), _eng._stream()),
+                self._lib)
+        N = int(out_len.item())                       # the one host wait: N depends on the data
+        if N > cap:
+            raise RuntimeError(f"joined length {N} exceeds the allocated {cap} samples")
+        return out[:, :N], spans[:B]
+
+
+# ------------------------------------------------------------------------------ pipeline
+@torch.inference_mode()
+def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model, vocoder,
+                  feature_extractor, break_ids, soft_break_ids=(), max_seconds: float = 25.0,
+                  batch_size: int = 32, joiner: Optional[WavJoiner] = None, x0=None,
+                  return_chunks: bool = False, num_step: int = 16, guidance_scale: float = 1.0,
+                  speed: float = 1.0, t_shift: float = 0.5, target_rms: float = 0.1,
+                  feat_scale: float = 0.1, feat_bias: float = 0.0, sampling_rate: int = 24000,
+                  prompt_sampling_rate: int = 24000):
+    """A text of any length with one prompt (mono and one-channel Dialog models).
+
+    The prompt is prepared once, as ``infer.generate_sentence`` does; ``chunk_budget`` and
+    ``chunk_tokens`` cut the text into K chunks that each fit ``max_seconds`` together with
+    the prompt; the chunks run through ``model.sample`` in text order, in consecutive groups
+    of at most ``batch_size`` rows that repeat the prompt (``x0``: None, or one initial-noise
+    tensor per group), and through ``vocoder.decode_features``; one ``WavJoiner`` call trims
+    and joins the K waveforms, with ``generate_sentence``'s RMS restore folded in as the
+    per-chunk gain.  Returns (wav (1, N) on the device, metrics with t, wav_seconds, rtf,
+    num_chunks, num_batches); with ``return_chunks`` also the list of per-chunk waveforms
+    (untrimmed, before the gain) and the joiner's spans."""
+    from .infer import _prompt_rms_normalise, _resampler
+    dev = model.device
+    w = torch.as_tensor(np.asarray(prompt_wav) if not torch.is_tensor(prompt_wav) else prompt_wav,
+                        dtype=torch.float32)
+    if w.dim() == 1:
+        w = w.unsqueeze(0)
+    if prompt_sampling_rate != sampling_rate:
+        w = _resampler(prompt_sampling_rate, sampling_rate)(w.to(dev))
+    w, prompt_rms = _prompt_rms_normalise(w, target_rms)
+    feats = feature_extractor.extract(w.to(dev), sampling_rate=sampling_rate)
+    prompt_features = ((feats.unsqueeze(0) + feat_bias) * feat_scale).to(dev)
+    P = prompt_features.size(1)
+
+    budget = chunk_budget(len(prompt_tokens), w.shape[-1] / sampling_rate, max_seconds, speed)
+    chunks = chunk_tokens(tokens, break_ids, budget, soft_break_ids)
+    if not chunks:
+        raise ValueError("no tokens to synthesise")
+    groups = [chunks[i:i + batch_size] for i in range(0, len(chunks), int(batch_size))]
+    if x0 is not None and len(x0) != len(groups):
+        raise ValueError(f"x0 must hold one tensor per sample() call ({len(groups)}), got {len(x0)}")
+    joiner = joiner if joiner is not None else WavJoiner()
+    hop = vocoder.cfg.hop_length
+
+    torch.cuda.synchronize(dev)
+    t0 = dt.datetime.now()
+    wavs, lens = [], []
+    for gi, grp in enumerate(groups):
+        nb = len(grp)
+        pred, pred_lens, _, _ = model.sample(
+            tokens=grp, prompt_tokens=[prompt_tokens] * nb,
+            prompt_features=prompt_features.expand(nb, -1, -1).contiguous(),
+            prompt_features_lens=torch.full((nb,), P, dtype=torch.int64, device=dev),
+            speed=speed, t_shift=t_shift, duration="predict", num_step=num_step,
+            guidance_scale=guidance_scale, x0=None if x0 is None else x0[gi])
+        wavs.append(vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale,
+                                            feat_bias=feat_bias, clamp=True))
+        lens.append(pred_lens)
+    lens_host = [int(v) * hop for v in torch.cat(lens).tolist()]
+    K, n = len(chunks), max(x.shape[1] for x in wavs)
+    if len(wavs) == 1:
+        batch = wavs[0]
+    else:
+        batch = torch.zeros((K, n), dtype=torch.float32, device=dev)
+        r = 0
+        for x in wavs:
+            batch[r:r + x.shape[0], :x.shape[1]] = x
+            r += x.shape[0]
+    gains = [prompt_rms / target_rms] * K if prompt_rms < target_rms else None
+    out, spans = joiner(batch, lens_host, gains)
+    torch.cuda.synchronize(dev)
+    t = (dt.datetime.now() - t0).total_seconds()
+    secs = out.shape[1] / sampling_rate
+    metrics = {"t": t, "wav_seconds": secs, "rtf": t / secs if secs else float("inf"),
+               "num_chunks": K, "num_batches": len(groups)}
+    if return_chunks:
+        return out, metrics, [batch[i, :lens_host[i]] for i in range(K)], spans
+    return out, metrics
