@@ -203,10 +203,7 @@ struct BvAct { float* alpha = nullptr; float* ibeta = nullptr; };
 
 struct zv_bigvgan {
   zv_bigvgan_config cfg;
-  std::map<std::string, std::vector<float>> staged;
-  std::vector<void*> allocs;
-  size_t weight_bytes = 0;
-  bool ready = false;
+  WeightStore store;
   BvFilter filt{};
   int halo = 8;                                  // zero rows around each utterance (>= max conv pad)
   Linear conv_pre;
@@ -234,70 +231,29 @@ struct zv_bigvgan {
       if (ev_join[j]) (void)ZV_BLOCKING(hipEventDestroy(ev_join[j]));
     }
     if (ev_fork) (void)ZV_BLOCKING(hipEventDestroy(ev_fork));
-    for (void* p : allocs) (void)ZV_BLOCKING(hipFree(p));
   }
 
-  template <typename T> T* dalloc(size_t n) {
-    void* p = nullptr;
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T))));
-    allocs.push_back(p);
-    weight_bytes += n * sizeof(T);
-    return reinterpret_cast<T*>(p);
-  }
-  const std::vector<float>& take(const std::string& k, size_t numel) {
-    auto it = staged.find(k);
-    if (it == staged.end()) throw std::invalid_argument("missing weight: " + k);
-    if (it->second.size() != numel)
-      throw std::invalid_argument("weight " + k + ": expected " + std::to_string(numel) +
-                                  " elements, got " + std::to_string(it->second.size()));
-    return it->second;
-  }
-  float* upload(const std::vector<float>& v) {
-    float* d = dalloc<float>(v.size());
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice)));
-    return d;
-  }
-  Linear make_linear(const std::vector<float>& w, int N, int K, const float* b) {
-    Linear L;
-    L.N = N; L.K = K;
-    L.Npad = (int)round_up(N, W_NPAD);
-    L.Kpad = (int)round_up(K, W_KPAD);
-    std::vector<bf16> hi((size_t)L.Npad * L.Kpad, (bf16)0.f), lo(hi.size(), (bf16)0.f);
-    for (int n = 0; n < N; ++n)
-      for (int k = 0; k < K; ++k) {
-        const float v = w[(size_t)n * K + k];
-        const bf16 hh = (bf16)v;
-        hi[(size_t)n * L.Kpad + k] = hh;
-        lo[(size_t)n * L.Kpad + k] = (bf16)(v - (float)hh);
-      }
-    L.hi = dalloc<bf16>(hi.size());
-    L.lo = dalloc<bf16>(lo.size());
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.hi, hi.data(), hi.size() * sizeof(bf16), hipMemcpyHostToDevice)));
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.lo, lo.data(), lo.size() * sizeof(bf16), hipMemcpyHostToDevice)));
-    if (b) L.b = upload(std::vector<float>(b, b + N));
-    return L;
-  }
   // Conv1d weight (Cout, Cin, k) -> GEMM rows [o][tap * Cin + c]
   // (input channels zero-padded to Cp: the implicit-conv operand's row width)
   Linear conv_linear(const std::string& p, int Cout, int Cin, int k, bool bias, int Cp = 0) {
     if (Cp < Cin) Cp = Cin;
-    const auto& w = take(p + ".weight", (size_t)Cout * Cin * k);
+    const auto& w = store.take(p + ".weight", (size_t)Cout * Cin * k);
     std::vector<float> w2((size_t)Cout * Cp * k, 0.f);
     for (int o = 0; o < Cout; ++o)
       for (int c = 0; c < Cin; ++c)
         for (int t = 0; t < k; ++t) w2[(size_t)o * Cp * k + (size_t)t * Cp + c] = w[((size_t)o * Cin + c) * k + t];
-    return make_linear(w2, Cout, Cp * k, bias ? take(p + ".bias", Cout).data() : nullptr);
+    return store.make_linear(w2.data(), Cout, Cp * k, bias ? store.take(p + ".bias", Cout).data() : nullptr);
   }
   BvAct snake(const std::string& p, int C) {
-    const auto& a = take(p + "alpha", C);
-    const auto& b = take(p + "beta", C);
+    const auto& a = store.take(p + "alpha", C);
+    const auto& b = store.take(p + "beta", C);
     std::vector<float> ea(C), ib(C);
     for (int c = 0; c < C; ++c) {
       ea[c] = cfg.snake_logscale ? expf(a[c]) : a[c];
       const float eb = cfg.snake_logscale ? expf(b[c]) : b[c];
       ib[c] = 1.0f / (eb + 1e-9f);
     }
-    return BvAct{upload(ea), upload(ib)};
+    return BvAct{store.upload(ea), store.upload(ib)};
   }
 
   // alias_free_activation filter.py: kaiser-windowed sinc, cutoff 0.25, half width 0.3,
@@ -341,13 +297,13 @@ struct zv_bigvgan {
       ZV_REQUIRE(u >= 1 && k >= u && (k - u) % 2 == 0, "upsample kernel / rate must satisfy k >= u, k - u even");
       ZV_REQUIRE(C % 2 == 0, "channel count must halve per stage");
       const std::string p = "ups." + std::to_string(i) + ".0.";
-      const auto& w = take(p + "weight", (size_t)C * Co * k);   // (Cin, Cout, k)
+      const auto& w = store.take(p + "weight", (size_t)C * Co * k);   // (Cin, Cout, k)
       std::vector<float> w2((size_t)k * Co * C);
       for (int c = 0; c < C; ++c)
         for (int o = 0; o < Co; ++o)
           for (int j = 0; j < k; ++j) w2[((size_t)j * Co + o) * C + c] = w[((size_t)c * Co + o) * k + j];
-      ups.push_back(make_linear(w2, k * Co, C, nullptr));
-      ups_b.push_back(upload(take(p + "bias", Co)));
+      ups.push_back(store.make_linear(w2.data(), k * Co, C, nullptr));
+      ups_b.push_back(store.upload_key(p + "bias", Co));
       expected += 2;
       C = Co;
       chans.push_back(C);
@@ -374,16 +330,16 @@ struct zv_bigvgan {
       }
     }
     act_post = snake("activation_post.act.", C);
-    post_w = upload(take("conv_post.weight", (size_t)C * 7));
+    post_w = store.upload_key("conv_post.weight", (size_t)C * 7);
     expected += 3;
     if (cfg.use_bias_at_final) {
-      post_b = take("conv_post.bias", 1)[0];
+      post_b = store.take("conv_post.bias", 1)[0];
       expected += 1;
     }
     // alias-free filter buffers (".upsample.filter", ".downsample.lowpass.filter") are
     // recomputed above; they must match it when present
     size_t filters = 0;
-    for (auto& kv : staged) {
+    for (auto& kv : store.staged) {
       const std::string& k = kv.first;
       const bool up = k.size() > 16 && k.compare(k.size() - 16, 16, ".upsample.filter") == 0;
       const bool dn = k.size() > 26 && k.compare(k.size() - 26, 26, ".downsample.lowpass.filter") == 0;
@@ -394,17 +350,17 @@ struct zv_bigvgan {
         ZV_REQUIRE(fabsf(kv.second[n] - filt.down[n]) <= 1e-6f,
                    "alias-free filter " + k + " differs from kaiser_sinc_filter1d(0.25, 0.3, 12)");
     }
-    if (staged.size() - filters != expected)
-      throw std::invalid_argument("bigvgan state dict has " + std::to_string(staged.size() - filters) +
+    if (store.staged.size() - filters != expected)
+      throw std::invalid_argument("bigvgan state dict has " + std::to_string(store.staged.size() - filters) +
                                   " tensors, config expects " + std::to_string(expected) +
                                   " (unexpected keys present)");
-    staged.clear();
+    store.staged.clear();
     ZV_CHECK(ZV_BLOCKING(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming)));
     for (int j = 0; j < nk; ++j) {
       ZV_CHECK(ZV_BLOCKING(hipStreamCreateWithFlags(&side[j], hipStreamNonBlocking)));
       ZV_CHECK(ZV_BLOCKING(hipEventCreateWithFlags(&ev_join[j], hipEventDisableTiming)));
     }
-    ready = true;
+    store.ready = true;
   }
 
   template <int SPLIT, int CONV = 0>
@@ -536,7 +492,7 @@ struct zv_bigvgan {
   }
 
   size_t device_bytes() const {
-    size_t b = weight_bytes + x.bytes + P.bytes + post.bytes + xa.bytes();
+    size_t b = store.weight_bytes + x.bytes + P.bytes + post.bytes + xa.bytes();
     for (int j = 0; j < 3; ++j) b += y[j].bytes + t1[j].bytes + col[j].bytes();
     return b;
   }

@@ -136,6 +136,13 @@ __device__ __forceinline__ void store4(bf16* p, const float (&v)[4]) {
 
 __host__ __device__ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 __host__ __device__ static inline long round_up(long a, long b) { return (a + b - 1) / b * b; }
+// grid of a grid-stride elementwise kernel over n elements
+static inline dim3 grid1d(long n, int block = 256) {
+  long g = (n + block - 1) / block;
+  if (g > 65536) g = 65536;
+  if (g < 1) g = 1;
+  return dim3((unsigned)g);
+}
 
 // ---------------------------------------------------------------------------
 // optional per-launch profiler (HIP events on the launch stream), used by

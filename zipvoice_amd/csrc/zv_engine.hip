@@ -28,31 +28,14 @@
 #include "zv_elem.inc"
 #include "zv_flash.inc"
 #include "zv_flash2.inc"
-// K-ring depth of the fp16 parity mode's weight-split value projection (A/B builds; 3: 25.3 ->
-// 21.6 ms per C2 step against 2, 4 stages at one block per CU 22.3, profiles/r06_wsplit_ab.txt)
-#ifndef ZV_WSPLIT_T_STAGES
-#define ZV_WSPLIT_T_STAGES 3
-#endif
+#include "zv_weights.inc"
+#include "zv_linear.inc"
 #include "../../include/zipvoice_hip.h"
 
 static thread_local std::string g_last_error;
 ZvProfiler g_zv_prof;
 
 namespace {
-
-constexpr int W_NPAD = 128;   // weight row padding (GEMM BN)
-constexpr int W_KPAD = 64;    // weight column padding (multiple of GEMM BK)
-
-struct Linear {
-  int N = 0, K = 0, Npad = 0, Kpad = 0;
-  bf16* hi = nullptr;
-  bf16* lo = nullptr;
-  uint8_t* q8 = nullptr;  // fp8 mode: MX-fp8 weight [Npad][Kq] + scales [Npad][Kq / 32] (zv_mx8.inc)
-  uint8_t* s8 = nullptr;
-  int Kq = 0;
-  float* w32 = nullptr;   // fp32 copy (small linears only)
-  float* b = nullptr;
-};
 
 struct LayerW {
   Linear attn_in;
@@ -120,16 +103,6 @@ struct DBuf {
     return reinterpret_cast<T*>(p);
   }
   ~DBuf() { if (p) (void)ZV_BLOCKING(hipFree(p)); }
-};
-
-struct Act {           // GEMM operand in HBM: bf16 hi (+ lo in fp32-accurate mode)
-  bf16* h = nullptr;
-  bf16* l = nullptr;
-  long ld = 0;
-  // fp8 mode: the MX-fp8 copy (values (rows, ldq), scales (rows, ldq / 32)) or null
-  uint8_t* q = nullptr;
-  uint8_t* qs = nullptr;
-  long ldq = 0;
 };
 
 struct ActBuf {
@@ -224,23 +197,12 @@ static void release_stream_set(const StreamSet& set) {
   stream_pool_free().push_back(set);
 }
 
-inline dim3 grid1d(long n, int block = 256) {
-  long g = (n + block - 1) / block;
-  if (g > 65536) g = 65536;
-  if (g < 1) g = 1;
-  return dim3((unsigned)g);
-}
-
 }  // namespace
 
 // ===========================================================================
-struct zv_engine {
+struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fused-epilogue launches)
   zv_config cfg;
-  std::map<std::string, std::vector<float>> staged;
-  std::map<std::string, std::vector<float>> derived;   // re-laid-out copies (stage_rows_scaled, ...)
-  std::vector<void*> allocs;
-  size_t weight_bytes = 0;
-  bool ready = false;
+  WeightStore store;
   ZipformerW dec, txt;
   float* embed_table = nullptr;   // (vocab, text_embed_dim)
   float* spk_table = nullptr;     // (2, feat_dim)
@@ -255,23 +217,6 @@ struct zv_engine {
   hipEvent_t split_fork = nullptr, split_join[MAX_SPLIT - 1] = {};
 
   bool materialize_attn = false;   // A/B: ZV_ATTN_MATERIALIZE=1 keeps the W-materialising path
-  // Measured launch-policy choices, fixed (their A/B knobs were retired in round 5; the records
-  // stay in profiles/): two 4-wave GEMM blocks per CU everywhere (profiles/r01_gemm_policy_ab.txt)
-  // and one tile per block (gridx -1: with the decoder split over streams, dynamically dispatched
-  // tiles fill the CUs another stream's kernel leaves idle; the persistent resident grid measured
-  // 2.6 % slower, profiles/r02_launch_policy_ab.txt); the attention-score projection on 128x128
-  // counted tiles (r02_n96_counted_ab.txt); the V^T projection on 64x64 tiles (r01_skinny_ab.txt);
-  // the copy-only SelfAttention out-projection on the counted epilogue (r02_sa_copy_ab.txt); no
-  // deferred stores (r01_gemm_defer_ab.txt); the 256x256 kernel from 256 tiles up.
-  static constexpr int occ_plain = 2, occ_resid = 2, occ_fused = 2;
-  static constexpr int gridx_plain = -1, gridx_resid = -1, gridx_fused = -1;
-  static constexpr int n96_mode = 2;
-  static constexpr bool sa_copy = true, skinny_tiles = true, defer_stores = false;
-  static constexpr int gemm256_min_tiles = 256;
-  // mixed (fp16 parity) mode: no lo half of the SelfAttention Toeplitz table, the fp32 positional
-  // table for the head-0 / NonlinAttention scoring, the weight-split attention-score projection
-  // (profiles/r03_mixed_ab.txt)
-  static constexpr bool mixed_plo = false, mixed_tpna = true, mixed_wsplit = true;
   // ZV_FFN: the decoder FeedForward modules as one fused kernel each (zv_ffn.inc: in_proj ->
   // SwooshL -> out_proj -> residual without the hidden tensor in HBM) for launches of at
   // least ffn_min_rows rows; 2 (default): FF3 also carries the layer's BiasNorm + bypass in its
@@ -297,13 +242,6 @@ struct zv_engine {
                                    // term on the MFMA chain (zv_attn_sa_tp_kernel), the head-0
                                    // stats / NonlinAttention scoring too; 0 = VALU forms
                                    // (3: A/B arm, SA with the one-wave register budget)
-  int res_counted = 31;            // ZV_RES_COUNTED: the counted epilogues (bit mask: 1 residual,
-                                   // 2 plain, 4 NA, 8 GLU, 16 transposed; 1 = all, 0 = the general
-                                   // epilogue, zv_gemm.inc gemm_epilogue: bitwise A/B tests;
-                                   // 32 + mask: that mask)
-  // ZV_GEMM256: the 256x256 phased kernel (zv_gemm256.inc) for the bias (+ SwooshL) and GLU
-  // linears with at least gemm256_min_tiles tiles (1 persistent, 2 one tile per block, 0 off)
-  int gemm256 = 2;
   // ZV_MIXED_SA (fp16 parity mode): the SelfAttention value projection as a weight-split product and
   // its out-projection's residual update as a split product (the K-concatenated conv + SelfAttention
   // out-projection runs [dw | o_hi | o_lo | o_hi] . [conv_out | sa_out_hi | sa_out_hi | sa_out_lo]):
@@ -333,49 +271,13 @@ struct zv_engine {
     ffn_fused = envi("ZV_FFN", 2);
     ffn_min_rows = envi("ZV_FFN_MIN_ROWS", 15000);
     ffn_persist = envi("ZV_FFN_PERSIST", 1);
-    res_counted = envi("ZV_RES_COUNTED", 31);
-    if (res_counted == 1) res_counted = 31;            // 1: all (0 / 1 are the A/B tests' arms)
-    else if (res_counted >= 32) res_counted &= 31;     // 32 + mask: exactly that mask (bisection)
     split_streams = envi("ZV_SPLIT_STREAMS", 3);
     split_min_rows = envi("ZV_SPLIT_MIN_ROWS", 8192);
-    gemm256 = envi("ZV_GEMM256", 2);
     mixed_sa = envi("ZV_MIXED_SA", 1) != 0;
     attn_b2 = envi("ZV_ATTN2", 1) != 0 && (cfg.precision == ZV_BF16 || cfg.precision == ZV_FP8);
     attn_b2_dec = attn_b2 || (envi("ZV_ATTN2", 1) != 0 && cfg.precision == ZV_MIXED);
     attn2_exact = envi("ZV_ATTN2_EXACT", 0) != 0;
     glu_dw = envi("ZV_GLU_DW", 1);
-  }
-  // the 256x256 kernel's preconditions (16-bit operands: the lo halves the fp32-accurate mode
-  // keeps beside them are not read; padded K rows, the direct
-  // epilogues' activations) and enough tiles to fill the chip
-  bool use_gemm256(const GemmParams& p) const {
-    return gemm256 != 0 && !p.Cl && !p.As && p.N % 8 == 0 && (p.act == 0 || p.act == 1) &&
-           p.lda % 8 == 0 && p.ldb % 8 == 0 && p.lda >= round_up(p.K, GEMM_BK) &&
-           p.ldb >= round_up(p.K, GEMM_BK) && p.Brows >= p.N &&
-           (long)cdiv(p.M, 256) * cdiv(p.N, 256) >= gemm256_min_tiles;
-  }
-  // Residual linears (counted ROLE 1 / 2 / 4 / 5 epilogues): the tile by how many 128 x 128 tiles
-  // the launch has.  These linears are HBM-bound in the epilogue; a grid of fewer tiles than
-  // ~1.5 per CU leaves CUs idle or single-block, and smaller tiles with more blocks per CU
-  // overlap one block's residual traffic with the others' K loops.  Bitwise equal (every
-  // accumulator sees the same MFMA sequence).  Lab, K = 560 ROLE 4 (profiles/r05_resid_tiles_ab.txt):
-  // M = 6502 14.1 -> 12.4 us (128 x 64), 1625 11.1 -> 6.8 us (64 x 64); 13003 and up: 128 x 128
-  // (128 x 64 or 64 x 64 at every size lost in the C2 step, round 6: profiles/r06_resid_tile_ab.txt)
-  template <int SPLIT, int ROLE>
-  void launch_resid(const GemmParams& p, hipStream_t s, const char* tag) {
-    const long t = (long)cdiv(p.M, 128) * cdiv(p.N, 128), cus = zv_num_cus();
-    if constexpr (SPLIT == 1) {
-
-      if (t < cus / 2) {
-        launch_gemm<64, 64, 2, 2, SPLIT, EPI_STD, 4, 2, GEMM_BK, 0, 0, 0, ROLE>(p, 1, s, tag, true, gridx_resid);
-        return;
-      }
-      if (t < cus * 3 / 2) {
-        launch_gemm<128, 64, 2, 2, SPLIT, EPI_STD, 2, 3, GEMM_BK, 0, 0, 0, ROLE>(p, 1, s, tag, true, gridx_resid);
-        return;
-      }
-    }
-    launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, ROLE>(p, 1, s, tag, true, gridx_resid);
   }
   // ---------------------------------------------------------------- HIP graphs
   // The whole N-step Euler solve (~250 launches per step) is captured once per
@@ -486,125 +388,64 @@ struct zv_engine {
     for (int i = 0; i < MAX_SPLIT - 1; ++i)
       if (split_join[i]) (void)ZV_BLOCKING(hipEventDestroy(split_join[i]));
     if (split_fork) (void)ZV_BLOCKING(hipEventDestroy(split_fork));
-    for (void* p : allocs) (void)ZV_BLOCKING(hipFree(p));
   }
 
   // ---------------------------------------------------------------- weights
-  template <typename T> T* dalloc(size_t n) {
-    void* p = nullptr;
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T))));
-    allocs.push_back(p);
-    weight_bytes += n * sizeof(T);
-    return reinterpret_cast<T*>(p);
-  }
-  const std::vector<float>& take(const std::string& k, size_t numel) {
-    auto dt = derived.find(k);
-    const std::vector<float>* v = nullptr;
-    if (dt != derived.end()) {
-      v = &dt->second;
-    } else {
-      auto it = staged.find(k);
-      if (it == staged.end()) throw std::invalid_argument("missing weight: " + k);
-      v = &it->second;
-    }
-    if (v->size() != numel)
-      throw std::invalid_argument("weight " + k + ": expected " + std::to_string(numel) +
-                                  " elements, got " + std::to_string(v->size()));
-    return *v;
-  }
-  float* upload_f32(const std::string& k, size_t numel) {
-    const auto& v = take(k, numel);
-    float* d = dalloc<float>(numel);
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(d, v.data(), numel * sizeof(float), hipMemcpyHostToDevice)));
-    return d;
-  }
   // perm (optional): row n of the device matrix is row perm[n] of the reference weight
   Linear make_linear(const std::string& prefix, int N, int K, bool bias, bool keep_f32,
                      const std::vector<int>* perm = nullptr, bool fp8 = false) {
-    Linear L;
-    L.N = N; L.K = K;
-    L.Npad = (int)round_up(N, W_NPAD);
-    L.Kpad = (int)round_up(K, W_KPAD);
-    const auto& w = take(prefix + ".weight", (size_t)N * K);
-    std::vector<bf16> hi((size_t)L.Npad * L.Kpad, (bf16)0.f), lo(hi.size(), (bf16)0.f);
-    for (int n = 0; n < N; ++n)
-      for (int k = 0; k < K; ++k) {
-        const int src = perm ? (*perm)[n] : n;
-        float v = w[(size_t)src * K + k];
-        bf16 h = (bf16)v;
-        hi[(size_t)n * L.Kpad + k] = h;
-        lo[(size_t)n * L.Kpad + k] = (bf16)(v - (float)h);
+    const auto& w = store.take(prefix + ".weight", (size_t)N * K);
+    const std::vector<float>* b = bias ? &store.take(prefix + ".bias", N) : nullptr;
+    std::vector<float> wp, bp;               // the permuted rows
+    if (perm) {
+      wp.resize((size_t)N * K);
+      for (int n = 0; n < N; ++n)
+        memcpy(&wp[(size_t)n * K], &w[(size_t)(*perm)[n] * K], (size_t)K * sizeof(float));
+      if (b) {
+        bp.resize(N);
+        for (int n = 0; n < N; ++n) bp[n] = (*b)[(*perm)[n]];
       }
-    L.hi = dalloc<bf16>(hi.size());
-    L.lo = dalloc<bf16>(lo.size());
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.hi, hi.data(), hi.size() * sizeof(bf16), hipMemcpyHostToDevice)));
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.lo, lo.data(), lo.size() * sizeof(bf16), hipMemcpyHostToDevice)));
+    }
+    const float* rows = perm ? wp.data() : w.data();
+    Linear L = store.make_linear(rows, N, K, !b ? nullptr : perm ? bp.data() : b->data());
     if (fp8 && cfg.precision == ZV_FP8 && K % MX8_KSTEP == 0) {
       // MX-fp8 copy of the (permuted) fp32 weight, rows zero-padded to Npad
       L.Kq = K;
-      std::vector<float> wp((size_t)L.Npad * K, 0.f);
-      for (int n = 0; n < N; ++n)
-        memcpy(&wp[(size_t)n * K], &w[(size_t)(perm ? (*perm)[n] : n) * K], (size_t)K * sizeof(float));
+      std::vector<float> wz((size_t)L.Npad * K, 0.f);
+      memcpy(wz.data(), rows, (size_t)N * K * sizeof(float));
       std::vector<uint8_t> q((size_t)L.Npad * K), sc((size_t)L.Npad * K / MX8_BLOCK);
-      mx8_quantize_host(wp.data(), K, L.Npad, K, q.data(), K, sc.data());
-      L.q8 = dalloc<uint8_t>(q.size());
-      L.s8 = dalloc<uint8_t>(sc.size());
-      ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.q8, q.data(), q.size(), hipMemcpyHostToDevice)));
-      ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.s8, sc.data(), sc.size(), hipMemcpyHostToDevice)));
+      mx8_quantize_host(wz.data(), K, L.Npad, K, q.data(), K, sc.data());
+      L.q8 = store.upload(q.data(), q.size());
+      L.s8 = store.upload(sc.data(), sc.size());
     }
-    if (keep_f32) {
-      L.w32 = dalloc<float>((size_t)N * K);
-      ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.w32, w.data(), (size_t)N * K * sizeof(float), hipMemcpyHostToDevice)));
-    }
-    if (bias) {
-      if (perm) {
-        const auto& b = take(prefix + ".bias", N);
-        std::vector<float> pb(N);
-        for (int n = 0; n < N; ++n) pb[n] = b[(*perm)[n]];
-        L.b = dalloc<float>(N);
-        ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.b, pb.data(), N * sizeof(float), hipMemcpyHostToDevice)));
-      } else {
-        L.b = upload_f32(prefix + ".bias", N);
-      }
-    }
+    if (keep_f32) L.w32 = store.upload(w.data(), (size_t)N * K);
     return L;
   }
   // [a | b] concatenated along K (a: N x Ka, b: N x Kb; bias a + b), rows padded like
   // make_linear: the operand is [a's input (Ka columns) | b's input (Kb columns)]
   // b_split: b's columns three times as [b_hi | b_hi | b_lo] (the operand [a | x_hi | x_lo | x_hi]:
-  // x . b as the split product x_hi b_hi + x_lo b_hi + x_hi b_lo in a 16-bit GEMM; lo array unused)
+  // x . b as the split product x_hi b_hi + x_lo b_hi + x_hi b_lo in a 16-bit GEMM; lo array unused):
+  // the third block's source is b's fp32 remainder v - hi, whose hi half is b_lo
   Linear make_linear_kcat(const std::string& pa, int Ka, const std::string& pb, int Kb, int N,
                           bool b_split = false) {
-    Linear L;
-    L.N = N; L.K = Ka + (b_split ? 3 : 1) * Kb;
-    L.Npad = (int)round_up(N, W_NPAD);
-    L.Kpad = (int)round_up(L.K, W_KPAD);
-    const auto& wa = take(pa + ".weight", (size_t)N * Ka);
-    const auto& wb = take(pb + ".weight", (size_t)N * Kb);
-    std::vector<bf16> hi((size_t)L.Npad * L.Kpad, (bf16)0.f), lo(hi.size(), (bf16)0.f);
-    for (int n = 0; n < N; ++n)
-      for (int k = 0; k < L.K; ++k) {
-        const int kb = k < Ka ? -1 : (k - Ka) % Kb, blk = k < Ka ? -1 : (k - Ka) / Kb;
-        const float v = k < Ka ? wa[(size_t)n * Ka + k] : wb[(size_t)n * Kb + kb];
-        const bf16 h = (bf16)v;
-        if (blk == 2) {                    // b_lo block
-          hi[(size_t)n * L.Kpad + k] = (bf16)(v - (float)h);
-          continue;
+    const int K = Ka + (b_split ? 3 : 1) * Kb;
+    const auto& wa = store.take(pa + ".weight", (size_t)N * Ka);
+    const auto& wb = store.take(pb + ".weight", (size_t)N * Kb);
+    std::vector<float> w((size_t)N * K);
+    for (int n = 0; n < N; ++n) {
+      float* row = &w[(size_t)n * K];
+      memcpy(row, &wa[(size_t)n * Ka], (size_t)Ka * sizeof(float));
+      for (int blk = 0; Ka + blk * Kb < K; ++blk)
+        for (int k = 0; k < Kb; ++k) {
+          const float v = wb[(size_t)n * Kb + k];
+          row[Ka + blk * Kb + k] = blk == 2 ? v - (float)(bf16)v : v;
         }
-        hi[(size_t)n * L.Kpad + k] = h;
-        lo[(size_t)n * L.Kpad + k] = (bf16)(v - (float)h);
-      }
-    L.hi = dalloc<bf16>(hi.size());
-    L.lo = dalloc<bf16>(lo.size());
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.hi, hi.data(), hi.size() * sizeof(bf16), hipMemcpyHostToDevice)));
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.lo, lo.data(), lo.size() * sizeof(bf16), hipMemcpyHostToDevice)));
-    const auto& ba = take(pa + ".bias", N);
-    const auto& bb = take(pb + ".bias", N);
+    }
+    const auto& ba = store.take(pa + ".bias", N);
+    const auto& bb = store.take(pb + ".bias", N);
     std::vector<float> b(N);
     for (int n = 0; n < N; ++n) b[n] = ba[n] + bb[n];
-    L.b = dalloc<float>(N);
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.b, b.data(), N * sizeof(float), hipMemcpyHostToDevice)));
-    return L;
+    return store.make_linear(w.data(), N, K, b.data());
   }
   // NonlinAttention in_proj rows [s | x | y] -> groups of 48 = [s16 | x16 | y16]
   static std::vector<int> perm_na(int hid) {
@@ -630,22 +471,22 @@ struct zv_engine {
   // staged copy of prefix.{weight, bias} with rows [r0, r1) multiplied by f (the second-generation
   // attention's base-2 scores: log2(e) on the k and p rows of the attention-score projection)
   std::string stage_rows_scaled(const std::string& prefix, int N, int K, int r0, int r1, float f) {
-    std::vector<float> w = take(prefix + ".weight", (size_t)N * K), b = take(prefix + ".bias", N);
+    std::vector<float> w = store.take(prefix + ".weight", (size_t)N * K), b = store.take(prefix + ".bias", N);
     for (int n = r0; n < r1; ++n) {
       for (int k = 0; k < K; ++k) w[(size_t)n * K + k] *= f;
       b[n] *= f;
     }
     const std::string np = prefix + "#b2";
-    derived[np + ".weight"] = std::move(w);
-    derived[np + ".bias"] = std::move(b);
+    store.derived[np + ".weight"] = std::move(w);
+    store.derived[np + ".bias"] = std::move(b);
     return np;
   }
   // staged copy of a SelfAttention value projection (heads * vd rows) laid out 16 rows per head:
   // [vd value rows | a zero row with bias 1 | zero rows]: its V^T carries the softmax denominator's
   // ones row (zv_flash2.inc)
   std::string stage_value_heads16(const std::string& prefix, int heads, int vd, int K) {
-    const auto& w = take(prefix + ".weight", (size_t)heads * vd * K);
-    const auto& b = take(prefix + ".bias", (size_t)heads * vd);
+    const auto& w = store.take(prefix + ".weight", (size_t)heads * vd * K);
+    const auto& b = store.take(prefix + ".bias", (size_t)heads * vd);
     std::vector<float> w2((size_t)heads * 16 * K, 0.f), b2((size_t)heads * 16, 0.f);
     for (int h = 0; h < heads; ++h) {
       for (int d = 0; d < vd; ++d) {
@@ -655,15 +496,15 @@ struct zv_engine {
       b2[h * 16 + 12] = 1.f;
     }
     const std::string np = prefix + "#v16";
-    derived[np + ".weight"] = std::move(w2);
-    derived[np + ".bias"] = std::move(b2);
+    store.derived[np + ".weight"] = std::move(w2);
+    store.derived[np + ".bias"] = std::move(b2);
     return np;
   }
   Linear make_small(const std::string& prefix, int N, int K, bool bias) {
     Linear L;
     L.N = N; L.K = K;
-    L.w32 = upload_f32(prefix + ".weight", (size_t)N * K);
-    if (bias) L.b = upload_f32(prefix + ".bias", N);
+    L.w32 = store.upload_key(prefix + ".weight", (size_t)N * K);
+    if (bias) L.b = store.upload_key(prefix + ".bias", N);
     return L;
   }
 
@@ -691,20 +532,20 @@ struct zv_engine {
       std::string ep = S.ds != 1 ? sp + "encoder." : sp;
       if (S.ds != 1) {
         ZV_REQUIRE(S.ds <= 8, "downsampling factor > 8 unsupported");
-        const auto& b = take(sp + "downsample.bias", S.ds);
+        const auto& b = store.take(sp + "downsample.bias", S.ds);
         float mx = -INFINITY;
         for (float v : b) mx = std::max(mx, v);
         std::vector<float> w(S.ds);
         float sum = 0.f;
         for (int k = 0; k < S.ds; ++k) { w[k] = expf(b[k] - mx); sum += w[k]; }
         for (int k = 0; k < S.ds; ++k) w[k] /= sum;
-        S.ds_w = dalloc<float>(S.ds);
+        S.ds_w = store.dalloc<float>(S.ds);
         ZV_CHECK(ZV_BLOCKING(hipMemcpy(S.ds_w, w.data(), S.ds * sizeof(float), hipMemcpyHostToDevice)));
-        S.combiner = upload_f32(sp + "out_combiner.bypass_scale", dim);
+        S.combiner = store.upload_key(sp + "out_combiner.bypass_scale", dim);
       }
       if (temb_dim > 0) S.time_emb = make_small(ep + "time_emb.1", dim, temb_dim, true);
       const size_t pw_n = (size_t)heads * Z.pd * Z.pos_dim;
-      S.pos_w_all = dalloc<float>(pw_n * std::max(layers[s], 1));
+      S.pos_w_all = store.dalloc<float>(pw_n * std::max(layers[s], 1));
       for (int li = 0; li < layers[s]; ++li) {
         std::string lp = ep + "layers." + std::to_string(li) + ".";
         LayerW W;
@@ -713,7 +554,7 @@ struct zv_engine {
                                         : lp + "self_attn_weights.in_proj",
                                 qkp, dim, true, false);
         {
-          const auto& pw = take(lp + "self_attn_weights.linear_pos.weight", pw_n);
+          const auto& pw = store.take(lp + "self_attn_weights.linear_pos.weight", pw_n);
           W.pos_w = S.pos_w_all + li * pw_n;
           ZV_CHECK(ZV_BLOCKING(hipMemcpy(W.pos_w, pw.data(), pw_n * sizeof(float), hipMemcpyHostToDevice)));
         }
@@ -736,8 +577,8 @@ struct zv_engine {
           if (ffn_fused && fp8_layers && dim == FFN_D && hs[f] % (2 * FFN_HC) == 0 &&
               (cfg.precision == ZV_BF16 || cfg.precision == ZV_MIXED)) {
             const long n = (long)hs[f] * FFN_D;
-            W.ffn_w1f[f] = dalloc<bf16>(n);
-            W.ffn_w2f[f] = dalloc<bf16>(n);
+            W.ffn_w1f[f] = store.dalloc<bf16>(n);
+            W.ffn_w2f[f] = store.dalloc<bf16>(n);
             hipLaunchKernelGGL(zv_ffn_pack_w1_kernel, dim3(cdiv(n, 256)), dim3(256), 0, 0, W.ff_in[f].hi,
                                (long)W.ff_in[f].Kpad, hs[f], W.ffn_w1f[f]);
             hipLaunchKernelGGL(zv_ffn_pack_w2_kernel, dim3(cdiv(n, 256)), dim3(256), 0, 0, W.ff_out[f].hi,
@@ -760,13 +601,13 @@ struct zv_engine {
             W.conv_sa_out[c] = make_linear_kcat(cp + "out_proj", dim,
                                                 lp + "self_attn" + std::to_string(c + 1) + ".out_proj",
                                                 heads * Z.vd, dim, cfg.precision == ZV_MIXED && mixed_sa);
-          W.dw_w[c] = upload_f32(cp + "depthwise_conv.weight", (size_t)dim * W.ks);
-          W.dw_b[c] = upload_f32(cp + "depthwise_conv.bias", dim);
+          W.dw_w[c] = store.upload_key(cp + "depthwise_conv.weight", (size_t)dim * W.ks);
+          W.dw_b[c] = store.upload_key(cp + "depthwise_conv.bias", dim);
         }
-        W.bypass = upload_f32(lp + "bypass.bypass_scale", dim);
-        W.bypass_mid = upload_f32(lp + "bypass_mid.bypass_scale", dim);
-        W.norm_bias = upload_f32(lp + "norm.bias", dim);
-        W.norm_log_scale = take(lp + "norm.log_scale", 1)[0];
+        W.bypass = store.upload_key(lp + "bypass.bypass_scale", dim);
+        W.bypass_mid = store.upload_key(lp + "bypass_mid.bypass_scale", dim);
+        W.norm_bias = store.upload_key(lp + "norm.bias", dim);
+        W.norm_log_scale = store.take(lp + "norm.log_scale", 1)[0];
         S.layers.push_back(std::move(W));
       }
       Z.stacks.push_back(std::move(S));
@@ -803,26 +644,26 @@ struct zv_engine {
                     cfg.text_encoder_num_heads, {1}, {cfg.text_encoder_num_layers},
                     {cfg.text_encoder_cnn_module_kernel}, {cfg.text_embed_dim}, {F}, false, -1,
                     false, attn_b2);
-    embed_table = upload_f32("embed.weight", (size_t)cfg.vocab_size * cfg.text_embed_dim);
-    if (dialog()) spk_table = upload_f32("spk_embed.weight", (size_t)2 * F);
+    embed_table = store.upload_key("embed.weight", (size_t)cfg.vocab_size * cfg.text_embed_dim);
+    if (dialog()) spk_table = store.upload_key("spk_embed.weight", (size_t)2 * F);
     // timestep-embedding frequencies, float32 as zipformer.py:56-60
     const int half = cfg.time_embed_dim / 2;
     std::vector<float> fr(half);
     for (int k = 0; k < half; ++k)
       fr[k] = expf((float)(-log(10000.0)) * (float)k / (float)half);
-    temb_freqs = dalloc<float>(half);
+    temb_freqs = store.dalloc<float>(half);
     ZV_CHECK(ZV_BLOCKING(hipMemcpy(temb_freqs, fr.data(), half * sizeof(float), hipMemcpyHostToDevice)));
-    attn_fallback = dalloc<unsigned>(4);
+    attn_fallback = store.dalloc<unsigned>(4);
     ZV_CHECK(ZV_BLOCKING(hipMemset(attn_fallback, 0, 4 * sizeof(unsigned))));
     // strict=True: nothing left over
     size_t expected = count_expected();
-    if (expected != staged.size())
-      throw std::invalid_argument("state dict has " + std::to_string(staged.size()) +
+    if (expected != store.staged.size())
+      throw std::invalid_argument("state dict has " + std::to_string(store.staged.size()) +
                                   " tensors, config expects " + std::to_string(expected) +
                                   " (unexpected keys present)");
-    staged.clear();
-    derived.clear();
-    ready = true;
+    store.staged.clear();
+    store.derived.clear();
+    store.ready = true;
   }
 
   size_t count_expected() const {
@@ -857,282 +698,57 @@ struct zv_engine {
     ZV_LAUNCH_CHECK();
   }
 
-  struct Out {              // epilogue of a linear
-    float* C = nullptr; long ldc = 0;
-    Act act;               // bf16 hi/lo copy (act.h null = none)
-    int act_fn = 0;
-    const float* resid = nullptr;
-    const float* rowvec = nullptr; long rowvec_ld = 0; int rows_per_group = 1;
-    const float* orig = nullptr; const float* byp = nullptr;
-    // pair-residual form (bf16 mode): residual / bypass original as bf16 hi/lo pairs
-    const bf16* residh = nullptr; const bf16* residl = nullptr;
-    const bf16* origh = nullptr; const bf16* origl = nullptr;
-  };
-
-  static GemmParams gp_linear(const Linear& Lw, const Act& A, long M) {
-    GemmParams p{};
-    p.M = (int)M; p.N = Lw.N; p.K = Lw.K; p.nz2 = 1; p.Brows = Lw.Npad;
-    p.Ah = A.h; p.Al = A.l; p.lda = A.ld;
-    p.Bh = Lw.hi; p.Bl = Lw.lo; p.ldb = Lw.Kpad;
-    p.bias = Lw.b; p.rows_per_group = 1; p.rpb = 1;
-    return p;
-  }
-
-  // ---------------------------------------------------------------- fp8 mode (ZV_FP8)
   bool fp8_mode() const { return cfg.precision == ZV_FP8; }
-  // the MX-fp8 copy of a bf16 operand, for producers that do not write one themselves
-  void pack8(const Act& A, long M, int K, hipStream_t s) {
-    ZV_REQUIRE(A.h && A.q && K % MX8_BLOCK == 0 && A.ldq >= K && A.ld % 8 == 0, "fp8 pack: operand layout");
-    hipLaunchKernelGGL(zv_mx8_pack_kernel, grid1d(M * (K / 8)), dim3(256), 0, s, A.h, A.ld, M, K, A.q,
-                       A.ldq, A.qs);
-    ZV_LAUNCH_CHECK();
-  }
-  static GemmParams gp_linear8(const Linear& Lw, const Act& A, long M) {
-    GemmParams p = gp_linear(Lw, A, M);
-    p.Ah = reinterpret_cast<const bf16*>(A.q); p.Al = nullptr; p.lda = A.ldq;
-    p.As = A.qs; p.ldas = A.ldq / MX8_BLOCK;
-    p.Bh = reinterpret_cast<const bf16*>(Lw.q8); p.Bl = nullptr; p.ldb = Lw.Kq;
-    p.Bs = Lw.s8; p.ldbs = Lw.Kq / MX8_BLOCK;
-    return p;
-  }
-  // a linear on block-scaled fp8 MFMA (A and W MX-fp8): the counted epilogues, writing the
-  // output's fp8 copy where the next fp8 linear reads it (MXO 1: with the bf16 copy, 2: only)
-  void linear8(const Linear& Lw, const Act& A, long M, const Out& o, hipStream_t s) {
-    GemmParams p = gp_linear8(Lw, A, M);
-    p.act = o.act_fn;
-    p.C = o.C; p.ldc = o.ldc;
-    p.Ch = o.act.h; p.Cl = nullptr; p.ldch = o.act.ld;
-    p.resid = o.resid; p.orig = o.orig; p.byp = o.byp;
-    p.rowvec = o.rowvec; p.rowvec_ld = o.rowvec_ld; p.rows_per_group = o.rows_per_group;
-    p.Cq = o.act.q; p.Cs = o.act.qs; p.ldcq = o.act.ldq;
-    ZV_REQUIRE(p.bias && !o.residh && Lw.N % 8 == 0 && (!o.rowvec || (o.resid && !o.orig && o.act.q)),
-               "fp8 linear: bias; a row vector only on a residual linear with the fp8 copy");
-    const int mxo = o.act.q ? (o.act.h ? 1 : 2) : 0;
-    if (o.resid) {
-      ZV_REQUIRE(mxo != 2 && !o.act_fn, "fp8 residual linear: fp32 stream out");
-      const char* tag = "gemm_fp8_resid";
-      if (o.rowvec) {
-        launch_gemm<128, 128, 2, 2, 8, EPI_STD, 2, 2, MX8_KSTEP, 0, 0, 0, 4, 1>(p, 1, s, tag, true, gridx_resid);
-      } else if (o.orig) {
-        if (mxo) launch_gemm<128, 128, 2, 2, 8, EPI_STD, 2, 2, MX8_KSTEP, 0, 0, 0, 2, 1>(p, 1, s, tag, true, gridx_resid);
-        else launch_gemm<128, 128, 2, 2, 8, EPI_STD, 2, 2, MX8_KSTEP, 0, 0, 0, 2, 0>(p, 1, s, tag, true, gridx_resid);
-      } else {
-        if (mxo) launch_gemm<128, 128, 2, 2, 8, EPI_STD, 2, 2, MX8_KSTEP, 0, 0, 0, 1, 1>(p, 1, s, tag, true, gridx_resid);
-        else launch_gemm<128, 128, 2, 2, 8, EPI_STD, 2, 2, MX8_KSTEP, 0, 0, 0, 1, 0>(p, 1, s, tag, true, gridx_resid);
-      }
-      return;
-    }
-    ZV_REQUIRE(!o.C && mxo, "fp8 plain linear: bias (+ activation) -> fp8 (+ bf16) copy");
-    if (mxo == 2) launch_gemm<128, 128, 2, 2, 8, EPI_STD, 2, 2, MX8_KSTEP, 0, 0, 0, 3, 2>(p, 1, s, "gemm_fp8", true, gridx_plain);
-    else launch_gemm<128, 128, 2, 2, 8, EPI_STD, 2, 2, MX8_KSTEP, 0, 0, 0, 3, 1>(p, 1, s, "gemm_fp8", true, gridx_plain);
-  }
 
+  // ---------------------------------------------------------------- fused attention consumers
+  // NonlinAttention's head-0 consumer, by the hidden width: the second-generation kernel (a2), the
+  // Toeplitz MFMA scoring (tp_na) or the VALU form
   template <int SPLIT>
-  void linear(const Linear& Lw, const Act& A, long M, const Out& o, hipStream_t s) {
-    if constexpr (SPLIT == 1)
-      if (Lw.q8 && A.q) { linear8(Lw, A, M, o, s); return; }
-    // a 16-bit linear whose output also feeds an fp8 linear: its kernel writes the fp8 copy
-    // (wave-specialised residual epilogue) or the pack kernel does
-    if (!linear16<SPLIT>(Lw, A, M, o, s) && o.act.q) pack8(o.act, M, Lw.N, s);
+  void attn_na(const FlashParams& f, int hid, bool a2, bool tp_na, hipStream_t s) {
+    constexpr int QTILES = SPLIT == 3 ? 4 : 8;
+    if constexpr (SPLIT == 1) {
+      if (a2) {
+        const bool q4 = na2_qtiles(f.L) == 4;
+        if (hid <= 128) { if (q4) launch_attn_na2<1, 4>(f, s); else launch_attn_na2<1>(f, s); }
+        else if (hid <= 256) { if (q4) launch_attn_na2<2, 4>(f, s); else launch_attn_na2<2>(f, s); }
+        else if (q4) launch_attn_na2<3, 4>(f, s);
+        else launch_attn_na2<3>(f, s);
+        return;
+      }
+      if (tp_na) {
+        if (hid <= 128) launch_attn_na<1, 1, QTILES, 1>(f, s);
+        else if (hid <= 256) launch_attn_na<1, 2, QTILES, 1>(f, s);
+        else launch_attn_na<1, 3, QTILES, 1>(f, s);
+        return;
+      }
+    }
+    if (hid <= 128) launch_attn_na<SPLIT, 1, QTILES>(f, s);
+    else if (hid <= 256) launch_attn_na<SPLIT, 2, QTILES>(f, s);
+    else launch_attn_na<SPLIT, 3, QTILES>(f, s);
   }
-
-  // returns whether the kernel wrote the output's fp8 copy (o.act.q)
+  // SelfAttention's consumer
   template <int SPLIT>
-  bool linear16(const Linear& Lw, const Act& A, long M, const Out& o, hipStream_t s) {
-    GemmParams p = gp_linear(Lw, A, M);
-    p.act = o.act_fn;
-    p.C = o.C; p.ldc = o.ldc;
-    p.Ch = o.act.h; p.Cl = o.act.l; p.ldch = o.act.ld;
-    p.resid = o.resid; p.rowvec = o.rowvec; p.rowvec_ld = o.rowvec_ld;
-    p.rows_per_group = o.rows_per_group; p.orig = o.orig; p.byp = o.byp;
-    p.residh = o.residh; p.residl = o.residl; p.origh = o.origh; p.origl = o.origl;
+  void attn_sa(const FlashParams& f, bool a2, hipStream_t s) {
     if constexpr (SPLIT == 1) {
-      if (o.residh) {   // pair-residual linear: own instantiation, the residual policy
-        if (occ_resid == 2) launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, GEMM_BK, 0, 1>(p, 1, s, "gemm_bf16", true, gridx_resid);
-        else launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 1, GEMM_BK, 0, 1>(p, 1, s, "gemm_bf16", true, gridx_resid);
-        return false;
-      }
-    }
-    ZV_REQUIRE(!o.residh, "pair residual needs the bf16 mode");
-    const char* tag = SPLIT == 3 ? "gemm_fp32" : "gemm_bf16";
-    if (Lw.N <= 64) {   // own tag: the roofline's gemm_bf16 is the 128x128 instantiation alone
-      launch_gemm<128, 64, 2, 2, SPLIT, EPI_STD>(p, 1, s, SPLIT == 3 ? "gemm_fp32_n64" : "gemm_bf16_n64");
-      return false;
-    }
-    if constexpr (SPLIT == 1) {
-      // bf16-only outputs on whole tiles: the next tile's K loop does not wait for
-      // this tile's stores (counted vmcnt, zv_gemm.inc DEFER)
-      if (defer_stores && !o.resid && !o.C && o.act.h && !o.act.l && Lw.N % 128 == 0 &&
-          o.act.ld % 8 == 0 && occ_plain == 2) {
-        launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, GEMM_BK, 8>(p, 1, s, tag, true, gridx_plain);
-        return false;
-      }
-    }
-    if (o.resid) {   // residual-stream linear: its own symbol / tag (HBM roofline)
-      const char* rtag = SPLIT == 3 ? "gemm_fp32_resid" : "gemm_bf16_resid";   // ROLE 1
-      if constexpr (SPLIT == 1) {
-        // the copy-only form (no fp32 output) on the counted epilogue (A/B ZV_SA_COPY)
-        if (sa_copy && !p.C && p.rowvec && !p.orig && !o.act.l && !o.act.q && p.Ch && p.bias &&
-            Lw.N % 8 == 0 && p.ldch % 8 == 0) {
-          if (occ_resid == 2) launch_resid<SPLIT, 5>(p, s, "gemm_bf16_resid_copy");
-          else launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 1, GEMM_BK, 0, 0, 0, 5>(p, 1, s, "gemm_bf16_resid_copy", true, gridx_resid);
-          return false;
+      if (a2) {
+        // LDS-staged K / V (sa3) while two blocks fit a CU; the register-fed form past that
+        switch (sa3_qpw(f.L)) {
+          case 4: launch_attn_sa3<4>(f, s); break;
+          case 3: launch_attn_sa3<3>(f, s); break;
+          case 2: launch_attn_sa3<2>(f, s); break;
+          default:
+            if (sa2_qpw(f.L) == 3) launch_attn_sa2<3, 1>(f, s);
+            else launch_attn_sa2<2>(f, s);
         }
+        return;
       }
-      // the counted residual epilogue (zv_gemm.inc gemm_epilogue_res; ROLE 2 = with the
-      // bypass original) where its preconditions hold, else the general epilogue
-      const bool counted = (res_counted & 1) && p.bias && !(p.rowvec && p.orig) && !p.act && p.C &&
-                           Lw.N % 8 == 0 && p.ldc % 4 == 0 && (!p.Ch || p.ldch % 8 == 0) &&
-                           (!p.orig || p.byp) && (p.Cl != nullptr) == (SPLIT == 3 && p.Ch != nullptr);
-      if (!counted) {
-        if (occ_resid == 2) launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2>(p, 1, s, rtag, true, gridx_resid);
-        else launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 1>(p, 1, s, rtag, true, gridx_resid);
-      } else if (p.orig) {           // one tag per ROLE: the roofline's bytes and PMC traffic per symbol
-        const char* t2 = SPLIT == 3 ? "gemm_fp32_resid_byp" : "gemm_bf16_resid_byp";
-        if (occ_resid == 2) launch_resid<SPLIT, 2>(p, s, t2);
-        else launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 1, GEMM_BK, 0, 0, 0, 2>(p, 1, s, t2, true, gridx_resid);
-      } else if (p.rowvec) {         // + the row-group vector (ROLE 4)
-        rtag = SPLIT == 3 ? "gemm_fp32_resid_rv" : "gemm_bf16_resid_rv";
-        if constexpr (SPLIT == 1)
-          if (o.act.q && o.act.h && p.Ch) {   // fp8 mode: + the stream's fp8 copy (MXO 1)
-            p.Cq = o.act.q; p.Cs = o.act.qs; p.ldcq = o.act.ldq;
-            launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 4, 1>(p, 1, s, rtag, true, gridx_resid);
-            return true;
-          }
-        if (occ_resid == 2) launch_resid<SPLIT, 4>(p, s, rtag);
-        else launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 1, GEMM_BK, 0, 0, 0, 4>(p, 1, s, rtag, true, gridx_resid);
-      } else {
-        if (occ_resid == 2) launch_resid<SPLIT, 1>(p, s, rtag);
-        else launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 1, GEMM_BK, 0, 0, 0, 1>(p, 1, s, rtag, true, gridx_resid);
+      if (sa_tp) {                 // positional term as a Toeplitz MFMA product
+        if (sa_tp == 3) launch_attn_sa_tp<0, 1>(f, s);   // A/B: the compiler's one-wave register budget
+        else launch_attn_sa_tp<0>(f, s);
+        return;
       }
-      return false;
     }
-    // 96-wide tiles where they waste fewer columns than 128-wide ones (the attention-score
-    // projection, N = 272: 288 computed columns instead of 384)
-    if ((Lw.N + 95) / 96 * 96 < (Lw.N + 127) / 128 * 128) {
-      // ZV_N96: 2 (default) = 128x128 tiles on the counted plain epilogue (384 columns computed),
-      // 1 = 128x64 counted (320), 0 = 128x96 on the general epilogue (288): bitwise equal,
-      // 9.1 / 10.1 / 12.9 ms per step (profiles/r02_n96_counted_ab.txt)
-      const bool cnt = (res_counted & 2) && p.bias && p.Ch && !p.C && !p.resid && !p.rowvec && !p.act &&
-                       Lw.N % 8 == 0 && p.ldch % 8 == 0 && (p.Cl != nullptr) == (SPLIT == 3);
-      if (cnt && n96_mode == 1) {
-        launch_gemm<128, 64, 2, 2, SPLIT, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, SPLIT == 3 ? "gemm_fp32_n96" : "gemm_bf16_n96", true, gridx_plain);
-        return false;
-      }
-      if (cnt && n96_mode == 2 && SPLIT == 1) {
-        // 128 x 64 tiles at 3 blocks per CU (320 columns computed), at every size: 15.2 -> 13.9 ms per
-        // C2 step against 128 x 128 for the large launches (round 6, profiles/r06_n96_ab.txt; 64 x 64
-        // with a 4-deep ring 15.3); bitwise equal
-        launch_gemm<128, 64, 2, 2, SPLIT, EPI_STD, 2, 3, GEMM_BK, 0, 0, 0, 3>(p, 1, s, "gemm_bf16_n96", true, gridx_plain);
-        return false;
-      }
-      if (cnt && n96_mode == 2) {
-        launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, SPLIT == 3 ? "gemm_fp32_n96" : "gemm_bf16_n96", true, gridx_plain);
-        return false;
-      }
-      launch_gemm<128, 96, 2, 2, SPLIT, EPI_STD, 2, 2>(p, 1, s, SPLIT == 3 ? "gemm_fp32_n96" : "gemm_bf16_n96", true, gridx_plain);
-      return false;
-    }
-    // bias (+ activation) -> bf16 copy: the counted epilogue (ROLE 3)
-    const bool counted = (res_counted & 2) && p.bias && p.Ch && !p.C && !p.rowvec && Lw.N % 8 == 0 &&
-                         p.ldch % 8 == 0 && (p.Cl != nullptr) == (SPLIT == 3);
-    if constexpr (SPLIT == 1)
-      if (counted && !o.act.q && use_gemm256(p)) {
-        launch_gemm256<EPI_STD, 3>(p, s, tag, gemm256 == 1);
-        return false;
-      }
-    if (counted) {
-      // (fewer than 1.5 128 x 128 tiles per CU: 128 x 64 tiles, 3 blocks per CU; bitwise equal;
-      // lab 3660 x 1536 x 512 13.7 -> 12.9 us, 1830 rows 10.5 -> 9.0, r05_resid_tiles_ab.txt)
-      if (occ_plain == 2 && SPLIT == 1 && (long)cdiv(p.M, 128) * cdiv(p.N, 128) < zv_num_cus() * 3 / 2)
-        launch_gemm<128, 64, 2, 2, SPLIT, EPI_STD, 2, 3, GEMM_BK, 0, 0, 0, 3>(p, 1, s, tag, true, gridx_plain);
-      else if (occ_plain == 2) launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, tag, true, gridx_plain);
-      else launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 1, GEMM_BK, 0, 0, 0, 3>(p, 1, s, tag, true, gridx_plain);
-    } else if (occ_plain == 2) {
-      launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2>(p, 1, s, tag, true, gridx_plain);
-    } else {
-      launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 1>(p, 1, s, tag, true, gridx_plain);
-    }
-    return false;
-  }
-
-  // mixed mode's attention-score projection: the weight-split product a.(wh + wl) (SPLIT 2:
-  // the 16-bit layer input against the weight's hi/lo pair, 2 MFMAs per product instead of
-  // the bf16x3 form's 3).  tools/precision_study.py --r03: mean |err| 5.4e-4 / 8.8e-4 / 9.3e-4
-  // on the C1 / dialog / stereo fixtures vs 5.2e-4 / 8.6e-4 / 8.9e-4 fully split
-  // (profiles/r03_precision_study_r03_*.txt); 128x64 tiles (the hi/lo weight stage fits two
-  // blocks per CU)
-  void attn_in_wsplit(const Linear& Lw, const Act& A, long M, const Out& o, hipStream_t s) {
-    GemmParams p = gp_linear(Lw, A, M);
-    p.Al = nullptr;
-    p.Ch = o.act.h; p.Cl = nullptr; p.ldch = o.act.ld;
-    ZV_REQUIRE(p.bias && p.Ch && !o.act.l && !o.C && !o.resid && !o.act_fn && Lw.lo && Lw.N % 8 == 0 &&
-                   p.ldch % 8 == 0,
-               "weight-split projection: bias -> 16-bit copy");
-    launch_gemm<128, 64, 2, 2, 2, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, "gemm_wsplit_n96", true, gridx_plain);
-  }
-
-  // The layer's fused-epilogue launch choices on a prepared GemmParams (shared with zv_linear_check).
-  // NonlinAttention in-projection (EPI_NA: rows permuted by perm_na)
-  template <int SPLIT>
-  void launch_na_in(const GemmParams& p, hipStream_t s) {
-    const bool split = SPLIT == 3;
-    bool done = false;
-    // counted NA epilogue: 16-bit modes (in the split mode it differs from the general one
-    // by up to 1.1e-4 in the decoder output, tools/counted_bisect.py; not bitwise: kept off)
-    if (done) {}
-    else if ((res_counted & 4) && SPLIT == 1 && occ_fused == 2 && p.bias && p.N % 48 == 0 && p.ldch % 4 == 0) {
-      // (64-row tiles at 3 blocks per CU at every size: 32.5 -> 31.4 ms per C2 step against 128-row
-      // tiles for the large launches, round 6, profiles/r06_ffn_rows_na_tile_ab.txt; bitwise equal)
-      if (SPLIT == 1)
-        launch_gemm<64, 96, 2, 2, SPLIT, EPI_NA, 2, 3, GEMM_BK, 0, 0, 0, 3>(p, 1, s, "gemm_bf16_na", true, gridx_fused);
-      else
-        launch_gemm<128, 96, 2, 2, SPLIT, EPI_NA, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, split ? "gemm_fp32_na" : "gemm_bf16_na", true, gridx_fused);
-    }
-    else if (occ_fused == 2) launch_gemm<128, 96, 2, 2, SPLIT, EPI_NA, 2, 2>(p, 1, s, split ? "gemm_fp32_na" : "gemm_bf16_na", true, gridx_fused);
-    else launch_gemm<128, 96, 2, 2, SPLIT, EPI_NA, 2, 1>(p, 1, s, split ? "gemm_fp32_na" : "gemm_bf16_na", true, gridx_fused);
-  }
-  // SelfAttention value projection (EPI_TRANS); sa_split: the fp16 parity mode's a . (w_hi + w_lo)
-  template <int SPLIT>
-  void launch_value_t(const GemmParams& p, bool sa_split, bool has_lo, hipStream_t s) {
-    const bool split = SPLIT == 3;
-    // N = 48 (64 padded): 64-row tiles give 2x the blocks of a 128-row grid (one tile column)
-    if (sa_split) {                    // fp16 parity mode: a . (w_hi + w_lo)
-      ZV_REQUIRE(has_lo && (res_counted & 16), "weight-split value projection");
-      launch_gemm<64, 64, 2, 2, 2, EPI_TRANS, ZV_WSPLIT_T_STAGES, ZV_WSPLIT_T_STAGES < 4 ? 2 : 1, GEMM_BK, 0, 0, 0, 3>(
-          p, 1, s, "gemm_wsplit_t", true, -1);
-    } else if (skinny_tiles && (res_counted & 16))
-      // (a 4-deep K ring: one 64-row tile per block has 8 K steps and little else in flight;
-      // 2 -> 4 stages: 24.0 -> 18.9 ms per C2 step, profiles/r05_vt_stages_ab.txt)
-      launch_gemm<64, 64, 2, 2, SPLIT, EPI_TRANS, 4, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, split ? "gemm_fp32_t" : "gemm_bf16_t", true, -1);
-    else if (skinny_tiles) launch_gemm<64, 64, 2, 2, SPLIT, EPI_TRANS>(p, 1, s, split ? "gemm_fp32_t" : "gemm_bf16_t", true, -1);
-    else launch_gemm<128, 64, 2, 2, SPLIT, EPI_TRANS>(p, 1, s, split ? "gemm_fp32_t" : "gemm_bf16_t");
-  }
-  // ConvolutionModule in-projection (EPI_GLU: rows permuted by perm_glu); g8: MX-fp8 operands
-  template <int SPLIT>
-  void launch_glu_in(const GemmParams& p, bool g8, hipStream_t s) {
-    const bool split = SPLIT == 3;
-    bool done = false;
-    if (g8) {
-      ZV_REQUIRE(p.bias && p.N % 32 == 0 && p.ldch % 8 == 0, "fp8 GLU linear layout");
-      launch_gemm<128, 128, 2, 2, 8, EPI_GLU, 2, 2, MX8_KSTEP, 0, 0, 0, 3>(p, 1, s, "gemm_fp8_glu", true, gridx_fused);
-      done = true;
-    }
-    if constexpr (SPLIT == 1)
-      if (!done && (res_counted & 8) && p.bias && p.N % 32 == 0 && p.ldch % 8 == 0 && use_gemm256(p)) {
-        launch_gemm256<EPI_GLU, 3>(p, s, "gemm_bf16_glu", gemm256 == 1);
-        done = true;
-      }
-    if (done) {}
-    else if ((res_counted & 8) && occ_fused == 2 && p.bias && p.N % 32 == 0 && p.ldch % 8 == 0) {
-      // (fewer than 1.5 128 x 128 tiles per CU: 64 x 128, 3 blocks per CU, as launch_resid)
-      if (SPLIT == 1 && (long)cdiv(p.M, 128) * cdiv(p.N, 128) < zv_num_cus() * 3 / 2)
-        launch_gemm<64, 128, 2, 2, SPLIT, EPI_GLU, 2, 3, GEMM_BK, 0, 0, 0, 3>(p, 1, s, "gemm_bf16_glu", true, gridx_fused);
-      else
-        launch_gemm<128, 128, 2, 2, SPLIT, EPI_GLU, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, split ? "gemm_fp32_glu" : "gemm_bf16_glu", true, gridx_fused);
-    }
-    else if (occ_fused == 2) launch_gemm<128, 128, 2, 2, SPLIT, EPI_GLU, 2, 2>(p, 1, s, split ? "gemm_fp32_glu" : "gemm_bf16_glu", true, gridx_fused);
-    else launch_gemm<128, 128, 2, 2, SPLIT, EPI_GLU, 2, 1>(p, 1, s, split ? "gemm_fp32_glu" : "gemm_bf16_glu", true, gridx_fused);
+    launch_attn_sa<SPLIT>(f, s);
   }
 
   // ---------------------------------------------------------------- one layer
@@ -1156,21 +772,21 @@ struct zv_engine {
     const int qkpN = W.attn_in.N;
     Act qkp = ws.qkp.get(M, qkpN, split);
     {
-      // mixed mode: the attention-score projection as a split product (the layer input
-      // src_a carries its lo half); q, k, p stay 16-bit
+      // mixed mode: the attention-score projection as a weight-split product (attn_in_wsplit;
+      // the fully split form is retired, zv_linear.inc); q, k, p stay 16-bit
       Out o; o.act = qkp;
-      if (SPLIT == 1 && io_split && mixed_wsplit) attn_in_wsplit(W.attn_in, src_a, M, o, s);
-      else if (SPLIT == 1 && io_split) linear<3>(W.attn_in, src_a, M, o, s);
+      if (SPLIT == 1 && io_split) attn_in_wsplit(W.attn_in, src_a, M, o, s);
       else linear<SPLIT>(W.attn_in, src_a, M, o, s);
     }
-    // head-0 scoring of the stats / NonlinAttention pair: Toeplitz MFMA form in bf16 mode
-    // (mixed mode keeps the fp32 positional table there: its lo half would not fit the
-    // NonlinAttention image at dialog lengths)
-    const bool tp_na = SPLIT == 1 && sa_tp && (!io_split || mixed_tpna);
+    // head-0 scoring of the stats / NonlinAttention pair: Toeplitz MFMA form in the 16-bit modes
+    // (the fp16 parity mode included, without the table's lo half, which would not fit the
+    // NonlinAttention image at dialog lengths; profiles/r03_mixed_ab.txt, zv_linear.inc)
+    const bool tp_na = SPLIT == 1 && sa_tp;
     // attention: either materialise W (reference structure; A/B path, and the
     // fallback for lengths whose fused LDS images do not fit) or keep only
     // per-row softmax statistics and recompute scores inside each consumer
-    const int sa_plo = (SPLIT == 1 && sa_tp) ? (io_split && mixed_plo ? 1 : 0) : -1;
+    // (sa_plo 0: no mode keeps the lo half of the SelfAttention Toeplitz table)
+    const int sa_plo = (SPLIT == 1 && sa_tp) ? 0 : -1;
     // second-generation consumers (zv_flash2.inc: base-2 scores from the log2(e)-scaled k / p
     // weights, no running maximum, no statistics pass) wherever this stack's weights were built for
     // them (Z.b2: the bf16 / fp8 engines, and the fp16 parity mode's decoder)
@@ -1265,26 +881,7 @@ struct zv_engine {
         f.nv = hid;
         f.mulh = y.h; f.mull = y.l; f.ldmul = y.ld;
         f.oh = nao.h; f.ol = nao.l; f.ldo = nao.ld; f.ocol_per_head = 0;
-        constexpr int QTILES = SPLIT == 3 ? 4 : 8;
-        bool done = false;
-        if constexpr (SPLIT == 1)
-          if (a2) {
-            const bool q4 = na2_qtiles(L) == 4;
-            if (hid <= 128) { if (q4) launch_attn_na2<1, 4>(f, s); else launch_attn_na2<1>(f, s); }
-            else if (hid <= 256) { if (q4) launch_attn_na2<2, 4>(f, s); else launch_attn_na2<2>(f, s); }
-            else if (q4) launch_attn_na2<3, 4>(f, s);
-            else launch_attn_na2<3>(f, s);
-            done = true;
-          } else if (tp_na) {
-            if (hid <= 128) launch_attn_na<1, 1, QTILES, 1>(f, s);
-            else if (hid <= 256) launch_attn_na<1, 2, QTILES, 1>(f, s);
-            else launch_attn_na<1, 3, QTILES, 1>(f, s);
-            done = true;
-          }
-        if (done) {}
-        else if (hid <= 128) launch_attn_na<SPLIT, 1, QTILES>(f, s);
-        else if (hid <= 256) launch_attn_na<SPLIT, 2, QTILES>(f, s);
-        else launch_attn_na<SPLIT, 3, QTILES>(f, s);
+        attn_na<SPLIT>(f, hid, a2, tp_na, s);
       }
       if (f8) pack8(nao, M, hid, s);
       linear<SPLIT>(W.na_out, nao, M, res, s);
@@ -1325,28 +922,7 @@ struct zv_engine {
         f.nv = vd;
         f.oh = o.h; f.ol = o.l; f.ldo = o.ld; f.ocol_per_head = vd;
         if (sa_split) { f.ol = o.h + HV; f.oh2 = o.h + 2 * HV; }   // [o_hi | o_lo | o_hi]
-        bool done = false;
-        if constexpr (SPLIT == 1)
-          if (a2) {
-            // LDS-staged K / V (sa3) while two blocks fit a CU; the register-fed form past that
-            switch (sa3_qpw(L)) {
-              case 4: launch_attn_sa3<4>(f, s); break;
-              case 3: launch_attn_sa3<3>(f, s); break;
-              case 2: launch_attn_sa3<2>(f, s); break;
-              default:
-                if (sa2_qpw(L) == 3) launch_attn_sa2<3, 1>(f, s);
-                else launch_attn_sa2<2>(f, s);
-            }
-            done = true;
-          } else if (sa_tp) {            // positional term as a Toeplitz MFMA product
-            if (sa_tp == 3) {          // A/B: the compiler's one-wave register budget
-              if (io_split && mixed_plo) launch_attn_sa_tp<1, 1>(f, s);
-              else launch_attn_sa_tp<0, 1>(f, s);
-            } else if (io_split && mixed_plo) launch_attn_sa_tp<1>(f, s);
-            else launch_attn_sa_tp<0>(f, s);
-            done = true;
-          }
-        if (!done) launch_attn_sa<SPLIT>(f, s);
+        attn_sa<SPLIT>(f, a2, s);
       }
       Out e = res;
       if (temb) { e.rowvec = temb; e.rowvec_ld = D; e.rows_per_group = L; }
@@ -1856,8 +1432,34 @@ struct zv_engine {
 
 static void check_ready(zv_handle h) {
   ZV_REQUIRE(h != nullptr, "null engine handle");
-  ZV_REQUIRE(h->ready, "engine weights not finalized (call zv_finalize)");
+  ZV_REQUIRE(h->store.ready, "engine weights not finalized (call zv_finalize)");
   h->check_dev_err();
+}
+
+// the bodies the handles' entry points share (engine, vocoder, BigVGAN: `what` names the handle)
+template <class H>
+static int api_set_weight(H* h, const char* what, const char* name, const float* host_data, int64_t numel) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(h, "bad arguments");
+  h->store.set(what, name, host_data, numel);
+  ZV_API_END
+}
+template <class H>
+static int api_finalize(H* h, const char* null_msg) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(h != nullptr, null_msg);
+  h->finalize();
+  ZV_API_END
+}
+// *_create: make() validates, builds and returns the handle; a failure leaves the message and null
+template <class F>
+static auto api_create(F make) -> decltype(make()) {
+  try {
+    return make();
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return nullptr;
+  }
 }
 
 // GEMM microbenchmark on random operands: C(M,N) fp32 = A(M,K) . W(N,K)^T
@@ -1898,7 +1500,7 @@ const char* zv_version(void) {
 }
 
 zv_handle zv_create(const zv_config* cfg) {
-  try {
+  return api_create([&] {
     ZV_REQUIRE(cfg != nullptr, "null config");
     ZV_REQUIRE(cfg->num_stacks >= 1 && cfg->num_stacks <= ZV_MAX_STACKS, "bad num_stacks");
     ZV_REQUIRE(cfg->variant >= 0 && cfg->variant <= 3, "bad variant");
@@ -1906,28 +1508,16 @@ zv_handle zv_create(const zv_config* cfg) {
                    (cfg->precision == ZV_FP8 && std::string(ZV_OPERAND_NAME) == "bf16"),
                "bad precision");
     return new zv_engine(*cfg);
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return nullptr;
-  }
+  });
 }
 
 void zv_destroy(zv_handle h) { delete h; }
 
 int zv_set_weight(zv_handle h, const char* name, const float* host_data, int64_t numel) {
-  ZV_API_BEGIN
-  ZV_REQUIRE(h && name && (host_data || numel == 0), "bad arguments");
-  ZV_REQUIRE(!h->ready, "engine already finalized");
-  h->staged[name].assign(host_data, host_data + numel);
-  ZV_API_END
+  return api_set_weight(h, "engine", name, host_data, numel);
 }
 
-int zv_finalize(zv_handle h) {
-  ZV_API_BEGIN
-  ZV_REQUIRE(h != nullptr, "null engine handle");
-  h->finalize();
-  ZV_API_END
-}
+int zv_finalize(zv_handle h) { return api_finalize(h, "null engine handle"); }
 
 int zv_reserve(zv_handle h, int max_batch, int max_frames) {
   ZV_API_BEGIN
@@ -2457,15 +2047,18 @@ int zv_linear_check(zv_linear_check_args* a) {
              "zv_linear_check: the transposed outputs");
   ZV_REQUIRE((form != ZV_LIN_NA || N % 48 == 0) && (form != ZV_LIN_GLU || N % 32 == 0), "zv_linear_check: NA / GLU widths");
 
-  zv_config c{};
-  c.precision = split3 ? ZV_FP32 : (a->split == 2 ? ZV_MIXED : ZV_BF16);
-  zv_engine eng(c);                       // a bare engine: its dispatch policy and weight builder
-  eng.staged["chk.weight"].assign(a->W, a->W + (size_t)N * K);
-  eng.staged["chk.bias"].assign(a->bias, a->bias + N);
-  std::vector<int> perm;
+  LinearPolicy policy;                     // the engine's dispatch policy (its run-time knobs)
+  WeightStore store;
+  std::vector<int> perm(N);               // the fused epilogues' row order (identity otherwise)
+  for (int n = 0; n < N; ++n) perm[n] = n;
   if (form == ZV_LIN_NA) perm = zv_engine::perm_na(N / 3);
   if (form == ZV_LIN_GLU) perm = zv_engine::perm_glu(N / 2);
-  const Linear Lw = eng.make_linear("chk", N, K, true, false, perm.empty() ? nullptr : &perm);
+  std::vector<float> wp((size_t)N * K), bp(N);
+  for (int n = 0; n < N; ++n) {
+    memcpy(&wp[(size_t)n * K], a->W + (size_t)perm[n] * K, (size_t)K * sizeof(float));
+    bp[n] = a->bias[perm[n]];
+  }
+  const Linear Lw = store.make_linear(wp.data(), N, K, bp.data());
 
   ChkDev dev;
   hipStream_t s = nullptr;
@@ -2496,7 +2089,7 @@ int zv_linear_check(zv_linear_check_args* a) {
   const uint8_t* dmask = a->rowmask ? dev.up(a->rowmask, (size_t)M) : nullptr;
 
   if (!fused) {
-    zv_engine::Out o;
+    Out o;
     o.act_fn = a->act;
     if (dC) { o.C = dC + (size_t)G * a->ldc; o.ldc = a->ldc; }
     if (dCh) { o.act.h = dCh + (size_t)G * a->ldch; o.act.ld = a->ldch; }
@@ -2519,11 +2112,11 @@ int zv_linear_check(zv_linear_check_args* a) {
       o.rowvec = dev.up(a->rowvec, (size_t)cdiv(M, a->rows_per_group) * N);
       o.rowvec_ld = N; o.rows_per_group = a->rows_per_group;
     }
-    if (a->split == 2) eng.attn_in_wsplit(Lw, A, M, o, s);
-    else if (split3) eng.linear16<3>(Lw, A, M, o, s);
-    else eng.linear16<1>(Lw, A, M, o, s);
+    if (a->split == 2) policy.attn_in_wsplit(Lw, A, M, o, s);
+    else if (split3) policy.linear16<3>(Lw, A, M, o, s);
+    else policy.linear16<1>(Lw, A, M, o, s);
   } else {
-    GemmParams p = zv_engine::gp_linear(Lw, A, M);
+    GemmParams p = LinearPolicy::gp_linear(Lw, A, M);
     if (a->split == 2) p.Al = nullptr;
     if (dCh) { p.Ch = dCh + (size_t)G * a->ldch; p.ldch = a->ldch; }
     if (dCl) p.Cl = dCl + (size_t)G * a->ldch;
@@ -2534,12 +2127,12 @@ int zv_linear_check(zv_linear_check_args* a) {
     }
     if (form == ZV_LIN_GLU) p.rowmask = dmask;
     if (form == ZV_LIN_NA) {
-      if (split3) eng.launch_na_in<3>(p, s); else eng.launch_na_in<1>(p, s);
+      if (split3) policy.launch_na_in<3>(p, s); else policy.launch_na_in<1>(p, s);
     } else if (form == ZV_LIN_TRANS) {
-      if (split3) eng.launch_value_t<3>(p, false, true, s);
-      else eng.launch_value_t<1>(p, a->split == 2, Lw.lo != nullptr, s);
+      if (split3) policy.launch_value_t<3>(p, false, true, s);
+      else policy.launch_value_t<1>(p, a->split == 2, Lw.lo != nullptr, s);
     } else {
-      if (split3) eng.launch_glu_in<3>(p, false, s); else eng.launch_glu_in<1>(p, false, s);
+      if (split3) policy.launch_glu_in<3>(p, false, s); else policy.launch_glu_in<1>(p, false, s);
     }
   }
   ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
@@ -2566,15 +2159,9 @@ int zv_ffn_check(zv_ffn_check_args* a) {
                  (!a->C2l || a->C2h),
              "zv_ffn_check: the form's operands");
   ZV_REQUIRE(a->part_slots <= zv_num_cus(), "zv_ffn_check: more lines than CUs");
-  zv_config c{};
-  c.precision = ZV_BF16;
-  zv_engine eng(c);
-  eng.staged["w1.weight"].assign(a->W1, a->W1 + (size_t)H * D);
-  eng.staged["w1.bias"].assign(a->b1, a->b1 + H);
-  eng.staged["w2.weight"].assign(a->W2, a->W2 + (size_t)D * H);
-  eng.staged["w2.bias"].assign(a->b2, a->b2 + D);
-  const Linear L1 = eng.make_linear("w1", H, D, true, false);
-  const Linear L2 = eng.make_linear("w2", D, H, true, false);
+  WeightStore store;
+  const Linear L1 = store.make_linear(a->W1, H, D, a->b1);
+  const Linear L2 = store.make_linear(a->W2, D, H, a->b2);
   ChkDev dev;
   hipStream_t s = nullptr;
   const long n = (long)H * D;
@@ -2646,7 +2233,7 @@ int64_t zv_host_block_count(void) { return (int64_t)g_zv_host_blocks.load(); }
 
 int64_t zv_device_bytes(zv_handle h) {
   if (!h) return 0;
-  return (int64_t)(h->weight_bytes + h->ws_dec.bytes() + h->ws_split[0].bytes() + h->ws_split[1].bytes() +
+  return (int64_t)(h->store.weight_bytes + h->ws_dec.bytes() + h->ws_split[0].bytes() + h->ws_split[1].bytes() +
                    h->ws_split[2].bytes() + h->ws_txt.bytes() + h->gx.bytes +
                    h->gtc.bytes + h->gsc.bytes + h->gpad.bytes + h->ggrows.bytes);
 }
@@ -2757,42 +2344,30 @@ int zv_speech_condition(zv_handle h, const float* prompt, int B, int Tp, int F,
 
 // ---------------------------------------------------------------- vocoder
 zv_vocoder_handle zv_vocoder_create(const zv_vocoder_config* cfg) {
-  try {
+  return api_create([&] {
     ZV_REQUIRE(cfg != nullptr, "null vocoder config");
     ZV_REQUIRE(cfg->precision == ZV_FP32 || cfg->precision == ZV_BF16, "bad precision");
     ZV_REQUIRE(cfg->n_mels > 0 && cfg->dim > 0 && cfg->intermediate_dim > 0 && cfg->num_layers > 0,
                "bad vocoder dimensions");
     ZV_REQUIRE(cfg->embed_kernel % 2 == 1, "embed kernel must be odd");
     return new zv_vocoder(*cfg);
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return nullptr;
-  }
+  });
 }
 
 void zv_vocoder_destroy(zv_vocoder_handle v) { delete v; }
 
 int zv_vocoder_set_weight(zv_vocoder_handle v, const char* name, const float* host_data,
                           int64_t numel) {
-  ZV_API_BEGIN
-  ZV_REQUIRE(v && name && (host_data || numel == 0), "bad arguments");
-  ZV_REQUIRE(!v->ready, "vocoder already finalized");
-  v->staged[name].assign(host_data, host_data + numel);
-  ZV_API_END
+  return api_set_weight(v, "vocoder", name, host_data, numel);
 }
 
-int zv_vocoder_finalize(zv_vocoder_handle v) {
-  ZV_API_BEGIN
-  ZV_REQUIRE(v != nullptr, "null vocoder handle");
-  v->finalize();
-  ZV_API_END
-}
+int zv_vocoder_finalize(zv_vocoder_handle v) { return api_finalize(v, "null vocoder handle"); }
 
 int zv_vocoder_decode(zv_vocoder_handle v, const float* mel, int layout, float feat_scale,
                       float feat_bias, const int32_t* lens, int B, int T, float* wav, int clamp,
                       void* stream) {
   ZV_API_BEGIN
-  ZV_REQUIRE(v != nullptr && v->ready, "vocoder not finalized (call zv_vocoder_finalize)");
+  ZV_REQUIRE(v != nullptr && v->store.ready, "vocoder not finalized (call zv_vocoder_finalize)");
   ZV_REQUIRE(B > 0 && T > 0, "empty batch");
   ZV_REQUIRE(layout == 0 || layout == 1, "layout must be 0 (B,C,T) or 1 (B,T,C)");
   ZV_REQUIRE(feat_scale != 0.f, "feat_scale must be nonzero");
@@ -2806,40 +2381,28 @@ int zv_vocoder_decode(zv_vocoder_handle v, const float* mel, int layout, float f
 
 // ---------------------------------------------------------------- BigVGAN
 zv_bigvgan_handle zv_bigvgan_create(const zv_bigvgan_config* cfg) {
-  try {
+  return api_create([&] {
     ZV_REQUIRE(cfg != nullptr, "null bigvgan config");
     ZV_REQUIRE(cfg->precision == ZV_FP32 || cfg->precision == ZV_BF16, "bad precision");
     ZV_REQUIRE(cfg->num_mels > 0 && cfg->upsample_initial_channel > 0, "bad bigvgan dimensions");
     return new zv_bigvgan(*cfg);
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return nullptr;
-  }
+  });
 }
 
 void zv_bigvgan_destroy(zv_bigvgan_handle v) { delete v; }
 
 int zv_bigvgan_set_weight(zv_bigvgan_handle v, const char* name, const float* host_data,
                           int64_t numel) {
-  ZV_API_BEGIN
-  ZV_REQUIRE(v && name && (host_data || numel == 0), "bad arguments");
-  ZV_REQUIRE(!v->ready, "bigvgan already finalized");
-  v->staged[name].assign(host_data, host_data + numel);
-  ZV_API_END
+  return api_set_weight(v, "bigvgan", name, host_data, numel);
 }
 
-int zv_bigvgan_finalize(zv_bigvgan_handle v) {
-  ZV_API_BEGIN
-  ZV_REQUIRE(v != nullptr, "null bigvgan handle");
-  v->finalize();
-  ZV_API_END
-}
+int zv_bigvgan_finalize(zv_bigvgan_handle v) { return api_finalize(v, "null bigvgan handle"); }
 
 int zv_bigvgan_decode(zv_bigvgan_handle v, const float* mel, int layout, float feat_scale,
                       float feat_bias, const int32_t* lens, int B, int T, float* wav,
                       void* stream) {
   ZV_API_BEGIN
-  ZV_REQUIRE(v != nullptr && v->ready, "bigvgan not finalized (call zv_bigvgan_finalize)");
+  ZV_REQUIRE(v != nullptr && v->store.ready, "bigvgan not finalized (call zv_bigvgan_finalize)");
   ZV_REQUIRE(B > 0 && T > 0, "empty batch");
   ZV_REQUIRE(layout == 0 || layout == 1, "layout must be 0 (B,C,T) or 1 (B,T,C)");
   ZV_REQUIRE(feat_scale != 0.f, "feat_scale must be nonzero");
@@ -2855,17 +2418,12 @@ int64_t zv_bigvgan_device_bytes(zv_bigvgan_handle v) { return v ? (int64_t)v->de
 
 zv_fbank_handle zv_fbank_create(int n_fft, int hop, int n_mels, const float* host_window,
                                 const float* host_fb) {
-  zv_fbank* f = nullptr;
-  try {
+  return api_create([&] {
     ZV_REQUIRE(host_window && host_fb, "null window / filterbank");
-    f = new zv_fbank();
+    std::unique_ptr<zv_fbank> f(new zv_fbank());
     f->init(n_fft, hop, n_mels, host_window, host_fb);
-    return f;
-  } catch (const std::exception& e) {
-    delete f;
-    g_last_error = e.what();
-    return nullptr;
-  }
+    return f.release();
+  });
 }
 
 void zv_fbank_destroy(zv_fbank_handle f) { delete f; }
@@ -2892,17 +2450,12 @@ int zv_fbank_extract(zv_fbank_handle f, const float* wav, int64_t wav_ld, const 
 
 zv_resample_handle zv_resample_create(int o, int n, int S, const int32_t* host_start,
                                       const float* host_table) {
-  zv_resample* h = nullptr;
-  try {
+  return api_create([&] {
     ZV_REQUIRE(host_start && host_table, "null host_start / host_table");
-    h = new zv_resample();
+    std::unique_ptr<zv_resample> h(new zv_resample());
     h->init(o, n, S, host_start, host_table);
-    return h;
-  } catch (const std::exception& e) {
-    delete h;
-    g_last_error = e.what();
-    return nullptr;
-  }
+    return h.release();
+  });
 }
 
 void zv_resample_destroy(zv_resample_handle h) { delete h; }
@@ -2921,16 +2474,11 @@ int zv_resample_apply(zv_resample_handle h, const float* wav, int64_t wav_ld, co
 int64_t zv_resample_device_bytes(zv_resample_handle h) { return h ? (int64_t)h->bytes : 0; }
 
 zv_wavjoin_handle zv_wavjoin_create(int frame, float thr, int keep_edge, int max_gap, int fade) {
-  zv_wavjoin* h = nullptr;
-  try {
-    h = new zv_wavjoin();
+  return api_create([&] {
+    std::unique_ptr<zv_wavjoin> h(new zv_wavjoin());
     h->init(frame, thr, keep_edge, max_gap, fade);
-    return h;
-  } catch (const std::exception& e) {
-    delete h;
-    g_last_error = e.what();
-    return nullptr;
-  }
+    return h.release();
+  });
 }
 
 void zv_wavjoin_destroy(zv_wavjoin_handle h) { delete h; }
@@ -2955,7 +2503,7 @@ int64_t zv_wavjoin_device_bytes(zv_wavjoin_handle h) { return h ? (int64_t)h->by
 
 int64_t zv_vocoder_device_bytes(zv_vocoder_handle v) {
   if (!v) return 0;
-  return (int64_t)(v->weight_bytes + v->x.bytes + v->frames.bytes + v->col.bytes() +
+  return (int64_t)(v->store.weight_bytes + v->x.bytes + v->frames.bytes + v->col.bytes() +
                    v->h.bytes() + v->hid.bytes() + v->spec.bytes());
 }
 

@@ -182,10 +182,7 @@ __global__ void zv_voc_ola_kernel(const float* frames, const float* window, cons
 // ===========================================================================
 struct zv_vocoder {
   zv_vocoder_config cfg;
-  std::map<std::string, std::vector<float>> staged;
-  std::vector<void*> allocs;
-  size_t weight_bytes = 0;
-  bool ready = false;
+  WeightStore store;
   int nbins = 0, nbins_pad = 0, spec_ld = 0;
   Linear embed, head, basis;
   std::vector<Linear> pw1, pw2;
@@ -196,54 +193,11 @@ struct zv_vocoder {
   ActBuf col, h, hid, spec;
 
   explicit zv_vocoder(const zv_vocoder_config& c) : cfg(c) {}
-  ~zv_vocoder() {
-    for (void* p : allocs) (void)ZV_BLOCKING(hipFree(p));
-  }
 
-  template <typename T> T* dalloc(size_t n) {
-    void* p = nullptr;
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T))));
-    allocs.push_back(p);
-    weight_bytes += n * sizeof(T);
-    return reinterpret_cast<T*>(p);
-  }
-  const std::vector<float>& take(const std::string& k, size_t numel) {
-    auto it = staged.find(k);
-    if (it == staged.end()) throw std::invalid_argument("missing weight: " + k);
-    if (it->second.size() != numel)
-      throw std::invalid_argument("weight " + k + ": expected " + std::to_string(numel) +
-                                  " elements, got " + std::to_string(it->second.size()));
-    return it->second;
-  }
-  float* upload(const std::vector<float>& v) {
-    float* d = dalloc<float>(v.size());
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice)));
-    return d;
-  }
-  float* upload_key(const std::string& k, size_t numel) { return upload(take(k, numel)); }
-  // host matrix w (N x K, row-major, fp32 or wider) -> padded bf16 hi/lo device weight
+  // host matrix w (N x K, row-major, computed in double) -> the padded hi/lo device weight
   Linear make_linear(const std::vector<double>& w, int N, int K, const std::vector<float>* b) {
-    Linear L;
-    L.N = N; L.K = K;
-    L.Npad = (int)round_up(N, W_NPAD);
-    L.Kpad = (int)round_up(K, W_KPAD);
-    std::vector<bf16> hi((size_t)L.Npad * L.Kpad, (bf16)0.f), lo(hi.size(), (bf16)0.f);
-    for (int n = 0; n < N; ++n)
-      for (int k = 0; k < K; ++k) {
-        const float v = (float)w[(size_t)n * K + k];
-        const bf16 hh = (bf16)v;
-        hi[(size_t)n * L.Kpad + k] = hh;
-        lo[(size_t)n * L.Kpad + k] = (bf16)(v - (float)hh);
-      }
-    L.hi = dalloc<bf16>(hi.size());
-    L.lo = dalloc<bf16>(lo.size());
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.hi, hi.data(), hi.size() * sizeof(bf16), hipMemcpyHostToDevice)));
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(L.lo, lo.data(), lo.size() * sizeof(bf16), hipMemcpyHostToDevice)));
-    if (b) L.b = upload(*b);
-    return L;
-  }
-  static std::vector<double> as_double(const std::vector<float>& v) {
-    return std::vector<double>(v.begin(), v.end());
+    const std::vector<float> wf(w.begin(), w.end());
+    return store.make_linear(wf.data(), N, K, b ? b->data() : nullptr);
   }
 
   void finalize() {
@@ -254,29 +208,29 @@ struct zv_vocoder {
                "bad n_fft / hop");
     // embed conv (C, n_mels, ke) -> [o][tap * n_mels + c]
     {
-      const auto& w = take("backbone.embed.weight", (size_t)C * nm * ke);
+      const auto& w = store.take("backbone.embed.weight", (size_t)C * nm * ke);
       std::vector<double> w2((size_t)C * nm * ke);
       for (int o = 0; o < C; ++o)
         for (int c = 0; c < nm; ++c)
           for (int t = 0; t < ke; ++t) w2[(size_t)o * nm * ke + t * nm + c] = w[((size_t)o * nm + c) * ke + t];
-      embed = make_linear(w2, C, nm * ke, &take("backbone.embed.bias", C));
+      embed = make_linear(w2, C, nm * ke, &store.take("backbone.embed.bias", C));
     }
-    norm0_w = upload_key("backbone.norm.weight", C);
-    norm0_b = upload_key("backbone.norm.bias", C);
+    norm0_w = store.upload_key("backbone.norm.weight", C);
+    norm0_b = store.upload_key("backbone.norm.bias", C);
     for (int i = 0; i < cfg.num_layers; ++i) {
       const std::string p = "backbone.convnext." + std::to_string(i) + ".";
-      dw_w.push_back(upload_key(p + "dwconv.weight", (size_t)C * 7));
-      dw_b.push_back(upload_key(p + "dwconv.bias", C));
-      ln_w.push_back(upload_key(p + "norm.weight", C));
-      ln_b.push_back(upload_key(p + "norm.bias", C));
-      pw1.push_back(make_linear(as_double(take(p + "pwconv1.weight", (size_t)I * C)), I, C,
-                                &take(p + "pwconv1.bias", I)));
-      pw2.push_back(make_linear(as_double(take(p + "pwconv2.weight", (size_t)C * I)), C, I,
-                                &take(p + "pwconv2.bias", C)));
-      gamma.push_back(upload_key(p + "gamma", C));
+      dw_w.push_back(store.upload_key(p + "dwconv.weight", (size_t)C * 7));
+      dw_b.push_back(store.upload_key(p + "dwconv.bias", C));
+      ln_w.push_back(store.upload_key(p + "norm.weight", C));
+      ln_b.push_back(store.upload_key(p + "norm.bias", C));
+      pw1.push_back(store.make_linear(store.take(p + "pwconv1.weight", (size_t)I * C).data(), I, C,
+                                      store.take(p + "pwconv1.bias", I).data()));
+      pw2.push_back(store.make_linear(store.take(p + "pwconv2.weight", (size_t)C * I).data(), C, I,
+                                      store.take(p + "pwconv2.bias", C).data()));
+      gamma.push_back(store.upload_key(p + "gamma", C));
     }
-    normf_w = upload_key("backbone.final_layer_norm.weight", C);
-    normf_b = upload_key("backbone.final_layer_norm.bias", C);
+    normf_w = store.upload_key("backbone.final_layer_norm.weight", C);
+    normf_b = store.upload_key("backbone.final_layer_norm.bias", C);
     // head Linear (n_fft+2, C): rows [mag | phase] -> groups of 32 = [mag16 | phase16],
     // bins padded to a multiple of 16 with zero rows
     const int N = cfg.n_fft;
@@ -284,8 +238,8 @@ struct zv_vocoder {
     nbins_pad = (int)round_up(nbins, 16);
     spec_ld = (int)round_up(2 * nbins_pad, W_KPAD);
     {
-      const auto& w = take("head.out.weight", (size_t)2 * nbins * C);
-      const auto& b = take("head.out.bias", (size_t)2 * nbins);
+      const auto& w = store.take("head.out.weight", (size_t)2 * nbins * C);
+      const auto& b = store.take("head.out.bias", (size_t)2 * nbins);
       std::vector<double> w2((size_t)2 * nbins_pad * C, 0.0);
       std::vector<float> b2((size_t)2 * nbins_pad, 0.f);
       for (int g = 0; g < nbins_pad / 16; ++g)
@@ -302,8 +256,8 @@ struct zv_vocoder {
     }
     // irfft * window basis: frame[n] = sum_k re_k C[n][k] + im_k S[n][k];
     // A operand columns [re (nbins_pad) | im (nbins_pad)]
-    const auto& win = take("head.istft.window", N);
-    window = upload(win);
+    const auto& win = store.take("head.istft.window", N);
+    window = store.upload(win);
     {
       std::vector<double> w2((size_t)N * 2 * nbins_pad, 0.0);
       for (int n = 0; n < N; ++n)
@@ -319,14 +273,14 @@ struct zv_vocoder {
     }
     size_t expected = 6 + 9 * (size_t)cfg.num_layers + 3;
     size_t ignored = 0;
-    for (auto& kv : staged)
+    for (auto& kv : store.staged)
       if (kv.first.rfind("feature_extractor.", 0) == 0) ++ignored;   // mel front-end buffers
-    if (staged.size() - ignored != expected)
-      throw std::invalid_argument("vocoder state dict has " + std::to_string(staged.size() - ignored) +
+    if (store.staged.size() - ignored != expected)
+      throw std::invalid_argument("vocoder state dict has " + std::to_string(store.staged.size() - ignored) +
                                   " tensors, config expects " + std::to_string(expected) +
                                   " (unexpected keys present)");
-    staged.clear();
-    ready = true;
+    store.staged.clear();
+    store.ready = true;
   }
 
   template <int SPLIT, int EPI>
