@@ -149,16 +149,19 @@ int zv_attn2_check(int kernel, int form, int B, int L, int H, int nv, const floa
                    const uint8_t* key_pad, const float* v, const float* y, int force_exact, float* out,
                    int64_t* counts);
 
-/* GEMM microbenchmark (random bf16 operands): average ms per launch of tile
- * variant `variant` (+100: one tile per block instead of the persistent grid) for
- * C(M,N) = A(M,K) W(N,K)^T with out_mode 0 = fp32 C, 1 = bf16 C, 2 = residual
- * (C += ..., fp32, plus a bf16 copy), 3 = SwooshL -> bf16. */
+/* GEMM microbenchmark (random bf16 operands): average ms per launch of the 128x128 kernel for
+ * C(M,N) = A(M,K) W(N,K)^T.  variant 0 = the general epilogue (any out_mode), 70 = the counted
+ * residual epilogue (out_mode 5 / 6), 72 = the counted plain epilogue (out_mode 7); +100: one tile
+ * per block instead of the persistent grid; any other value is rejected.  out_mode 0 = fp32 C,
+ * 1 = bf16 C, 2 = residual (C += ..., fp32, plus a bf16 copy), 3 = SwooshL -> bf16, 4 = no output,
+ * 5 = bias + residual (a residual linear's epilogue), 6 = 5 + bypass original and scale, 7 = bias +
+ * SwooshL -> bf16 (a plain linear's). */
 int zv_bench_gemm(int M, int N, int K, int variant, int iters, int out_mode, float* ms_out);
 
-/* GEMM self-check (test infrastructure): tile variant `variant` (30: 4-stage ring with a
- * 32-deep K step, 40: deferred stores, 70 / 71 / 72: the counted residual / residual + bypass /
- * plain epilogues; any other value is rejected) against the general 128x128 kernel on the same
- * random operands; mode 0 plain, 1 SwooshL, 2 residual.  Writes max |diff| and max |ref|. */
+/* GEMM self-check (test infrastructure): variant 70 / 71 / 72 = the counted residual / residual +
+ * bypass / plain epilogue of the 128x128 kernel (any other value is rejected) against its general
+ * epilogue on the same random operands; mode 0 plain, 1 SwooshL (variant 72), 2 residual (70 / 71).
+ * Writes max |diff| and max |ref|. */
 int zv_gemm_selftest(int M, int N, int K, int variant, int mode, float* maxdiff, float* maxref);
 
 /* One linear through the engine's own dispatch, on host arrays (test infrastructure: pins

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
-"""GEMM tile-variant microbenchmark on the engine's kernels (random bf16 operands).
+"""GEMM microbenchmark on the engine's 128x128 kernel (random bf16 operands).  Other tiles, rings
+and K steps were measured and retired (csrc/zv_checks.inc lists them with their records); new tile
+experiments belong in tools/lab/gemm_lab.hip.
 
 usage: bench_gemm.py [variants] [modes] [shapes]
-  variants: comma list (+100 = one tile per block instead of the persistent grid)
+  variants: comma list of 0 the general epilogue (any mode), 70 the counted residual epilogue
+            (modes 5 / 6), 72 the counted plain epilogue (mode 7); +100 = one tile per block
+            instead of the persistent grid (default: 0,100)
   modes:    comma list of 0 fp32 C, 1 bf16 C, 2 residual (fp32 C += .., bf16 copy),
-            5 residual + bias (the residual linears' epilogue; variant 70 = counted), 6 + bypass,
-            7 bias + SwooshL -> bf16 (a plain linear's; variant 72 = counted),
+            5 residual + bias (the residual linears' epilogue), 6 + bypass,
+            7 bias + SwooshL -> bf16 (a plain linear's),
             3 SwooshL -> bf16, 4 no output (epilogue store ablation)
   shapes:   "MxNxK;MxNxK" (default: the decoder's full-length shapes)
 """
@@ -21,7 +25,7 @@ MODES = {0: "f32", 1: "bf16", 2: "resid", 3: "swooshl", 4: "none", 5: "resid+bia
 lib = engine.load_library()
 shapes = [(78016, 1536, 512), (78016, 512, 1536), (78016, 1152, 512), (78016, 512, 512),
           (78016, 1024, 512), (78016, 512, 48), (4096, 4096, 4096)]
-variants = [int(v) for v in (sys.argv[1].split(",") if len(sys.argv) > 1 else range(8))]
+variants = [int(v) for v in (sys.argv[1].split(",") if len(sys.argv) > 1 else (0, 100))]
 modes = [int(v) for v in (sys.argv[2].split(",") if len(sys.argv) > 2 else (0, 1))]
 if len(sys.argv) > 3:
     shapes = [tuple(int(x) for x in s.split("x")) for s in sys.argv[3].split(";")]

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Bitwise self-check of GEMM tile variants against the 128x128 kernel (random
-bf16 operands; same MFMA order per output, so the fp32 results must agree).
+"""Bitwise self-check of the 128x128 kernel's counted epilogues against its general one (random
+bf16 operands; same arithmetic in the same order, so the results must agree).  Variants 70 / 71:
+the residual / residual + bypass epilogue (mode 2); 72: the plain one (modes 0, 1 = SwooshL).
 
 usage: gemm_selftest.py [variants] [shapes]"""
 import ctypes
@@ -12,14 +13,15 @@ import torch  # noqa: E402,F401
 from zipvoice_amd import engine  # noqa: E402
 
 lib = engine.load_library()
-variants = [int(v) for v in (sys.argv[1].split(",") if len(sys.argv) > 1 else (20, 21, 22, 23))]
-shapes = [(1000, 300, 200), (78016, 1536, 512), (4096, 512, 1920), (777, 1024, 48), (256, 256, 64)]
+variants = [int(v) for v in (sys.argv[1].split(",") if len(sys.argv) > 1 else (70, 71, 72))]
+# N a multiple of 8 (the counted epilogues move 16-B pieces of a row)
+shapes = [(1000, 296, 200), (78016, 1536, 512), (4096, 512, 1920), (777, 1024, 48), (256, 256, 64)]
 if len(sys.argv) > 2:
     shapes = [tuple(int(x) for x in s.split("x")) for s in sys.argv[2].split(";")]
 bad = 0
 for (M, N, K) in shapes:
     for v in variants:
-        for mode in ((0, 1) if v == 40 else (0, 1, 2)):
+        for mode in ((0, 1) if v == 72 else (2,)):
             d, r = ctypes.c_float(), ctypes.c_float()
             rc = lib.zv_gemm_selftest(M, N, K, v, mode, ctypes.byref(d), ctypes.byref(r))
             if rc:

@@ -161,9 +161,9 @@ int main(int argc, char** argv) {
       if (mode == 4) { g2.rowvec = rowvec; g2.rowvec_ld = 0; g2.rows_per_group = 1219; }
       auto unfused = [&]() {
         launch_gemm256<EPI_STD, 3>(g1, s, "lab", false);
-        if (mode == 1) launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 1>(g2, 1, s, "lab", true, -1);
-        else if (mode == 2) launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 2>(g2, 1, s, "lab", true, -1);
-        else launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 4>(g2, 1, s, "lab", true, -1);
+        if (mode == 1) launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, 1>(g2, 1, s, "lab", true, -1);
+        else if (mode == 2) launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, 2>(g2, 1, s, "lab", true, -1);
+        else launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, 4>(g2, 1, s, "lab", true, -1);
       };
       const FfnParams fc = fparams(C2, Ch2, Cl2, C2h2, 1, false);
       const FfnParams fp = fparams(C3, Ch3, Cl3, C2h3, 1, true);

@@ -48,7 +48,7 @@ static void run256(const GemmParams& p, hipStream_t s) {
 
 template <int EPI, int ROLE>
 static void run128(const GemmParams& p, hipStream_t s) {
-  launch_gemm<128, 128, 2, 2, 1, EPI, 2, 2, GEMM_BK, 0, 0, 0, ROLE>(p, 1, s, "lab", true, -1);
+  launch_gemm<128, 128, 2, 2, 1, EPI, 2, 2, GEMM_BK, 0, 0, ROLE>(p, 1, s, "lab", true, -1);
 }
 
 // mode -> (params, launchers)

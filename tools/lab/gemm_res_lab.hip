@@ -55,11 +55,11 @@ static GemmParams make_params(int mode, int M, int N, int K, long Kp, long Np, c
 template <int ROLE>
 static void arm(int a, const GemmParams& p, hipStream_t s) {
   switch (a) {
-    case 0: launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, ROLE>(p, 1, s, "lab", true, -1); break;
-    case 1: launch_gemm<64, 128, 2, 2, 1, EPI_STD, 2, 3, GEMM_BK, 0, 0, 0, ROLE>(p, 1, s, "lab", true, -1); break;
-    case 2: launch_gemm<128, 64, 2, 2, 1, EPI_STD, 2, 3, GEMM_BK, 0, 0, 0, ROLE>(p, 1, s, "lab", true, -1); break;
-    case 3: launch_gemm<64, 128, 2, 2, 1, EPI_STD, 3, 2, GEMM_BK, 0, 0, 0, ROLE>(p, 1, s, "lab", true, -1); break;
-    case 4: launch_gemm<64, 64, 2, 2, 1, EPI_STD, 4, 2, GEMM_BK, 0, 0, 0, ROLE>(p, 1, s, "lab", true, -1); break;
+    case 0: launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, ROLE>(p, 1, s, "lab", true, -1); break;
+    case 1: launch_gemm<64, 128, 2, 2, 1, EPI_STD, 2, 3, GEMM_BK, 0, 0, ROLE>(p, 1, s, "lab", true, -1); break;
+    case 2: launch_gemm<128, 64, 2, 2, 1, EPI_STD, 2, 3, GEMM_BK, 0, 0, ROLE>(p, 1, s, "lab", true, -1); break;
+    case 3: launch_gemm<64, 128, 2, 2, 1, EPI_STD, 3, 2, GEMM_BK, 0, 0, ROLE>(p, 1, s, "lab", true, -1); break;
+    case 4: launch_gemm<64, 64, 2, 2, 1, EPI_STD, 4, 2, GEMM_BK, 0, 0, ROLE>(p, 1, s, "lab", true, -1); break;
   }
 }
 static void run(int mode, int a, const GemmParams& p, hipStream_t s) {

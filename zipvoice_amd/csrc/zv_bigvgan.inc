@@ -380,18 +380,18 @@ struct zv_bigvgan {
       // channel count (Cp = round_up(C, 32): 64-deep steps when Cp % 64 == 0)
       if (conv_c % 64 == 0) {
         if (W.N <= 48)
-          launch_gemm<256, 48, 4, 1, SPLIT, EPI_STD, 2, 2, 64, 0, 0, 1>(p, 1, s, tag, true, -1);
+          launch_gemm<256, 48, 4, 1, SPLIT, EPI_STD, 2, 2, 64, 0, 1>(p, 1, s, tag, true, -1);
         else if (W.N <= 64)
-          launch_gemm<64, 64, 2, 2, SPLIT, EPI_STD, 2, 2, 64, 0, 0, 1>(p, 1, s, tag, true, -1);
+          launch_gemm<64, 64, 2, 2, SPLIT, EPI_STD, 2, 2, 64, 0, 1>(p, 1, s, tag, true, -1);
         else
-          launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, 64, 0, 0, 1>(p, 1, s, tag);
+          launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, 64, 0, 1>(p, 1, s, tag);
       } else {
         if (W.N <= 32)
-          launch_gemm<256, 32, 4, 1, SPLIT, EPI_STD, 2, 2, 32, 0, 0, 1>(p, 1, s, tag, true, -1);
+          launch_gemm<256, 32, 4, 1, SPLIT, EPI_STD, 2, 2, 32, 0, 1>(p, 1, s, tag, true, -1);
         else if (W.N <= 96)
-          launch_gemm<128, 96, 2, 2, SPLIT, EPI_STD, 2, 2, 32, 0, 0, 1>(p, 1, s, tag, true, -1);
+          launch_gemm<128, 96, 2, 2, SPLIT, EPI_STD, 2, 2, 32, 0, 1>(p, 1, s, tag, true, -1);
         else
-          launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, 32, 0, 0, 1>(p, 1, s, tag);
+          launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, 32, 0, 1>(p, 1, s, tag);
       }
     } else {
       launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD>(p, 1, s, tag);

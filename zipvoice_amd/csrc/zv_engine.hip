@@ -1462,32 +1462,7 @@ static auto api_create(F make) -> decltype(make()) {
   }
 }
 
-// GEMM microbenchmark on random operands: C(M,N) fp32 = A(M,K) . W(N,K)^T
-static __global__ void zv_fill_rand_bf16(bf16* p, long n, unsigned seed) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    unsigned x = (unsigned)i * 2654435761u ^ seed;
-    x ^= x >> 13; x *= 0x5bd1e995u; x ^= x >> 15;
-    p[i] = (bf16)(((float)(x & 0xffff) / 65535.0f) * 2.0f - 1.0f);
-  }
-}
-
-template <int BM, int BN, int WGM, int WGN, int STAGES, int BK = GEMM_BK, int DEFER = 0, int ROLE = 0>
-static float bench_variant(GemmParams p, int iters, bool persistent, hipStream_t s) {
-  hipEvent_t e0, e1;
-  ZV_CHECK(ZV_BLOCKING(hipEventCreate(&e0))); ZV_CHECK(ZV_BLOCKING(hipEventCreate(&e1)));
-  launch_gemm<BM, BN, WGM, WGN, 1, EPI_STD, STAGES, 2, BK, DEFER, 0, 0, ROLE>(p, 1, s, "bench", persistent);
-  ZV_CHECK(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i)
-    launch_gemm<BM, BN, WGM, WGN, 1, EPI_STD, STAGES, 2, BK, DEFER, 0, 0, ROLE>(p, 1, s, "bench", persistent);
-  ZV_CHECK(hipEventRecord(e1, s));
-  ZV_CHECK(ZV_BLOCKING(hipEventSynchronize(e1)));
-  float ms = 0.f;
-  ZV_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  ZV_CHECK(ZV_BLOCKING(hipEventDestroy(e0))); ZV_CHECK(ZV_BLOCKING(hipEventDestroy(e1)));
-  return ms / iters;
-}
-
-
+#include "zv_checks.inc"
 
 extern "C" {
 
@@ -1529,31 +1504,21 @@ int zv_reserve(zv_handle h, int max_batch, int max_frames) {
   const int Fx = h->stereo() ? 2 * h->cfg.feat_dim : h->cfg.feat_dim;
   const size_t nx = (size_t)max_batch * max_frames * Fx;
   const size_t nt = (size_t)max_batch * max_frames * h->cfg.feat_dim;
-  float *x = nullptr, *tc = nullptr, *v = nullptr;
-  uint8_t* pad = nullptr;
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&x, nx * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&tc, nt * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&v, nx * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&pad, (size_t)max_batch * max_frames)));
-  ZV_CHECK(ZV_BLOCKING(hipMemset(x, 0, nx * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMemset(tc, 0, nt * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMemset(pad, 0, (size_t)max_batch * max_frames)));
-  auto release = [&]() { (void)ZV_BLOCKING(hipFree(x)); (void)ZV_BLOCKING(hipFree(tc)); (void)ZV_BLOCKING(hipFree(v)); (void)ZV_BLOCKING(hipFree(pad)); };
+  // zero-filled inputs and the output, freed on return (as every fresh buffer, they move the
+  // workspace generation: reserve before the solves whose graphs are to stay)
+  DBuf bx, btc, bv, bpad;
+  const float *x = bx.get<float>(nx), *tc = btc.get<float>(nt);
+  float* v = bv.get<float>(nx);
+  const uint8_t* pad = bpad.get<uint8_t>((size_t)max_batch * max_frames);
   // the graph path's staging copies of the inputs, too
   (void)h->gx.get<float>(nx);
   (void)h->gtc.get<float>(nt);
   (void)h->gsc.get<float>(nx);
   (void)h->gpad.get<uint8_t>((size_t)max_batch * max_frames);
   (void)h->ggrows.get<float>((size_t)max_batch);
-  try {
-    h->velocity(0.25f, 1.0f, nullptr, false, x, tc, x, pad, max_batch, max_frames, v, false,
-                0.f, nullptr);
-    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
-  } catch (...) {
-    release();
-    throw;
-  }
-  release();
+  h->velocity(0.25f, 1.0f, nullptr, false, x, tc, x, pad, max_batch, max_frames, v, false,
+              0.f, nullptr);
+  ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
   ZV_API_END
 }
 
@@ -1603,629 +1568,6 @@ int zv_profile_report(char* buf, int buflen) {
   js += "}";
   ZV_REQUIRE((int)js.size() < buflen, "report buffer too small");
   memcpy(buf, js.c_str(), js.size() + 1);
-  ZV_API_END
-}
-
-int zv_bench_gemm(int M, int N, int K, int variant, int iters, int out_mode, float* ms_out) {
-  ZV_API_BEGIN
-  hipStream_t s = nullptr;
-  const long Kp = round_up(K, 64), Np = round_up(N, 256);
-  bf16 *A, *W, *Ch = nullptr;
-  float* C = nullptr;
-  const bool persistent = variant < 100;
-  variant %= 100;
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&A, (size_t)M * Kp * 2)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&W, (size_t)Np * Kp * 2)));
-  if (out_mode != 0) ZV_CHECK(ZV_BLOCKING(hipMalloc(&Ch, (size_t)M * N * 2)));
-  if (out_mode == 0 || out_mode == 2) {
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&C, (size_t)M * N * 4)));
-    ZV_CHECK(hipMemsetAsync(C, 0, (size_t)M * N * 4, s));
-  }
-  hipLaunchKernelGGL(zv_fill_rand_bf16, dim3(4096), dim3(256), 0, s, A, (long)M * Kp, 1u);
-  hipLaunchKernelGGL(zv_fill_rand_bf16, dim3(4096), dim3(256), 0, s, W, (long)Np * Kp, 2u);
-  GemmParams p{};
-  p.M = M; p.N = N; p.K = K; p.nz2 = 1; p.Brows = (int)Np;
-  p.Ah = A; p.lda = Kp; p.Bh = W; p.ldb = Kp;
-  p.C = C; p.ldc = N; p.Ch = Ch; p.ldch = N; p.rows_per_group = 1; p.rpb = 1;
-  if (out_mode == 2) p.resid = C;
-  if (out_mode == 3) p.act = 1;
-  if (out_mode == 4) { p.C = nullptr; p.Ch = nullptr; }
-  float* extra = nullptr;          // modes 5 / 6: a residual linear's epilogue operands
-  if (out_mode == 7) {             // a plain linear's: bias + SwooshL -> bf16 copy
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&extra, (size_t)N * 4)));
-    ZV_CHECK(hipMemsetAsync(extra, 0, (size_t)N * 4, s));
-    p.C = nullptr; p.bias = extra; p.act = 1;
-  }
-  if (out_mode == 5 || out_mode == 6) {
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&C, (size_t)M * N * 4)));
-    ZV_CHECK(hipMemsetAsync(C, 0, (size_t)M * N * 4, s));
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&extra, (size_t)(2 * N + (out_mode == 6 ? (size_t)M * N : 0)) * 4)));
-    ZV_CHECK(hipMemsetAsync(extra, 0, (size_t)(2 * N + (out_mode == 6 ? (size_t)M * N : 0)) * 4, s));
-    p.C = C; p.resid = C; p.bias = extra;
-    if (out_mode == 6) { p.byp = extra + N; p.orig = extra + 2 * N; }
-  }
-  float ms = -1.f;
-  switch (variant) {
-    case 0: ms = bench_variant<128, 128, 2, 2, 2>(p, iters, persistent, s); break;
-    case 1: ms = bench_variant<128, 128, 2, 2, 3>(p, iters, persistent, s); break;
-    case 2: ms = bench_variant<256, 128, 4, 2, 2>(p, iters, persistent, s); break;
-    case 3: ms = bench_variant<256, 128, 4, 2, 3>(p, iters, persistent, s); break;
-    case 4: ms = bench_variant<128, 64, 2, 2, 3>(p, iters, persistent, s); break;
-    case 5: ms = bench_variant<128, 256, 2, 4, 2>(p, iters, persistent, s); break;
-    case 6: ms = bench_variant<128, 128, 2, 2, 4>(p, iters, persistent, s); break;
-    case 7: ms = bench_variant<256, 128, 2, 2, 2>(p, iters, persistent, s); break;
-    case 8: ms = bench_variant<256, 256, 2, 4, 2>(p, iters, persistent, s); break;
-    case 9: ms = bench_variant<256, 128, 2, 4, 2>(p, iters, persistent, s); break;
-    case 10: ms = bench_variant<128, 256, 1, 4, 2>(p, iters, persistent, s); break;
-    case 30: ms = bench_variant<128, 128, 2, 2, 4, 32>(p, iters, persistent, s); break;
-    case 40: ms = bench_variant<128, 128, 2, 2, 2, GEMM_BK, 8>(p, iters, persistent, s); break;
-    case 31: ms = bench_variant<128, 128, 2, 2, 3, 32>(p, iters, persistent, s); break;
-    case 32: ms = bench_variant<256, 128, 2, 2, 2, 32>(p, iters, persistent, s); break;
-    case 33: ms = bench_variant<256, 128, 2, 2, 3, 32>(p, iters, persistent, s); break;
-    case 72: {                     // counted plain epilogue (out mode 7)
-      if (out_mode != 7) throw std::invalid_argument("variant 72: mode 7 only");
-      ms = bench_variant<128, 128, 2, 2, 2, GEMM_BK, 0, 3>(p, iters, persistent, s);
-      break;
-    }
-    case 70: {                     // counted residual epilogue (out modes 5 / 6)
-      if (out_mode != 5 && out_mode != 6) throw std::invalid_argument("variant 70: modes 5 / 6 only");
-      ms = out_mode == 5 ? bench_variant<128, 128, 2, 2, 2, GEMM_BK, 0, 1>(p, iters, persistent, s)
-                         : bench_variant<128, 128, 2, 2, 2, GEMM_BK, 0, 2>(p, iters, persistent, s);
-      break;
-    }
-    default: throw std::invalid_argument("unknown variant");
-  }
-  *ms_out = ms;
-  ZV_CHECK(ZV_BLOCKING(hipFree(A))); ZV_CHECK(ZV_BLOCKING(hipFree(W)));
-  if (extra) ZV_CHECK(ZV_BLOCKING(hipFree(extra)));
-  if (C) ZV_CHECK(ZV_BLOCKING(hipFree(C)));
-  if (Ch) ZV_CHECK(ZV_BLOCKING(hipFree(Ch)));
-  ZV_API_END
-}
-
-// GEMM self-check: variant (bench ids) against the 128x128 kernel on the same
-// random operands, fp32 C (+ optional residual / SwooshL epilogue).  Writes the
-// max |diff| and the max |ref|.
-static __global__ void zv_zero_kpad_kernel(bf16* p, long rows, int ld, int K) {
-  const long n = rows * (long)(ld - K);
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    p[(i / (ld - K)) * ld + K + i % (ld - K)] = (bf16)0.f;
-}
-static __global__ void zv_bf16_to_f32_kernel(const bf16* a, float* b, long n) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    b[i] = (float)a[i];
-}
-static __global__ void zv_maxdiff_kernel(const float* a, const float* b, long n, float* out) {
-  float d = 0.f, r = 0.f;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    d = fmaxf(d, fabsf(a[i] - b[i]));
-    r = fmaxf(r, fabsf(b[i]));
-  }
-  atomicMax(reinterpret_cast<int*>(out), __float_as_int(d));
-  atomicMax(reinterpret_cast<int*>(out + 1), __float_as_int(r));
-}
-
-int zv_attn_plan(int split, int sa_plo, int tpm, int L, int nv_na, int64_t* lds_sa, int64_t* lds_na,
-                 int64_t* lds_stats, int* fits) {
-  ZV_API_BEGIN
-  ZV_REQUIRE((split == 1 || split == 3) && L > 0 && nv_na > 0 && sa_plo >= -1 && sa_plo <= 1 &&
-                 tpm >= 0 && tpm <= 3 && (split == 1 || (sa_plo < 0 && tpm == 0)) && lds_sa && lds_na &&
-                 lds_stats && fits,
-             "bad arguments");
-  if (tpm == 3) {   // second-generation set (zv_flash2.inc): no statistics kernel
-    *lds_sa = (int64_t)(sa3_qpw(L) ? sa3_plan_lds(L) : sa2_qpw(L) == 3 ? sa2_lds_bytes<3>(L) : sa2_lds_bytes<2>(L));
-    *lds_na = (int64_t)(nv_na <= 128 ? na2_lds_bytes<1, 8>(L) : nv_na <= 256 ? na2_lds_bytes<2, 8>(L) : na2_lds_bytes<3, 8>(L));
-    *lds_stats = 0;
-    *fits = fused_attn2_fits(L, nv_na);
-    return 0;
-  }
-  *lds_sa = (int64_t)(sa_plo < 0 ? sa_lds_bytes(L) : (sa_plo ? sa_tp_lds_bytes<1>(L) : sa_tp_lds_bytes<0>(L)));
-  *lds_na = (int64_t)(split == 1 ? na_lds_bytes_for<1>(L, nv_na, tpm) : na_lds_bytes_for<3>(L, nv_na, tpm));
-  *lds_stats = (int64_t)pos_mask_bytes(L, 64, true);
-  *fits = split == 1 ? fused_attn_fits<1>(L, nv_na, sa_plo, tpm) : fused_attn_fits<3>(L, nv_na, sa_plo, tpm);
-  ZV_API_END
-}
-
-// Second-generation attention consumers on the device, alone (test infrastructure; host pointers).
-// Inputs are rounded to the library's 16-bit operand format here (bf16, or fp16 in
-// libzipvoice_hip_f16.so, whose kernels add the per-query offsets), as the engine's producers round
-// them: qkp (B, L, 2 H 32 + 4 H) fp32 = [q | k | p] per row in base-2 units (the engine folds
-// log2(e) into the k / p weights), P (2L - 1, 4 H) the positional projection (also base 2), key_pad
-// (B, L) or null.  kernel 0 SelfAttention: v (B, L, H * nv), nv <= 12, out (B, L, H * nv);
-// kernel 1 NonlinAttention (head 0): v (B, L, nv), y (B, L, nv), out (B, L, nv) = y * (W0 . v).
-// form 0: the engine's choice for L; SelfAttention 1 / 2: sa2 with 2 / 3 query tiles per wave,
-// 3 / 4 / 5: sa3 with 2 / 3 / 4; NonlinAttention 1 / 2: 4 / 8 query tiles per block.
-// force_exact: every wave / block on its exact path.  counts (or null): zv_attn_fallbacks's three.
-int zv_attn2_check(int kernel, int form, int B, int L, int H, int nv, const float* qkp, const float* P,
-                   const uint8_t* key_pad, const float* v, const float* y, int force_exact, float* out,
-                   int64_t* counts) {
-  ZV_API_BEGIN
-  ZV_REQUIRE((kernel == 0 || kernel == 1) && B > 0 && L > 0 && H > 0 && qkp && P && v && out &&
-                 (kernel == 0 ? (nv > 0 && nv <= 12) : (nv > 0 && nv <= 384 && y)),
-             "zv_attn2_check: bad arguments");
-  const long ldq = 2L * H * ATT_QD + H * ATT_PD, M = (long)B * L, Lpad = round_up(L, 64);
-  const long vrows = kernel == 0 ? 16L * H : nv;   // V^T rows per utterance
-  std::vector<bf16> hq((size_t)M * ldq), hv((size_t)B * vrows * Lpad, (bf16)0.f);
-  for (size_t i = 0; i < hq.size(); ++i) hq[i] = (bf16)qkp[i];
-  for (int b = 0; b < B; ++b)
-    for (long r = 0; r < vrows; ++r) {
-      const int h = kernel == 0 ? (int)(r / 16) : 0, d = kernel == 0 ? (int)(r % 16) : (int)r;
-      for (int j = 0; j < L; ++j) {
-        float x = 0.f;
-        if (kernel == 1) x = v[((long)b * L + j) * nv + d];
-        else if (d < nv) x = v[((long)b * L + j) * H * nv + (long)h * nv + d];
-        else if (d == 12) x = 1.f;                       // the ones row (softmax denominator)
-        hv[((size_t)b * vrows + r) * Lpad + j] = (bf16)x;
-      }
-    }
-  std::vector<bf16> hy;
-  if (kernel == 1) {
-    hy.resize((size_t)M * nv);
-    for (size_t i = 0; i < hy.size(); ++i) hy[i] = (bf16)y[i];
-  }
-  const long ocols = kernel == 0 ? (long)H * nv : nv, ldo = round_up(ocols, 8);
-  bf16 *dq = nullptr, *dv = nullptr, *dy = nullptr, *dout = nullptr;
-  float* dP = nullptr;
-  uint8_t* dpad = nullptr;
-  unsigned* dcnt = nullptr;
-  auto release = [&]() {
-    for (void* ptr : {(void*)dq, (void*)dv, (void*)dy, (void*)dout, (void*)dP, (void*)dpad, (void*)dcnt})
-      if (ptr) (void)ZV_BLOCKING(hipFree(ptr));
-  };
-  try {
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&dq, hq.size() * 2)));
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&dv, hv.size() * 2)));
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&dout, (size_t)M * ldo * 2)));
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&dP, (size_t)(2 * L - 1) * H * ATT_PD * 4)));
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&dcnt, 16)));
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(dq, hq.data(), hq.size() * 2, hipMemcpyHostToDevice)));
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(dv, hv.data(), hv.size() * 2, hipMemcpyHostToDevice)));
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(dP, P, (size_t)(2 * L - 1) * H * ATT_PD * 4, hipMemcpyHostToDevice)));
-    ZV_CHECK(ZV_BLOCKING(hipMemset(dout, 0, (size_t)M * ldo * 2)));
-    ZV_CHECK(ZV_BLOCKING(hipMemset(dcnt, 0, 16)));
-    if (key_pad) {
-      ZV_CHECK(ZV_BLOCKING(hipMalloc(&dpad, (size_t)M)));
-      ZV_CHECK(ZV_BLOCKING(hipMemcpy(dpad, key_pad, (size_t)M, hipMemcpyHostToDevice)));
-    }
-    if (kernel == 1) {
-      ZV_CHECK(ZV_BLOCKING(hipMalloc(&dy, hy.size() * 2)));
-      ZV_CHECK(ZV_BLOCKING(hipMemcpy(dy, hy.data(), hy.size() * 2, hipMemcpyHostToDevice)));
-    }
-    FlashParams f{};
-    f.qh = dq; f.ldq = ldq; f.P = dP; f.key_pad = dpad; f.B = B; f.L = L; f.H = H;
-    f.vh = dv; f.ldv = Lpad; f.sv_b = vrows * Lpad; f.nv = nv;
-    f.oh = dout; f.ldo = ldo;
-    f.force_exact = force_exact; f.fallback = dcnt;
-    hipStream_t s = nullptr;
-    if (kernel == 0) {
-      f.vrows_per_head = 16; f.ocol_per_head = nv;
-      const int fm = form ? form : (sa3_qpw(L) == 4 ? 5 : sa3_qpw(L) == 3 ? 4 : sa3_qpw(L) == 2 ? 3 : sa2_qpw(L) == 3 ? 2 : 1);
-      switch (fm) {
-        case 1: launch_attn_sa2<2>(f, s); break;
-        case 2: launch_attn_sa2<3, 1>(f, s); break;
-        case 3: launch_attn_sa3<2>(f, s); break;
-        case 4: launch_attn_sa3<3>(f, s); break;
-        case 5: launch_attn_sa3<4>(f, s); break;
-        default: throw std::invalid_argument("zv_attn2_check: SelfAttention form 0..5");
-      }
-    } else {
-      f.vrows_per_head = 0; f.ocol_per_head = 0;
-      f.mulh = dy; f.ldmul = nv;
-      const int fm = form ? form : (na2_qtiles(L) == 4 ? 1 : 2);
-      ZV_REQUIRE(fm == 1 || fm == 2, "zv_attn2_check: NonlinAttention form 0..2");
-      if (nv <= 128) { if (fm == 1) launch_attn_na2<1, 4>(f, s); else launch_attn_na2<1>(f, s); }
-      else if (nv <= 256) { if (fm == 1) launch_attn_na2<2, 4>(f, s); else launch_attn_na2<2>(f, s); }
-      else if (fm == 1) launch_attn_na2<3, 4>(f, s);
-      else launch_attn_na2<3>(f, s);
-    }
-    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
-    std::vector<bf16> ho((size_t)M * ldo);
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(ho.data(), dout, ho.size() * 2, hipMemcpyDeviceToHost)));
-    for (long m = 0; m < M; ++m)
-      for (long c = 0; c < ocols; ++c) out[m * ocols + c] = (float)ho[m * ldo + c];
-    if (counts) {
-      unsigned c[4];
-      ZV_CHECK(ZV_BLOCKING(hipMemcpy(c, dcnt, 16, hipMemcpyDeviceToHost)));
-      for (int i = 0; i < 3; ++i) counts[i] = c[i];
-    }
-  } catch (...) {
-    release();
-    throw;
-  }
-  release();
-  ZV_API_END
-}
-
-int zv_mx8_quantize(const float* x, int rows, int K, uint8_t* q, uint8_t* s) {
-  ZV_API_BEGIN
-  ZV_REQUIRE(x && q && s && rows >= 0 && K > 0, "bad arguments");
-  mx8_quantize_host(x, K, rows, K, q, round_up(K, MX8_KSTEP), s);
-  ZV_API_END
-}
-
-int zv_mx8_gemm_check(int M, int N, int K, const float* A, const float* W, float* C, uint8_t* Aq,
-                      uint8_t* As) {
-  ZV_API_BEGIN
-  ZV_REQUIRE(A && W && C && M > 0 && N > 0 && K > 0 && K % MX8_KSTEP == 0 && N % 8 == 0,
-             "zv_mx8_gemm_check: K a multiple of 128, N of 8");
-  hipStream_t s = nullptr;
-  const long Np = round_up(N, 128);
-  std::vector<bf16> ah((size_t)M * K);
-  for (size_t i = 0; i < ah.size(); ++i) ah[i] = (bf16)A[i];
-  std::vector<float> wp((size_t)Np * K, 0.f);
-  memcpy(wp.data(), W, (size_t)N * K * 4);
-  std::vector<uint8_t> wq((size_t)Np * K), ws((size_t)Np * K / MX8_BLOCK);
-  mx8_quantize_host(wp.data(), K, (int)Np, K, wq.data(), K, ws.data());
-  bf16* dA; uint8_t *dAq, *dAs, *dWq, *dWs; float *dC, *dB;
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&dA, ah.size() * 2)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&dAq, (size_t)M * K)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&dAs, (size_t)M * K / MX8_BLOCK)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&dWq, wq.size())));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&dWs, ws.size())));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&dC, (size_t)M * N * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&dB, (size_t)N * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMemcpy(dA, ah.data(), ah.size() * 2, hipMemcpyHostToDevice)));
-  ZV_CHECK(ZV_BLOCKING(hipMemcpy(dWq, wq.data(), wq.size(), hipMemcpyHostToDevice)));
-  ZV_CHECK(ZV_BLOCKING(hipMemcpy(dWs, ws.data(), ws.size(), hipMemcpyHostToDevice)));
-  ZV_CHECK(ZV_BLOCKING(hipMemset(dC, 0, (size_t)M * N * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMemset(dB, 0, (size_t)N * 4)));
-  hipLaunchKernelGGL(zv_mx8_pack_kernel, grid1d((long)M * (K / 8)), dim3(256), 0, s, dA, (long)K, (long)M,
-                     K, dAq, (long)K, dAs);
-  ZV_LAUNCH_CHECK();
-  GemmParams p{};
-  p.M = M; p.N = N; p.K = K; p.nz2 = 1; p.Brows = (int)Np;
-  p.Ah = reinterpret_cast<const bf16*>(dAq); p.lda = K; p.As = dAs; p.ldas = K / MX8_BLOCK;
-  p.Bh = reinterpret_cast<const bf16*>(dWq); p.ldb = K; p.Bs = dWs; p.ldbs = K / MX8_BLOCK;
-  p.bias = dB; p.C = dC; p.ldc = N; p.resid = dC; p.rows_per_group = 1; p.rpb = 1;
-  launch_gemm<128, 128, 2, 2, 8, EPI_STD, 2, 2, MX8_KSTEP, 0, 0, 0, 1>(p, 1, s, "mx8_check", true, -1);
-  ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
-  ZV_CHECK(ZV_BLOCKING(hipMemcpy(C, dC, (size_t)M * N * 4, hipMemcpyDeviceToHost)));
-  if (Aq) ZV_CHECK(ZV_BLOCKING(hipMemcpy(Aq, dAq, (size_t)M * K, hipMemcpyDeviceToHost)));
-  if (As) ZV_CHECK(ZV_BLOCKING(hipMemcpy(As, dAs, (size_t)M * K / MX8_BLOCK, hipMemcpyDeviceToHost)));
-  for (void* ptr : {(void*)dA, (void*)dAq, (void*)dAs, (void*)dWq, (void*)dWs, (void*)dC, (void*)dB})
-    ZV_CHECK(ZV_BLOCKING(hipFree(ptr)));
-  ZV_API_END
-}
-
-int zv_gemm_selftest(int M, int N, int K, int variant, int mode, float* maxdiff, float* maxref) {
-  ZV_API_BEGIN
-  hipStream_t s = nullptr;
-  const long Kp = round_up(K, 64), Np = round_up(N, 256);
-  bf16 *A, *W;
-  float *C0, *C1, *R, *res;
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&A, (size_t)M * Kp * 2)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&W, (size_t)Np * Kp * 2)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&C0, (size_t)M * N * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&C1, (size_t)M * N * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&R, (size_t)M * N * 4)));
-  ZV_CHECK(ZV_BLOCKING(hipMalloc(&res, 8)));
-  hipLaunchKernelGGL(zv_fill_rand_bf16, dim3(4096), dim3(256), 0, s, A, (long)M * Kp, 1u);
-  hipLaunchKernelGGL(zv_fill_rand_bf16, dim3(4096), dim3(256), 0, s, W, (long)Np * Kp, 2u);
-  hipLaunchKernelGGL(zv_fill_rand_bf16, dim3(4096), dim3(256), 0, s, reinterpret_cast<bf16*>(R),
-                     (long)M * N * 2, 3u);   // finite garbage as the residual
-  if (Kp > K) {   // the engine's operands are zero beyond K (padded to the K step)
-    hipLaunchKernelGGL(zv_zero_kpad_kernel, dim3(1024), dim3(256), 0, s, A, (long)M, (int)Kp, K);
-    hipLaunchKernelGGL(zv_zero_kpad_kernel, dim3(1024), dim3(256), 0, s, W, (long)Np, (int)Kp, K);
-  }
-  GemmParams p{};
-  p.M = M; p.N = N; p.K = K; p.nz2 = 1; p.Brows = (int)Np;
-  p.Ah = A; p.lda = Kp; p.Bh = W; p.ldb = Kp; p.ldc = N; p.rows_per_group = 1; p.rpb = 1;
-  if (mode == 1) p.act = 1;
-  float* outs[2] = {C0, C1};
-  float* extra = nullptr;          // dual-group variants: bias, bypass original / scale
-  if (variant == 72) {             // counted plain epilogue: bias (+ SwooshL) -> bf16
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&extra, (size_t)N * 4)));
-    hipLaunchKernelGGL(zv_fill_rand_bf16, dim3(64), dim3(256), 0, s, reinterpret_cast<bf16*>(extra),
-                       (long)N * 2, 5u);
-    p.bias = extra;
-  }
-  if (variant == 60 || variant == 61 || variant == 70 || variant == 71) {
-    if (mode != 2) throw std::invalid_argument("selftest: residual-only variant");
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&extra, (size_t)(2 * N + (size_t)M * N) * 4)));
-    hipLaunchKernelGGL(zv_fill_rand_bf16, dim3(4096), dim3(256), 0, s, reinterpret_cast<bf16*>(extra),
-                       (long)(2 * N + (long)M * N) * 2, 4u);
-    p.bias = extra;
-    if (variant == 61 || variant == 71) { p.byp = extra + N; p.orig = extra + 2 * N; }
-  }
-  // the deferred-store variant writes bf16 only: both runs then write bf16 (into
-  // the two halves of R) and are widened into C0 / C1 for the comparison
-  const bool bf16_out = variant == 40 || variant == 72;
-  if (bf16_out && mode == 2) throw std::invalid_argument("selftest: variant 40 has no residual form");
-  for (int k = 0; k < 2; ++k) {
-    p.C = outs[k];
-    if (bf16_out) {
-      p.C = nullptr;
-      p.Ch = reinterpret_cast<bf16*>(R) + (size_t)k * M * N;   // R (2 x M x N bf16) is free here
-      p.ldch = N;
-    }
-    if (mode == 2) {
-      ZV_CHECK(hipMemcpyAsync(outs[k], R, (size_t)M * N * 4, hipMemcpyDeviceToDevice, s));
-      p.resid = outs[k];
-    }
-    if (k == 0) launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2>(p, 1, s, "ref", true, 0);
-    else switch (variant) {
-      case 30: launch_gemm<128, 128, 2, 2, 1, EPI_STD, 4, 2, 32>(p, 1, s, "t", true, 0); break;
-      case 40: launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 8>(p, 1, s, "t", true, 0); break;
-      // the counted residual epilogue (ROLE 1 / 2) against the general one
-      case 70: launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 1>(p, 1, s, "t", true, -1); break;
-      case 71: launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 2>(p, 1, s, "t", true, -1); break;
-      case 72: launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 0, 0, 3>(p, 1, s, "t", true, -1); break;
-      default: throw std::invalid_argument("selftest: unknown variant");
-    }
-  }
-  if (bf16_out)
-    for (int k = 0; k < 2; ++k)
-      hipLaunchKernelGGL(zv_bf16_to_f32_kernel, dim3(1024), dim3(256), 0, s,
-                         reinterpret_cast<bf16*>(R) + (size_t)k * M * N, outs[k], (long)M * N);
-  ZV_CHECK(hipMemsetAsync(res, 0, 8, s));
-  hipLaunchKernelGGL(zv_maxdiff_kernel, dim3(1024), dim3(256), 0, s, C1, C0, (long)M * N, res);
-  float h[2];
-  ZV_CHECK(ZV_BLOCKING(hipMemcpy(h, res, 8, hipMemcpyDeviceToHost)));
-  *maxdiff = h[0]; *maxref = h[1];
-  for (void* q : {(void*)A, (void*)W, (void*)C0, (void*)C1, (void*)R, (void*)res}) ZV_CHECK(ZV_BLOCKING(hipFree(q)));
-  if (extra) ZV_CHECK(ZV_BLOCKING(hipFree(extra)));
-  ZV_API_END
-}
-
-// ---------------------------------------------------------------------------
-// zv_linear_check / zv_ffn_check (test infrastructure): one linear through the engine's dispatch,
-// and the fused FeedForward alone, on host arrays with canary-guarded outputs
-// ---------------------------------------------------------------------------
-extern "C++" {
-namespace {
-struct ChkDev {   // the device buffers of one check call, freed when it returns or throws
-  std::vector<void*> ptrs;
-  void* raw(size_t bytes) {
-    void* p = nullptr;
-    ZV_CHECK(ZV_BLOCKING(hipMalloc(&p, bytes + 256)));
-    ptrs.push_back(p);
-    return p;
-  }
-  template <typename T> T* up(const T* host, size_t n) {
-    T* d = reinterpret_cast<T*>(raw(n * sizeof(T)));
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice)));
-    return d;
-  }
-  template <typename T> void down(T* host, const T* dev, size_t n) {
-    ZV_CHECK(ZV_BLOCKING(hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost)));
-  }
-  ~ChkDev() { for (void* p : ptrs) (void)ZV_BLOCKING(hipFree(p)); }
-};
-// an activation as the engine's producers write it: (rows, ld) 16-bit hi (+ lo), zero beyond cols
-void chk_act(const float* x, long rows, int cols, long ld, bool lo, std::vector<bf16>& h, std::vector<bf16>& l) {
-  h.assign((size_t)rows * ld, (bf16)0.f);
-  if (lo) l.assign((size_t)rows * ld, (bf16)0.f);
-  for (long r = 0; r < rows; ++r)
-    for (int c = 0; c < cols; ++c) {
-      const float v = x[r * cols + c];
-      const bf16 hv = (bf16)v;
-      h[(size_t)r * ld + c] = hv;
-      if (lo) l[(size_t)r * ld + c] = (bf16)(v - (float)hv);
-    }
-}
-// a (rows, cols) fp32 host array re-laid with row stride ld (zero padding)
-std::vector<float> chk_pad(const float* x, long rows, int cols, long ld) {
-  std::vector<float> v((size_t)rows * ld, 0.f);
-  for (long r = 0; r < rows; ++r) memcpy(&v[(size_t)r * ld], x + r * cols, (size_t)cols * sizeof(float));
-  return v;
-}
-void chk_record(int* launch, int* num_cus) {
-  const ZvLaunchRec& r = g_zv_last_launch;
-  const int v[8] = {r.BM, r.BN, r.SPLIT, r.EPI, r.ROLE, r.k256, r.grid, r.aux};
-  memcpy(launch, v, sizeof(v));
-  *num_cus = zv_num_cus();
-}
-}  // namespace
-}  // extern "C++"
-
-int zv_linear_check(zv_linear_check_args* a) {
-  ZV_API_BEGIN
-  ZV_REQUIRE(a && a->M > 0 && a->N > 0 && a->K > 0 && a->A && a->W && a->bias && a->guard >= 0 &&
-                 (a->split == 1 || a->split == 2 || a->split == 3) && a->form >= ZV_LIN_PLAIN &&
-                 a->form <= ZV_LIN_GLU,
-             "zv_linear_check: bad arguments");
-  const int M = a->M, N = a->N, K = a->K, form = a->form, G = a->guard;
-  const bool split3 = a->split == 3;
-  const bool fused = form >= ZV_LIN_TRANS;
-  const bool resid = form >= ZV_LIN_RESID && form <= ZV_LIN_RESID_RV_COPY;
-  const bool rv = form == ZV_LIN_RESID_RV || form == ZV_LIN_RESID_RV_COPY;
-  const bool wantC = form == ZV_LIN_PLAIN_F32 || (resid && form != ZV_LIN_RESID_RV_COPY);
-  const bool wantT = form == ZV_LIN_TRANS || form == ZV_LIN_NA;
-  ZV_REQUIRE(a->split != 2 || (form == ZV_LIN_PLAIN && !a->act) || form == ZV_LIN_TRANS,
-             "zv_linear_check: split 2 is the plain form without activation, or TRANS");
-  ZV_REQUIRE(wantC == (a->C != nullptr) && (!a->C || a->ldc >= N) && (!resid || a->resid) &&
-                 (form != ZV_LIN_RESID_BYP || (a->orig && a->byp)) &&
-                 (!rv || (a->rowvec && a->rows_per_group > 0)) && (form != ZV_LIN_RESID_RV_COPY || a->ldc >= N),
-             "zv_linear_check: the form's fp32 operands");
-  const int wch = form == ZV_LIN_NA ? N / 3 : form == ZV_LIN_GLU ? N / 2 : N;   // width of Ch
-  const bool needCh = form == ZV_LIN_PLAIN || form == ZV_LIN_RESID_RV_COPY || form == ZV_LIN_NA || form == ZV_LIN_GLU;
-  ZV_REQUIRE((!needCh || a->Ch) && (form != ZV_LIN_PLAIN_F32 || !a->Ch) && (form != ZV_LIN_TRANS || !a->Ch) &&
-                 (!a->Ch || a->ldch >= wch) && (a->Cl != nullptr) == (split3 && a->Ch != nullptr),
-             "zv_linear_check: the form's 16-bit outputs (Cl with split 3 only)");
-  ZV_REQUIRE(wantT == (a->Cth != nullptr) && (!wantT || (a->rpb > 0 && a->ldct >= a->rpb)) &&
-                 (a->Ctl != nullptr) == (split3 && wantT),
-             "zv_linear_check: the transposed outputs");
-  ZV_REQUIRE((form != ZV_LIN_NA || N % 48 == 0) && (form != ZV_LIN_GLU || N % 32 == 0), "zv_linear_check: NA / GLU widths");
-
-  LinearPolicy policy;                     // the engine's dispatch policy (its run-time knobs)
-  WeightStore store;
-  std::vector<int> perm(N);               // the fused epilogues' row order (identity otherwise)
-  for (int n = 0; n < N; ++n) perm[n] = n;
-  if (form == ZV_LIN_NA) perm = zv_engine::perm_na(N / 3);
-  if (form == ZV_LIN_GLU) perm = zv_engine::perm_glu(N / 2);
-  std::vector<float> wp((size_t)N * K), bp(N);
-  for (int n = 0; n < N; ++n) {
-    memcpy(&wp[(size_t)n * K], a->W + (size_t)perm[n] * K, (size_t)K * sizeof(float));
-    bp[n] = a->bias[perm[n]];
-  }
-  const Linear Lw = store.make_linear(wp.data(), N, K, bp.data());
-
-  ChkDev dev;
-  hipStream_t s = nullptr;
-  Act A;
-  {
-    std::vector<bf16> h, l;
-    A.ld = round_up(K, 64);
-    chk_act(a->A, M, K, A.ld, split3, h, l);
-    A.h = dev.up(h.data(), h.size());
-    if (split3) A.l = dev.up(l.data(), l.size());
-  }
-  const long rows = (long)M + 2 * G;
-  float* dC = nullptr;
-  bf16 *dCh = nullptr, *dCl = nullptr, *dCth = nullptr, *dCtl = nullptr;
-  const int nutt = wantT ? cdiv(M, a->rpb) : 0, rows_t = form == ZV_LIN_NA ? N / 3 : N;
-  const long trows = wantT ? (long)nutt * rows_t + 2 * G : 0;
-  if (a->C) {
-    std::vector<float> hc(a->C, a->C + (size_t)rows * a->ldc);
-    if (resid)
-      for (long m = 0; m < M; ++m)
-        memcpy(&hc[(size_t)(G + m) * a->ldc], a->resid + m * N, (size_t)N * sizeof(float));
-    dC = dev.up(hc.data(), hc.size());
-  }
-  if (a->Ch) dCh = reinterpret_cast<bf16*>(dev.up(a->Ch, (size_t)rows * a->ldch));
-  if (a->Cl) dCl = reinterpret_cast<bf16*>(dev.up(a->Cl, (size_t)rows * a->ldch));
-  if (a->Cth) dCth = reinterpret_cast<bf16*>(dev.up(a->Cth, (size_t)trows * a->ldct));
-  if (a->Ctl) dCtl = reinterpret_cast<bf16*>(dev.up(a->Ctl, (size_t)trows * a->ldct));
-  const uint8_t* dmask = a->rowmask ? dev.up(a->rowmask, (size_t)M) : nullptr;
-
-  if (!fused) {
-    Out o;
-    o.act_fn = a->act;
-    if (dC) { o.C = dC + (size_t)G * a->ldc; o.ldc = a->ldc; }
-    if (dCh) { o.act.h = dCh + (size_t)G * a->ldch; o.act.ld = a->ldch; }
-    if (dCl) o.act.l = dCl + (size_t)G * a->ldch;
-    if (resid) {
-      if (o.C) {
-        o.resid = o.C;                     // in place, as the engine updates its stream
-      } else {
-        o.ldc = a->ldc;
-        std::vector<float> r = chk_pad(a->resid, M, N, a->ldc);
-        o.resid = dev.up(r.data(), r.size());
-      }
-    }
-    if (form == ZV_LIN_RESID_BYP) {
-      std::vector<float> og = chk_pad(a->orig, M, N, a->ldc);
-      o.orig = dev.up(og.data(), og.size());
-      o.byp = dev.up(a->byp, (size_t)N);
-    }
-    if (rv) {
-      o.rowvec = dev.up(a->rowvec, (size_t)cdiv(M, a->rows_per_group) * N);
-      o.rowvec_ld = N; o.rows_per_group = a->rows_per_group;
-    }
-    if (a->split == 2) policy.attn_in_wsplit(Lw, A, M, o, s);
-    else if (split3) policy.linear16<3>(Lw, A, M, o, s);
-    else policy.linear16<1>(Lw, A, M, o, s);
-  } else {
-    GemmParams p = LinearPolicy::gp_linear(Lw, A, M);
-    if (a->split == 2) p.Al = nullptr;
-    if (dCh) { p.Ch = dCh + (size_t)G * a->ldch; p.ldch = a->ldch; }
-    if (dCl) p.Cl = dCl + (size_t)G * a->ldch;
-    if (wantT) {
-      p.Cth = dCth + (size_t)G * a->ldct;
-      if (dCtl) p.Ctl = dCtl + (size_t)G * a->ldct;
-      p.ldct = a->ldct; p.rpb = a->rpb; p.sCt = (long)rows_t * a->ldct;
-    }
-    if (form == ZV_LIN_GLU) p.rowmask = dmask;
-    if (form == ZV_LIN_NA) {
-      if (split3) policy.launch_na_in<3>(p, s); else policy.launch_na_in<1>(p, s);
-    } else if (form == ZV_LIN_TRANS) {
-      if (split3) policy.launch_value_t<3>(p, false, true, s);
-      else policy.launch_value_t<1>(p, a->split == 2, Lw.lo != nullptr, s);
-    } else {
-      if (split3) policy.launch_glu_in<3>(p, false, s); else policy.launch_glu_in<1>(p, false, s);
-    }
-  }
-  ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
-  chk_record(a->launch, &a->num_cus);
-  if (a->C) dev.down(a->C, dC, (size_t)rows * a->ldc);
-  if (a->Ch) dev.down(a->Ch, reinterpret_cast<uint16_t*>(dCh), (size_t)rows * a->ldch);
-  if (a->Cl) dev.down(a->Cl, reinterpret_cast<uint16_t*>(dCl), (size_t)rows * a->ldch);
-  if (a->Cth) dev.down(a->Cth, reinterpret_cast<uint16_t*>(dCth), (size_t)trows * a->ldct);
-  if (a->Ctl) dev.down(a->Ctl, reinterpret_cast<uint16_t*>(dCtl), (size_t)trows * a->ldct);
-  ZV_API_END
-}
-
-int zv_ffn_check(zv_ffn_check_args* a) {
-  ZV_API_BEGIN
-  ZV_REQUIRE(a && a->M > 0 && a->H > 0 && a->H % (2 * FFN_HC) == 0 && a->form >= 0 && a->form <= 3 &&
-                 a->guard >= 0 && a->part_slots >= 0 && a->x && a->W1 && a->b1 && a->W2 && a->b2 &&
-                 a->resid && a->C && a->ldc >= FFN_D && (!a->Ch || a->ldch >= FFN_D),
-             "zv_ffn_check: bad arguments");
-  const int M = a->M, H = a->H, form = a->form, G = a->guard, D = FFN_D;
-  const bool norm = form == 3, byp = form == 2 || norm, rv = a->rowvec != nullptr;
-  ZV_REQUIRE((form == 1) == (rv && !norm) || norm, "zv_ffn_check: the row vector belongs to form 1 (or 3)");
-  ZV_REQUIRE((!rv || a->rows_per_group > 0) && (!byp || (a->orig && a->byp)) && (!norm || a->nb) &&
-                 (form == 0 || a->Ch) && (norm || (!a->Cl && !a->C2h && !a->C2l)) &&
-                 (!a->C2l || a->C2h),
-             "zv_ffn_check: the form's operands");
-  ZV_REQUIRE(a->part_slots <= zv_num_cus(), "zv_ffn_check: more lines than CUs");
-  WeightStore store;
-  const Linear L1 = store.make_linear(a->W1, H, D, a->b1);
-  const Linear L2 = store.make_linear(a->W2, D, H, a->b2);
-  ChkDev dev;
-  hipStream_t s = nullptr;
-  const long n = (long)H * D;
-  bf16* w1f = reinterpret_cast<bf16*>(dev.raw((size_t)n * sizeof(bf16)));
-  bf16* w2f = reinterpret_cast<bf16*>(dev.raw((size_t)n * sizeof(bf16)));
-  hipLaunchKernelGGL(zv_ffn_pack_w1_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, L1.hi, (long)L1.Kpad, H, w1f);
-  hipLaunchKernelGGL(zv_ffn_pack_w2_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, L2.hi, (long)L2.Kpad, H, w2f);
-  ZV_LAUNCH_CHECK();
-  FfnParams q{};
-  q.H = H; q.nseg = 1;
-  FfnSeg& g = q.seg[0];
-  g.M = M;
-  {
-    std::vector<bf16> h, l;
-    chk_act(a->x, M, D, D, false, h, l);
-    g.X = dev.up(h.data(), h.size());
-    q.ldx = D;
-  }
-  q.W1f = w1f; q.b1 = L1.b; q.W2f = w2f; q.b2 = L2.b;
-  const long rows = (long)M + 2 * G;
-  // C: resid in its interior (in place), or for the BiasNorm epilogue orig (C == orig, resid apart)
-  std::vector<float> hc(a->C, a->C + (size_t)rows * a->ldc);
-  for (long m = 0; m < M; ++m)
-    memcpy(&hc[(size_t)(G + m) * a->ldc], (norm ? a->orig : a->resid) + m * D, (size_t)D * sizeof(float));
-  float* dC = dev.up(hc.data(), hc.size());
-  g.C = dC + (size_t)G * a->ldc; q.ldc = a->ldc;
-  auto padded = [&](const float* x) {
-    std::vector<float> v = chk_pad(x, M, D, a->ldc);
-    return dev.up(v.data(), v.size());
-  };
-  if (norm) { g.resid = padded(a->resid); g.orig = g.C; }
-  else { g.resid = g.C; if (byp) g.orig = padded(a->orig); }
-  if (byp) q.byp = dev.up(a->byp, (size_t)D);
-  if (norm) { q.nb = dev.up(a->nb, (size_t)D); q.log_scale = a->log_scale; }
-  if (rv) {
-    g.rowvec = dev.up(a->rowvec, (size_t)cdiv(M, a->rows_per_group) * D);
-    q.rowvec_ld = D; q.rows_per_group = a->rows_per_group;
-  }
-  uint16_t* host16[4] = {a->Ch, a->Cl, a->C2h, a->C2l};
-  bf16* dev16[4] = {};
-  for (int i = 0; i < 4; ++i)
-    if (host16[i]) dev16[i] = reinterpret_cast<bf16*>(dev.up(host16[i], (size_t)rows * a->ldch));
-  q.ldch = a->Ch ? a->ldch : 0;
-  auto inner = [&](bf16* p) { return p ? p + (size_t)G * a->ldch : nullptr; };
-  g.Ch = inner(dev16[0]); g.Cl = inner(dev16[1]); g.C2h = inner(dev16[2]); g.C2l = inner(dev16[3]);
-  if (a->part_slots > 0) {   // the persistent line schedule's scratch, zero-filled
-    q.part_slots = a->part_slots;
-    q.part = reinterpret_cast<float*>(dev.raw((size_t)a->part_slots * FFN_PART_FLOATS * sizeof(float)));
-    q.flag = reinterpret_cast<unsigned*>(dev.raw(((size_t)a->part_slots + 64) * sizeof(unsigned)));
-    ZV_CHECK(ZV_BLOCKING(hipMemset(q.part, 0, (size_t)a->part_slots * FFN_PART_FLOATS * sizeof(float))));
-    ZV_CHECK(ZV_BLOCKING(hipMemset(q.flag, 0, ((size_t)a->part_slots + 64) * sizeof(unsigned))));
-  }
-  ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
-  launch_ffn(q, s, norm ? "ffn_norm_check" : "ffn_check");
-  ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
-  chk_record(a->launch, &a->num_cus);
-  volatile unsigned* e = zv_dev_err_host();
-  if (*e != 0) {
-    *e = 0;
-    throw std::runtime_error("zv_ffn_check: the device error word was set (a C item outwaited its producer)");
-  }
-  dev.down(a->C, dC, (size_t)rows * a->ldc);
-  for (int i = 0; i < 4; ++i)
-    if (host16[i]) dev.down(host16[i], reinterpret_cast<uint16_t*>(dev16[i]), (size_t)rows * a->ldch);
   ZV_API_END
 }
 

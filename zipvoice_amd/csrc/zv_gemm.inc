@@ -201,15 +201,10 @@ __device__ __forceinline__ void load_split4(const bf16* hi, const bf16* lo, long
 // SWZ: unpadded strip (16 x WN fp32, WN a power of two >= 64) with the 16-column
 // groups XOR-swizzled by row quad instead of the padded row (bank spread at
 // 4 KiB per wave for WN = 64: the 256x256 kernel's scratch budget).
-// DEFER (> 0): the STD store-only form whose stores the next tile's first K step
-// does not wait for: rows past M are clamped to M - 1 (their accumulators are
-// that row's: the A rows were clamped the same way, so the duplicate store writes
-// identical bytes) and N is a multiple of the tile width, so every lane issues
-// exactly DEFER stores per tile and the kernel counts them (vmcnt(DEFER)).
 // RP: the residual (and bypass original) arrive as bf16 hi/lo pairs (p.residh /
 // p.residl, p.origh / p.origl, indexed like Ch) and the result leaves as the pair
 // (Ch / Cl): 8 B per residual update instead of fp32 read + write + bf16 copy.
-template <int TM, int TN, int EPI, bool SWZ = false, int DEFER = 0, int RP = 0>
+template <int TM, int TN, int EPI, bool SWZ = false, int RP = 0>
 __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[TM][TN], int m0,
                                               int n0, int z1, int z2, int lane, float* scr) {
   constexpr int WN = EpiScratch<TN>::W;      // staged columns (the wave's full width)
@@ -288,10 +283,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
       for (int q = 0; q < Q8; ++q) {
         const int idx = lane + 64 * q;
         const int row = idx / C8, c8 = (idx % C8) * 8;
-        const int m = DEFER ? min(mrow0 + row, p.M - 1) : mrow0 + row, n = n0 + c8;
-        static_assert(!DEFER || (EPI == EPI_STD && NCH % 64 == 0 && DEFER == TM * Q8),
-                      "deferred stores: one 16-B bf16 store per chunk");
-        if ((NCH % 64 == 0 || idx < NCH) && (DEFER || (m < p.M && n < p.N))) {
+        const int m = mrow0 + row, n = n0 + c8;
+        if ((NCH % 64 == 0 || idx < NCH) && m < p.M && n < p.N) {
           float v[8];
           {
             const f32x4 t0 = *reinterpret_cast<const f32x4*>(scr + sx(row, c8));
@@ -929,7 +922,7 @@ __device__ __forceinline__ void gemm_epilogue_trans_c(const GemmParams& p, f32x4
 #define ZV_GEMM_PRELOAD 1
 #endif
 template <int BM, int BN, int WGM, int WGN, int SPLIT, int EPI, int STAGES = 2, int OCC = 2,
-          int BK = GEMM_BK, int DEFER = 0, int RP = 0, int CONV = 0, int ROLE = 0,
+          int BK = GEMM_BK, int RP = 0, int CONV = 0, int ROLE = 0,
           int PRELOAD = ZV_GEMM_PRELOAD, int MXO = 0>
 __global__ __launch_bounds__(64 * WGM * WGN, OCC) void zv_gemm_kernel(GemmParams p) {
   constexpr int NW = WGM * WGN;
@@ -943,10 +936,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, OCC) void zv_gemm_kernel(GemmParams
   // the same 128-B staged row as a 64-deep bf16 step, plus 4 scale bytes per row
   constexpr bool MX = SPLIT == 8;
   constexpr int EB = MX ? 1 : 2;                                // bytes per operand element
-  static_assert(MX ? (BK == MX8_KSTEP && STAGES == 2 && !CONV && !DEFER && !RP)
+  static_assert(MX ? (BK == MX8_KSTEP && STAGES == 2 && !CONV && !RP)
                    : (BK == 64 || BK == 32), "K step depth");
   static_assert(MXO == 0 || (ROLE >= 1 && EPI == EPI_STD), "fp8 copy out: counted STD epilogues");
-  static_assert(DEFER == 0 || STAGES == 2, "deferred epilogue stores: two-stage ring");
   constexpr int RB = BK * EB, CPRW = RB / 16, RPP = 1024 / RB;  // row bytes, chunks/row, rows/piece
   constexpr int A_BYTES = BM * BK * EB, B_BYTES = BN * BK * EB;
   constexpr int SA_P = MX ? (BM + 63) / 64 : 0, SB_P = MX ? (BN + 63) / 64 : 0;   // scale pieces
@@ -1179,8 +1171,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, OCC) void zv_gemm_kernel(GemmParams
     for (int kt = 0; kt < nk; ++kt, ++step) {
       {
         const int ahead = min(STAGES - 2, total - 1 - step);   // stages issued after this one
-        if (DEFER > 0 && kt == 0 && it > 0) wait_vmcnt<DEFER>();   // this step's DMA, not the stores after it
-        else if (ahead <= 0) wait_vmcnt<0>();
+        if (ahead <= 0) wait_vmcnt<0>();
         else if (ahead == 1) wait_vmcnt<PER_WAVE>();
         else if (ahead == 2) wait_vmcnt<2 * PER_WAVE>();
         else wait_vmcnt<3 * PER_WAVE>();
@@ -1194,7 +1185,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, OCC) void zv_gemm_kernel(GemmParams
     const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
     __builtin_amdgcn_s_barrier();          // every wave done reading the last stage
     float* scr = reinterpret_cast<float*>(smem + ((step - 1) % STAGES) * STAGE + wave * SCR);
-    if constexpr (ROLE >= 1 && EPI == EPI_STD && !RP && !DEFER && !SWZ)
+    if constexpr (ROLE >= 1 && EPI == EPI_STD && !RP && !SWZ)
       gemm_epilogue_res<TM, TN, NS, ROLE == 2, ROLE != 3, MXO, ROLE == 4 || ROLE == 5, ROLE == 5>(
           p, acc, m0 + wm0, n0 + wn0, lane, scr);
     else if constexpr (ROLE == 3 && EPI == EPI_GLU && !SWZ)
@@ -1204,11 +1195,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, OCC) void zv_gemm_kernel(GemmParams
     else if constexpr (ROLE == 3 && EPI == EPI_TRANS && !SWZ)
       gemm_epilogue_trans_c<TM, TN, NS>(p, acc, m0 + wm0, n0 + wn0, lane, scr);
     else
-      gemm_epilogue<TM, TN, EPI, SWZ, DEFER, RP>(p, acc, m0 + wm0, n0 + wn0, z1, z2, lane, scr);
+      gemm_epilogue<TM, TN, EPI, SWZ, RP>(p, acc, m0 + wm0, n0 + wn0, z1, z2, lane, scr);
     // drain the epilogue's own loads/stores with a wait hipcc can see, so its
     // waitcnt pass carries no pending VMEM into the next tile's k-loop (it would
     // otherwise re-wait vmcnt(0) inside every k-step, stalling on the DMA ring)
-    if constexpr (DEFER == 0) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
   }
 }
 
@@ -1274,7 +1265,7 @@ static int zv_num_cus() {
 
 // the counted epilogues' preconditions and operands (sink, zero row mask), shared by the
 // 128x128 and 256x256 launchers
-template <int SPLIT, int EPI, int ROLE, int MXO, int RP, int DEFER>
+template <int SPLIT, int EPI, int ROLE, int MXO, int RP>
 static GemmParams gemm_prep_epilogue(const GemmParams& p, int nz) {
   GemmParams pr = p;
   if constexpr (ROLE == 3 && EPI == EPI_GLU) {
@@ -1290,14 +1281,14 @@ static GemmParams gemm_prep_epilogue(const GemmParams& p, int nz) {
                    (p.Ctl != nullptr) == (SPLIT == 3) && (EPI == EPI_TRANS || (p.Cl != nullptr) == (SPLIT == 3)),
                "counted NA / transposed epilogue: bias, outputs present, N % 48 == 0");
     pr.sink = zv_epi_sink();
-  } else if constexpr (ROLE == 3 && EPI == EPI_STD && !RP && !DEFER) {
+  } else if constexpr (ROLE == 3 && EPI == EPI_STD && !RP) {
     ZV_REQUIRE(p.bias && (p.Ch || MXO == 2) && !p.C && !p.resid && !p.orig && !p.rowvec && !p.mulh &&
                    !p.colscale && p.N % 8 == 0 && p.ldch % 8 == 0 && nz == 1 && p.nz2 == 1 &&
                    (p.Cl != nullptr) == (SPLIT == 3),
                "counted plain GEMM epilogue: bias (+ activation) -> bf16 copy, N % 8 == 0");
     pr.sink = zv_epi_sink();
     if (MXO == 2) { pr.Ch = reinterpret_cast<bf16*>(pr.sink + 4096); pr.ldch = 0; }   // not written
-  } else if constexpr (ROLE >= 1 && EPI == EPI_STD && !RP && !DEFER) {
+  } else if constexpr (ROLE >= 1 && EPI == EPI_STD && !RP) {
     ZV_REQUIRE(p.resid && (ROLE == 5) == (p.C == nullptr) && (ROLE != 5 || p.Ch) && p.bias &&
                    (ROLE == 4 || ROLE == 5) == (p.rowvec != nullptr) && p.rows_per_group > 0 &&
                    !p.act && !p.mulh && !p.colscale &&
@@ -1339,7 +1330,7 @@ struct ZvLaunchRec { int BM, BN, SPLIT, EPI, ROLE, k256, grid, aux; };
 static thread_local ZvLaunchRec g_zv_last_launch = {};
 
 template <int BM, int BN, int WGM, int WGN, int SPLIT, int EPI, int STAGES = 2, int OCC = 2,
-          int BK = GEMM_BK, int DEFER = 0, int RP = 0, int CONV = 0, int ROLE = 0, int MXO = 0>
+          int BK = GEMM_BK, int RP = 0, int CONV = 0, int ROLE = 0, int MXO = 0>
 static void launch_gemm(const GemmParams& p, int nz, hipStream_t s, const char* tag,
                         bool persistent = true, int gridx = 0) {
   constexpr int NS = (SPLIT == 3) ? 2 : 1;
@@ -1349,7 +1340,7 @@ static void launch_gemm(const GemmParams& p, int nz, hipStream_t s, const char* 
   static unsigned long long attr = 0;   // per device (hipFuncSetAttribute is per device)
   if (!((attr >> zv_cur_device()) & 1)) {
     ZV_CHECK(hipFuncSetAttribute(
-        (const void*)zv_gemm_kernel<BM, BN, WGM, WGN, SPLIT, EPI, STAGES, OCC, BK, DEFER, RP, CONV, ROLE, ZV_GEMM_PRELOAD, MXO>,
+        (const void*)zv_gemm_kernel<BM, BN, WGM, WGN, SPLIT, EPI, STAGES, OCC, BK, RP, CONV, ROLE, ZV_GEMM_PRELOAD, MXO>,
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr |= 1ull << zv_cur_device();
   }
@@ -1361,14 +1352,11 @@ static void launch_gemm(const GemmParams& p, int nz, hipStream_t s, const char* 
   if constexpr (MXO > 0)
     ZV_REQUIRE(p.Cq && p.Cs && p.ldcq % MX8_KSTEP == 0 && p.N <= p.ldcq,
                "fp8 output copy: values and scales, row stride a multiple of 128");
-  if constexpr (DEFER > 0)
-    ZV_REQUIRE(p.N % BN == 0 && p.Ch && !p.Cl && !p.C && !p.resid && p.ldch % 8 == 0 && p.nz2 == 1,
-               "deferred-store GEMM: bf16-only output, N a multiple of the tile width");
   if constexpr (RP > 0)
     ZV_REQUIRE(p.residh && p.residl && p.Ch && p.Cl && !p.C && !p.resid && !p.orig && p.N % 8 == 0 &&
                    p.ldch % 8 == 0 && EPI == EPI_STD,
                "pair-residual GEMM: hi/lo residual in and out, N and ld multiples of 8");
-  GemmParams pr = gemm_prep_epilogue<SPLIT, EPI, ROLE, MXO, RP, DEFER>(p, nz);
+  GemmParams pr = gemm_prep_epilogue<SPLIT, EPI, ROLE, MXO, RP>(p, nz);
   if constexpr (CONV)
     ZV_REQUIRE(p.conv_c > 0 && p.conv_c % BK == 0 && p.K % p.conv_c == 0 && p.lda == p.conv_c &&
                    p.conv_pad >= 0 && p.conv_d > 0 && p.nz2 == 1,
@@ -1395,7 +1383,7 @@ static void launch_gemm(const GemmParams& p, int nz, hipStream_t s, const char* 
   g_zv_last_launch = ZvLaunchRec{BM, BN, SPLIT, EPI, ROLE, 0, G, STAGES * 16 + OCC};
   const double bytes = gemm_alg_bytes<SPLIT, ROLE, MXO>(p, nz);
   ZvProfScope prof(tag, 2.0 * p.M * p.N * (double)p.K * nz, bytes, s);
-  hipLaunchKernelGGL((zv_gemm_kernel<BM, BN, WGM, WGN, SPLIT, EPI, STAGES, OCC, BK, DEFER, RP, CONV, ROLE, ZV_GEMM_PRELOAD, MXO>), dim3(G, 1, nz),
+  hipLaunchKernelGGL((zv_gemm_kernel<BM, BN, WGM, WGN, SPLIT, EPI, STAGES, OCC, BK, RP, CONV, ROLE, ZV_GEMM_PRELOAD, MXO>), dim3(G, 1, nz),
                      dim3(64 * WGM * WGN), lds, s, pr);
   ZV_LAUNCH_CHECK();
 }

@@ -611,7 +611,7 @@ static void launch_gemm256(const GemmParams& p, hipStream_t s, const char* tag, 
   if constexpr (MXO > 0)
     ZV_REQUIRE(p.Cq && p.Cs && p.ldcq % MX8_KSTEP == 0 && p.N <= p.ldcq,
                "fp8 output copy: values and scales, row stride a multiple of 128");
-  GemmParams pr = ROLE == 9 ? p : gemm_prep_epilogue<1, EPI, ROLE, MXO, 0, 0>(p, 1);
+  GemmParams pr = ROLE == 9 ? p : gemm_prep_epilogue<1, EPI, ROLE, MXO, 0>(p, 1);
   if constexpr (DIRECT && ROLE != 9)
     ZV_REQUIRE(p.N % 8 == 0 && (EPI != EPI_GLU || p.ldch % 8 == 0) && (p.act == 0 || p.act == 1),
                "gemm256 direct epilogue: N % 8 == 0, activation none or SwooshL");

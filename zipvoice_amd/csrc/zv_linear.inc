@@ -18,7 +18,7 @@
 //    128x64 counted tiles at two blocks per CU (mode 1): 12.9 / 10.1 ms per step against 9.1 ms for
 //    counted 128x128 (r02_n96_counted_ab.txt); 16-bit mode since on 128x64 at three blocks per CU
 //    (below)
-//  - deferred epilogue stores (zv_gemm.inc DEFER 8) for the bf16-only linears on whole tiles:
+//  - deferred epilogue stores (since removed from zv_gemm.inc) for the bf16-only linears on whole tiles:
 //    208.4 against 217.4 us alone at 78016 x 1536 x 512, but one guided forward 35.66 against
 //    35.34 ms (r01_gemm_defer_ab.txt)
 //  - the V^T projection on 128x64 persistent tiles: 44.3 against 37.0 us at 78016 rows
@@ -69,7 +69,7 @@ struct Out {              // epilogue of a linear
 template <int BM, int BN, int SPLIT, int EPI, int STAGES = 2, int OCC = 2, int ROLE = 0, int MXO = 0,
           int BK = GEMM_BK>
 void gemm_tile(const GemmParams& p, hipStream_t s, const char* tag) {
-  launch_gemm<BM, BN, 2, 2, SPLIT, EPI, STAGES, OCC, BK, 0, 0, 0, ROLE, MXO>(p, 1, s, tag, true, -1);
+  launch_gemm<BM, BN, 2, 2, SPLIT, EPI, STAGES, OCC, BK, 0, 0, ROLE, MXO>(p, 1, s, tag, true, -1);
 }
 
 struct LinearPolicy {
@@ -199,7 +199,7 @@ struct LinearPolicy {
     p.residh = o.residh; p.residl = o.residl; p.origh = o.origh; p.origl = o.origl;
     if constexpr (SPLIT == 1) {
       if (o.residh) {   // pair-residual linear: own instantiation (RP 1), the residual policy
-        launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 0, 1>(p, 1, s, "gemm_bf16", true, -1);
+        launch_gemm<128, 128, 2, 2, 1, EPI_STD, 2, 2, GEMM_BK, 1>(p, 1, s, "gemm_bf16", true, -1);
         return false;
       }
     }
