@@ -194,7 +194,12 @@ enum zv_linear_form {
   ZV_LIN_RESID_RV_COPY = 5,/* the same value to Ch only (no fp32 output; resid read from `resid`) */
   ZV_LIN_TRANS = 6,        /* bias -> Cth (/ Ctl), transposed per utterance of rpb rows */
   ZV_LIN_NA = 7,           /* W rows [s | x | y] (chunk(3)): x * tanh(s) -> Cth, y -> Ch, N / 3 wide */
-  ZV_LIN_GLU = 8           /* W rows [x | s] (chunk(2)): x * sigmoid(s), 0 where rowmask -> Ch, N / 2 wide */
+  ZV_LIN_GLU = 8,          /* W rows [x | s] (chunk(2)): x * sigmoid(s), 0 where rowmask -> Ch, N / 2 wide */
+  ZV_LIN_GLU_DW = 9        /* the ConvolutionModule's fused launch (zv_gemm256.inc g256_epi_glu_dw): GLU as above,
+                              rounded to the operand format, then the depthwise conv of dw_ks taps ("same" zero
+                              padding per utterance of dw_L rows) + SwooshR -> Ch, N / 2 wide.  split 1, N = 1024,
+                              dw_ks 7 / 15 / 31, M % dw_L == 0, ldch % 8 == 0: the engine's own conditions for this
+                              launch; anything else is rejected, never replaced by the unfused pair */
 };
 typedef struct {
   int M, N, K, split, form, act;
@@ -207,6 +212,9 @@ typedef struct {
   const float* byp;        /* (N) */
   const float* rowvec;     /* (ceil(M / rows_per_group), N) */
   const uint8_t* rowmask;  /* (M) or NULL */
+  const float* dw_w;       /* GLU_DW: the conv's taps (N / 2, dw_ks) */
+  const float* dw_b;       /* GLU_DW: the conv's bias (N / 2) */
+  int dw_ks, dw_L;         /* GLU_DW: kernel size, rows per utterance */
   float* C; int64_t ldc;
   uint16_t* Ch; uint16_t* Cl; int64_t ldch;
   uint16_t* Cth; uint16_t* Ctl; int64_t ldct;
@@ -243,6 +251,59 @@ typedef struct {
   int num_cus;
 } zv_ffn_check_args;
 int zv_ffn_check(zv_ffn_check_args* a);
+
+/* The ConvolutionModule's depthwise conv + SwooshR alone, through the engine's launch_dwconv (test
+ * infrastructure: pins csrc/zv_elem.inc's four kernels against float64 in tests/test_gpu_dwconv_ref.py;
+ * no reference counterpart; synchronous).  g (B * L, C) is rounded to the operand format (with its lo
+ * half when split = 3) into rows of ldin elements; w (C, ks) and bias (C) are fp32.  The kernel is the
+ * one the engine would launch for these sizes, strides and operands; ZV_DWCONV_PIPE (0, 1 = automatic
+ * chunk, n = chunks of n 64-frame tiles) and ZV_DWCONV_LDS=0 are read per launch and select the other
+ * arms.  Oh / Ol: (guard + B * L + guard, ldout) 16-bit, canary-filled by the caller (Ol with split 3
+ * only); q / qs (or NULL): the output's MX-fp8 copy, (guard + B * L + guard, ldq) codes and
+ * (..., ldq / 32) scale bytes, canary-filled.  launch: {kernel (0 generic, 1 register-window, 2 LDS,
+ * 3 pipe), ks, 3 with lo halves else 1, fp8 copy, grid x, grid y, grid z, 64-frame tiles per pipe
+ * chunk (0 for the other kernels)}. */
+typedef struct {
+  int B, L, C, ks, split, guard;
+  const float* g; const float* w; const float* bias;
+  int64_t ldin;
+  uint16_t* Oh; uint16_t* Ol; int64_t ldout;
+  uint8_t* q; uint8_t* qs; int64_t ldq;
+  int launch[8];
+  int num_cus;
+} zv_dwconv_check_args;
+int zv_dwconv_check(zv_dwconv_check_args* a);
+
+/* The kernels at the stack boundaries, each launched as zv_engine launches it (test infrastructure:
+ * pins them against float64 in tests/test_gpu_stackedge_ref.py; synchronous).  M = B * L rows,
+ * dL = ceil(L / ds).  fp32 outputs have guard rows only (their row stride is C); 16-bit outputs have
+ * guard rows and a row stride ldact (a multiple of 4); all are canary-filled by the caller.
+ *   ZV_SE_DOWNSAMPLE  x (M, C), w (ds) -> out (guard + B * dL + guard, C)
+ *   ZV_SE_UPSAMPLE    x = the downsampled stream (B * dL, C), w = the combiner scale (C), orig (M, C)
+ *                     -> out (guard + M + guard, C), updated in place over orig; the row-blocked kernel
+ *                     where 256 % (C / 4) == 0, else the grid-stride one (launch[1] = 0 / 1)
+ *   ZV_SE_MASK        mask (B, L) -> mout (guard + B * dL + guard) bytes
+ *   ZV_SE_ENTRY       x = src (M, C), rowvec (or NULL) -> h / l = src, h2 / l2 = src + rowvec[row /
+ *                     rows_per_group] (l, l2 optional), and the fp32 sum -> out where given
+ *   ZV_SE_BIASNORM    x (M, C), nb (C), log_scale, w = bypass scale (C), orig (M, C) -> out in place
+ *                     over orig, h (/ l); h2 (/ l2) = out + rowvec where given, and its MX-fp8 copy
+ *                     q2 (guard + M + guard, ldq) / qs2 (..., ldq / 32); zv_biasnorm_bypass_v_kernel<2>
+ *                     at C = 512, else the generic kernel (launch[1] = 1 / 0)
+ * launch: {kind, kernel form, grid blocks, block threads, 0...}. */
+enum zv_stackedge_kind { ZV_SE_DOWNSAMPLE = 0, ZV_SE_UPSAMPLE = 1, ZV_SE_MASK = 2, ZV_SE_ENTRY = 3, ZV_SE_BIASNORM = 4 };
+typedef struct {
+  int kind, B, L, C, ds, guard, rows_per_group;
+  float log_scale;
+  const float* x; const float* w; const float* nb; const float* orig; const float* rowvec;
+  const uint8_t* mask;
+  float* out;
+  uint8_t* mout;
+  uint16_t* h; uint16_t* l; uint16_t* h2; uint16_t* l2; int64_t ldact;
+  uint8_t* q2; uint8_t* qs2; int64_t ldq;
+  int launch[8];
+  int num_cus;
+} zv_stackedge_check_args;
+int zv_stackedge_check(zv_stackedge_check_args* a);
 
 /* Attention plan (host only, no GPU; test infrastructure): the LDS bytes of the fused
  * attention consumers a layer of sequence length L would launch — SelfAttention (sa_plo < 0:

@@ -1,7 +1,9 @@
 """CPU checks of the float64 kernel references (tests/kernel_ref.py) that the GPU tests
 test_gpu_linear_ref.py / test_gpu_ffn_ref.py rely on: the 16-bit rounding helpers against torch,
 the exact class's exactness argument, the fp32-formula error table the transcendental tolerances
-come from, and the FeedForward tolerance's 2 % cap."""
+come from, the FeedForward tolerance's 2 % cap, and for test_gpu_dwconv_ref.py / test_gpu_stackedge_ref.py
+the conv reference against independent formulations, the exact class's exactness, SwooshR's error over
+the conv's range and the ambiguity cap of every case's inputs."""
 import numpy as np
 import pytest
 
@@ -116,3 +118,165 @@ def test_ffn_tolerance_cap(fmt, H):
           f"{np.median(drop / tol):.0f}x")
     assert worst < 0.02
     assert np.median(drop / tol) > 10
+
+
+# --------------------------------------------------------------------------- depthwise conv
+@pytest.mark.parametrize("B,L,C,ks", [(1, 1, 4, 7), (3, 3, 6, 7), (2, 14, 5, 31), (3, 65, 8, 15), (2, 40, 3, 63),
+                                      (2, 9, 6, 5), (1, 130, 4, 9)])
+def test_dwconv_ref_matches_conv1d(B, L, C, ks):
+    """dwconv_ref (loops over taps) against torch's grouped conv1d in float64, one utterance at a time."""
+    rng = np.random.default_rng(ks * 1000 + L)
+    g, w, bias = rng.standard_normal((B * L, C)), rng.standard_normal((C, ks)), rng.standard_normal(C)
+    y, u, mag = kr.dwconv_ref(g, w, bias, B, L)
+    for b in range(B):
+        x = torch.from_numpy(g[b * L:(b + 1) * L].T.copy())[None]            # (1, C, L)
+        ref = torch.nn.functional.conv1d(x, torch.from_numpy(w)[:, None, :], torch.from_numpy(bias),
+                                         padding=ks // 2, groups=C)[0].T.numpy()
+        assert np.abs(u[b * L:(b + 1) * L] - ref).max() < 1e-12
+        m = torch.nn.functional.conv1d(x.abs(), torch.from_numpy(np.abs(w))[:, None, :], torch.from_numpy(np.abs(bias)),
+                                       padding=ks // 2, groups=C)[0].T.numpy()
+        assert np.abs(mag[b * L:(b + 1) * L] - m).max() < 1e-12
+    assert np.array_equal(y, kr.swoosh_r(u))
+
+
+def test_dwconv_ref_matches_oracle_conv_module():
+    """dwconv_ref against the oracle's ConvolutionModule conv (oracle/zipvoice_np.py, fp32) on the
+    depthwise weights the golden fixtures were made with (the synthetic state dict, seed 0)."""
+    from oracle.zipvoice_np import depthwise_conv1d, swoosh_r_fwd
+    from zipvoice_amd.config import default_config
+    from zipvoice_amd.weights import synthetic_state_dict
+    sd = synthetic_state_dict(default_config("zipvoice"), 0)
+    keys = sorted(k for k in sd if k.startswith("fm_decoder") and k.endswith("conv_module1.depthwise_conv.weight"))
+    sizes = set()
+    for k in keys:
+        w3 = np.asarray(sd[k], np.float32)
+        bias = np.asarray(sd[k[:-6] + "bias"], np.float32)
+        C, _, ks = w3.shape
+        if ks in sizes:
+            continue
+        sizes.add(ks)
+        B, L = 2, 41
+        x = np.random.default_rng(ks).standard_normal((B, L, C)).astype(np.float32)
+        want = depthwise_conv1d(x, w3, bias).astype(np.float64).reshape(B * L, C)
+        y, u, mag = kr.dwconv_ref(x.reshape(B * L, C).astype(np.float64), w3[:, 0].astype(np.float64),
+                                  bias.astype(np.float64), B, L)
+        assert (np.abs(u - want) <= (ks + 2) * 2.0 ** -23 * mag).all(), ks
+        yo = swoosh_r_fwd(want.astype(np.float32)).astype(np.float64)
+        assert (np.abs(y - yo) <= 0.92 * (ks + 2) * 2.0 ** -23 * mag + 2 * kr.err_swoosh_r(u)).all(), ks
+    assert {7, 15, 31} <= sizes, sizes
+
+
+def _dw_ref(case, fmt, klass):
+    arm, ks, B, L, C, pad, split, q8 = case
+    g, w, bias = kr.dwconv_inputs(B, L, C, ks, fmt, klass, split)
+    y, u, mag = kr.dwconv_ref(g, w, bias, B, L)
+    return g, w, bias, y, u, mag
+
+
+_DW_SHAPES = sorted({c[1:5] + c[6:7] for c in kr.dwconv_cases()})     # (ks, B, L, C, split)
+
+
+@pytest.mark.parametrize("fmt", ["bf16", "f16"])
+def test_dwconv_exact_class_is_exact(fmt):
+    """Exact class: the operands are exact 16-bit values (in hi alone), u is exact in fp32 in any
+    order (the lsb argument), and an fp32 evaluation in the reverse tap order gives the same bits."""
+    for ks, B, L, C, split in _DW_SHAPES:
+        g, w, bias, y, u, mag = _dw_ref(("", ks, B, L, C, 0, split, False), fmt, "exact")
+        assert np.array_equal(kr.round16(g, fmt), g) and np.array_equal(w.astype(np.float32), w)
+        kr.dwconv_exact_u(g, w, bias, u, mag)
+        if L in (9, 65):
+            acc = np.zeros((B, L, C), np.float32)
+            g3 = g.reshape(B, L, C).astype(np.float32)
+            for t in reversed(range(ks)):
+                s = t - ks // 2
+                lo, hi = max(0, -s), min(L, L - s)
+                if lo < hi:
+                    acc[:, lo:hi] += g3[:, lo + s:hi + s] * w[:, t].astype(np.float32)
+            assert np.array_equal((acc + bias.astype(np.float32)).reshape(B * L, C).astype(np.float64), u)
+    with pytest.raises(AssertionError):
+        kr.dwconv_exact_u(np.array([[3.0]]), np.array([[1 / 16.0]]), np.zeros(1), np.array([[2.0 ** 18]]),
+                          np.array([[2.0 ** 21]]))                # 2^25 lsb units
+
+
+@pytest.mark.parametrize("klass", ["exact", "general"])
+@pytest.mark.parametrize("fmt", ["bf16", "f16"])
+def test_dwconv_ambiguity_cap(fmt, klass):
+    """Every stand-alone conv case's inputs, from the reference alone: at most one output in ten is
+    ambiguous under check16's rule, multi-ulp ones only next to SwooshR's zeros; and the fp32 SwooshR
+    formula's error over these very pre-activations stays within err_swoosh_r (exact class: multiples
+    of 1/16) / err_swoosh_r_any (general class), of which the tolerance is TRANS_FACTOR times.  Measured worst ambiguous share: bf16 4.8 % (exact) /
+    1.9 % (general), fp16 9.8 % (exact, ks = 31 at L = 327) / 8.5 % (general); the fp32 formula at most
+    0.87 of err_swoosh_r over the exact class's |u| <= 504, 0.94 of err_swoosh_r_any over the general
+    class's |u| <= 2.0e3."""
+    worst, werr, umax = 0.0, 0.0, 0.0
+    for ks, B, L, C, split in _DW_SHAPES:
+        g, w, bias, y, u, mag = _dw_ref(("", ks, B, L, C, 0, split, False), fmt, klass)
+        _, tol_y = kr.dwconv_tol(u, mag, ks, klass)
+        amb, multi = kr.amb16(y, tol_y, fmt)
+        worst = max(worst, kr.assert_amb_cap(amb, multi, u, tol_y, fmt, f"{fmt} {klass} k{ks} B{B} L{L} C{C}"))
+        e = np.abs(kr.swoosh_r_f32(u).astype(np.float64) - kr.swoosh_r(u.astype(np.float32).astype(np.float64)))
+        werr = max(werr, float((e / (kr.err_swoosh_r(u) if klass == "exact" else kr.err_swoosh_r_any(u))).max()))
+        umax = max(umax, float(np.abs(u).max()))
+        assert np.isfinite(kr.round16(y, fmt)).all()
+    print(f"{fmt} {klass}: worst ambiguous share {100 * worst:.2f} %, fp32 SwooshR error / bound <= "
+          f"{werr:.2f} over |u| <= {umax:.3g}")
+    assert werr <= 1.0
+
+
+def test_swoosh_r_error_over_the_conv_range():
+    """err_swoosh_r on the exact class's grid out to its edge frames' range, err_swoosh_r_any on a
+    dense sweep of arbitrary fp32 arguments.  Measured: 1.86 and 2.21 here (2.26 on a sweep twice as
+    dense), in units of 2^-24 (|x| + 6)."""
+    x = np.arange(-1100 * 64, 1100 * 64 + 1) / 64.0
+    r = (np.abs(kr.swoosh_r_f32(x).astype(np.float64) - kr.swoosh_r(x)) / (kr.U32 * (np.abs(x) + 6.0))).max()
+    print(f"SwooshR on multiples of 1/64, |x| <= 1100: {r:.2f}")
+    assert r <= 1.9
+    x = np.linspace(-9000.0, 9000.0, 4000001).astype(np.float32).astype(np.float64)
+    r = (np.abs(kr.swoosh_r_f32(x).astype(np.float64) - kr.swoosh_r(x)) / (kr.U32 * (np.abs(x) + 6.0))).max()
+    print(f"SwooshR on a dense sweep, |x| <= 9000: {r:.2f}")
+    assert r <= 2.4
+
+
+@pytest.mark.parametrize("ks", [7, 15, 31])
+@pytest.mark.parametrize("fmt", ["bf16", "f16"])
+def test_glu_dw_ambiguity_cap(fmt, ks):
+    """The fused launch's cases: outputs whose window holds an ambiguous GLU value count as ambiguous;
+    still at most one in ten.  Measured worst share: bf16 0.5 / 0.9 / 2.2 % at ks = 7 / 15 / 31,
+    fp16 2.3 / 4.3 / 8.1 %."""
+    worst = 0.0
+    for B, L in kr.GLU_DW_SHAPES:
+        for klass in ("exact", "general"):
+            ins = kr.glu_dw_inputs(B, L, ks, fmt, klass, (B, L) == kr.GLU_DW_MASKED)
+            y, tol_y, u, amb, multi = kr.glu_dw_ref(*ins, B, L, fmt, klass)
+            worst = max(worst, kr.assert_amb_cap(amb, multi, u, tol_y, fmt, f"{fmt} {klass} k{ks} B{B} L{L}"))
+            assert np.isfinite(kr.round16(y, fmt)).all()
+    print(f"{fmt} ks={ks}: worst ambiguous share {100 * worst:.2f} %")
+
+
+# --------------------------------------------------------------------------- stack boundaries
+def test_stackedge_refs():
+    """downsample_ref / upsample_combine_ref / mask_downsample_ref against the oracle's formulation
+    (pad by repeating the last frame, reshape, weighted sum; repeat and cut; [:, ::ds]), and the
+    exactness of the dyadic inputs."""
+    rng = np.random.default_rng(5)
+    for ds in (2, 4):
+        w = kr.ds_weights(ds)
+        assert w.sum() == 1.0 and len(w) == ds
+        for L in (1, 2, 5, 9, 64, 65):
+            B, C = 2, 8
+            x = rng.integers(-64, 65, (B * L, C)).astype(np.float64)
+            d = kr.downsample_ref(x, w, B, L, ds, exact=True)
+            dL = -(-L // ds)
+            for b in range(B):
+                for i in range(dL):
+                    rows = [x[b * L + min(i * ds + k, L - 1)] * w[k] for k in range(ds)]
+                    assert np.array_equal(d[b * dL + i], np.sum(rows, axis=0))
+            sc = rng.choice([0.0, 0.25, 0.5, 1.0], C)
+            out = kr.upsample_combine_ref(x, d * 4, sc, B, L, ds, exact=True)
+            for b in range(B):
+                for l in range(L):
+                    o, u = x[b * L + l], 4 * d[b * dL + l // ds]
+                    assert np.array_equal(out[b * L + l], o + (u - o) * sc)
+            m = rng.integers(0, 2, B * L).astype(np.uint8)
+            md = kr.mask_downsample_ref(m, B, L, ds)
+            assert md.shape == (B * dL,) and all(md[b * dL + i] == m[b * L + i * ds] for b in range(B) for i in range(dL))

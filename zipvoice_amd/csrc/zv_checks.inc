@@ -1,5 +1,6 @@
 // Test-infrastructure and microbenchmark entry points of the C ABI: zv_bench_gemm, zv_gemm_selftest,
-// zv_attn_plan, zv_attn2_check, zv_mx8_quantize, zv_mx8_gemm_check, zv_linear_check, zv_ffn_check.
+// zv_attn_plan, zv_attn2_check, zv_mx8_quantize, zv_mx8_gemm_check, zv_linear_check, zv_ffn_check,
+// zv_dwconv_check, zv_stackedge_check.
 // None of them builds an engine: each runs one launch (or a timed loop of one launch) of a kernel the
 // engine, the vocoder or BigVGAN dispatch also instantiates, on operands it makes itself.  Included by
 // zv_engine.hip after zv_engine (zv_linear_check uses its perm_na / perm_glu) and the ZV_API_* helpers.
@@ -403,7 +404,7 @@ int zv_linear_check(zv_linear_check_args* a) {
   ZV_API_BEGIN
   ZV_REQUIRE(a && a->M > 0 && a->N > 0 && a->K > 0 && a->A && a->W && a->bias && a->guard >= 0 &&
                  (a->split == 1 || a->split == 2 || a->split == 3) && a->form >= ZV_LIN_PLAIN &&
-                 a->form <= ZV_LIN_GLU,
+                 a->form <= ZV_LIN_GLU_DW,
              "zv_linear_check: bad arguments");
   const int M = a->M, N = a->N, K = a->K, form = a->form, G = a->guard;
   const bool split3 = a->split == 3;
@@ -418,22 +419,30 @@ int zv_linear_check(zv_linear_check_args* a) {
                  (form != ZV_LIN_RESID_BYP || (a->orig && a->byp)) &&
                  (!rv || (a->rowvec && a->rows_per_group > 0)) && (form != ZV_LIN_RESID_RV_COPY || a->ldc >= N),
              "zv_linear_check: the form's fp32 operands");
-  const int wch = form == ZV_LIN_NA ? N / 3 : form == ZV_LIN_GLU ? N / 2 : N;   // width of Ch
-  const bool needCh = form == ZV_LIN_PLAIN || form == ZV_LIN_RESID_RV_COPY || form == ZV_LIN_NA || form == ZV_LIN_GLU;
+  const bool glu = form == ZV_LIN_GLU || form == ZV_LIN_GLU_DW;
+  const int wch = form == ZV_LIN_NA ? N / 3 : glu ? N / 2 : N;   // width of Ch
+  const bool needCh = form == ZV_LIN_PLAIN || form == ZV_LIN_RESID_RV_COPY || form == ZV_LIN_NA || glu;
   ZV_REQUIRE((!needCh || a->Ch) && (form != ZV_LIN_PLAIN_F32 || !a->Ch) && (form != ZV_LIN_TRANS || !a->Ch) &&
                  (!a->Ch || a->ldch >= wch) && (a->Cl != nullptr) == (split3 && a->Ch != nullptr),
              "zv_linear_check: the form's 16-bit outputs (Cl with split 3 only)");
   ZV_REQUIRE(wantT == (a->Cth != nullptr) && (!wantT || (a->rpb > 0 && a->ldct >= a->rpb)) &&
                  (a->Ctl != nullptr) == (split3 && wantT),
              "zv_linear_check: the transposed outputs");
-  ZV_REQUIRE((form != ZV_LIN_NA || N % 48 == 0) && (form != ZV_LIN_GLU || N % 32 == 0), "zv_linear_check: NA / GLU widths");
+  ZV_REQUIRE((form != ZV_LIN_NA || N % 48 == 0) && (!glu || N % 32 == 0), "zv_linear_check: NA / GLU widths");
+  // the fused GLU + depthwise conv: the conditions of zv_engine::layer's conv lambda
+  const int dwk = a->dw_ks;
+  ZV_REQUIRE(form != ZV_LIN_GLU_DW || (a->dw_w && a->dw_b && a->dw_L > 0 && M % a->dw_L == 0),
+             "zv_linear_check: GLU_DW needs the taps, the conv bias and whole utterances of dw_L rows");
+  ZV_REQUIRE(form != ZV_LIN_GLU_DW || (a->split == 1 && N == 2 * 512 && (dwk == 7 || dwk == 15 || dwk == 31)),
+             "zv_linear_check: GLU_DW is the 16-bit product at 512 channels with kernel size 7, 15 or 31");
+  ZV_REQUIRE(form != ZV_LIN_GLU_DW || a->ldch % 8 == 0, "zv_linear_check: GLU_DW output rows of a multiple of 8 elements");
 
   LinearPolicy policy;                     // the engine's dispatch policy (its run-time knobs)
   WeightStore store;
   std::vector<int> perm(N);               // the fused epilogues' row order (identity otherwise)
   for (int n = 0; n < N; ++n) perm[n] = n;
   if (form == ZV_LIN_NA) perm = zv_engine::perm_na(N / 3);
-  if (form == ZV_LIN_GLU) perm = zv_engine::perm_glu(N / 2);
+  if (glu) perm = zv_engine::perm_glu(N / 2);
   std::vector<float> wp((size_t)N * K), bp(N);
   for (int n = 0; n < N; ++n) {
     memcpy(&wp[(size_t)n * K], a->W + (size_t)perm[n] * K, (size_t)K * sizeof(float));
@@ -506,8 +515,17 @@ int zv_linear_check(zv_linear_check_args* a) {
       if (dCtl) p.Ctl = dCtl + (size_t)G * a->ldct;
       p.ldct = a->ldct; p.rpb = a->rpb; p.sCt = (long)rows_t * a->ldct;
     }
-    if (form == ZV_LIN_GLU) p.rowmask = dmask;
-    if (form == ZV_LIN_NA) {
+    if (glu) p.rowmask = dmask;
+    if (form == ZV_LIN_GLU_DW) {
+      p.dw_w = dev.up(a->dw_w, (size_t)(N / 2) * dwk); p.dw_b = dev.up(a->dw_b, (size_t)(N / 2));
+      p.dw_out = p.Ch; p.ld_dw = p.ldch; p.dw_L = a->dw_L;
+      ZV_REQUIRE((policy.res_counted & 8) && p.bias && !p.Cl && !p.As && p.lda % 8 == 0 && p.ldb % 8 == 0 &&
+                     p.lda >= round_up(p.K, GEMM_BK) && p.ldb >= round_up(p.K, GEMM_BK) && p.Brows >= p.N,
+                 "zv_linear_check: GLU_DW operands (the engine would take the unfused pair)");
+      if (dwk == 31) launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 31>(p, s, "glu_dw_check", false);
+      else if (dwk == 15) launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 15>(p, s, "glu_dw_check", false);
+      else launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 7>(p, s, "glu_dw_check", false);
+    } else if (form == ZV_LIN_NA) {
       if (split3) policy.launch_na_in<3>(p, s); else policy.launch_na_in<1>(p, s);
     } else if (form == ZV_LIN_TRANS) {
       if (split3) policy.launch_value_t<3>(p, false, true, s);
@@ -605,6 +623,176 @@ int zv_ffn_check(zv_ffn_check_args* a) {
   dev.down(a->C, dC, (size_t)rows * a->ldc);
   for (int i = 0; i < 4; ++i)
     if (host16[i]) dev.down(host16[i], reinterpret_cast<uint16_t*>(dev16[i]), (size_t)rows * a->ldch);
+  ZV_API_END
+}
+
+// ---------------------------------------------------------------------------
+// zv_dwconv_check / zv_stackedge_check: the ConvolutionModule's depthwise conv through
+// launch_dwconv, and the kernels at the stack boundaries as zv_engine launches them, on host
+// arrays with canary-guarded outputs
+// ---------------------------------------------------------------------------
+int zv_dwconv_check(zv_dwconv_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && a->B > 0 && a->L > 0 && a->C > 0 && a->ks > 0 && (a->split == 1 || a->split == 3) &&
+                 a->guard >= 0 && a->g && a->w && a->bias && a->Oh && a->ldin >= a->C && a->ldout >= a->C,
+             "zv_dwconv_check: bad arguments");
+  ZV_REQUIRE((a->Ol != nullptr) == (a->split == 3), "zv_dwconv_check: Ol with split 3 only");
+  ZV_REQUIRE(!a->q || (a->qs && a->ldq >= a->C && a->ldq % MX8_KSTEP == 0),
+             "zv_dwconv_check: the fp8 copy needs its scales and a row stride that is a multiple of 128");
+  const int B = a->B, L = a->L, C = a->C, G = a->guard;
+  const long M = (long)B * L, rows = M + 2 * G;
+  const bool split3 = a->split == 3;
+  ChkDev dev;
+  hipStream_t s = nullptr;
+  std::vector<bf16> h, l;
+  chk_act(a->g, M, C, a->ldin, split3, h, l);
+  const bf16* ih = dev.up(h.data(), h.size());
+  const bf16* il = split3 ? dev.up(l.data(), l.size()) : nullptr;
+  const float* w = dev.up(a->w, (size_t)C * a->ks);
+  const float* bias = dev.up(a->bias, (size_t)C);
+  bf16* dOh = reinterpret_cast<bf16*>(dev.up(a->Oh, (size_t)rows * a->ldout));
+  bf16* dOl = split3 ? reinterpret_cast<bf16*>(dev.up(a->Ol, (size_t)rows * a->ldout)) : nullptr;
+  const long ldqs = a->ldq / MX8_BLOCK;
+  uint8_t* dq = a->q ? dev.up(a->q, (size_t)rows * a->ldq) : nullptr;
+  uint8_t* dqs = a->q ? dev.up(a->qs, (size_t)rows * ldqs) : nullptr;
+  launch_dwconv(ih, il, a->ldin, w, bias, dOh + (size_t)G * a->ldout, dOl ? dOl + (size_t)G * a->ldout : nullptr,
+                a->ldout, B, L, C, a->ks, s, dq ? dq + (size_t)G * a->ldq : nullptr,
+                dqs ? dqs + (size_t)G * ldqs : nullptr, a->ldq);
+  ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+  chk_record(a->launch, &a->num_cus);
+  dev.down(a->Oh, reinterpret_cast<uint16_t*>(dOh), (size_t)rows * a->ldout);
+  if (dOl) dev.down(a->Ol, reinterpret_cast<uint16_t*>(dOl), (size_t)rows * a->ldout);
+  if (dq) {
+    dev.down(a->q, dq, (size_t)rows * a->ldq);
+    dev.down(a->qs, dqs, (size_t)rows * ldqs);
+  }
+  ZV_API_END
+}
+
+int zv_stackedge_check(zv_stackedge_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && a->kind >= ZV_SE_DOWNSAMPLE && a->kind <= ZV_SE_BIASNORM && a->B > 0 && a->L > 0 &&
+                 a->guard >= 0 && (a->kind == ZV_SE_MASK || (a->C > 0 && a->C % 4 == 0 && a->x)),
+             "zv_stackedge_check: bad arguments");
+  const int kind = a->kind, B = a->B, L = a->L, C = a->C, ds = a->ds, G = a->guard;
+  const bool resample = kind <= ZV_SE_MASK;
+  ZV_REQUIRE(!resample || ds >= 1, "zv_stackedge_check: the downsampling factor");
+  const int dL = resample ? (L + ds - 1) / ds : 0;
+  const long M = (long)B * L, Md = (long)B * dL;
+  ChkDev dev;
+  hipStream_t s = nullptr;
+  int rec[8] = {kind, 0, 0, 0, 0, 0, 0, 0};          // {kind, kernel form, grid blocks, block threads}
+  // a canary-guarded fp32 output of `n` rows of C, with `fill` (or nothing) in its interior
+  auto up32 = [&](long n, const float* fill) {
+    std::vector<float> hc(a->out, a->out + (size_t)(n + 2 * G) * C);
+    if (fill) memcpy(&hc[(size_t)G * C], fill, (size_t)n * C * sizeof(float));
+    return dev.up(hc.data(), hc.size());
+  };
+  auto up16 = [&](uint16_t* p, long n) {
+    return p ? reinterpret_cast<bf16*>(dev.up(p, (size_t)(n + 2 * G) * a->ldact)) : nullptr;
+  };
+  auto in16 = [&](bf16* p) { return p ? p + (size_t)G * a->ldact : nullptr; };
+  auto down16 = [&](uint16_t* p, bf16* d, long n) {
+    if (p) dev.down(p, reinterpret_cast<uint16_t*>(d), (size_t)(n + 2 * G) * a->ldact);
+  };
+  if (kind == ZV_SE_DOWNSAMPLE) {
+    ZV_REQUIRE(a->w && a->out, "zv_stackedge_check: downsample needs the weights and out");
+    const float* in = dev.up(a->x, (size_t)M * C);
+    const float* w = dev.up(a->w, (size_t)ds);
+    float* d = up32(Md, nullptr);
+    const dim3 grid = grid1d(Md * C);
+    hipLaunchKernelGGL(zv_downsample_kernel, grid, dim3(256), 0, s, in, d + (size_t)G * C, B, L, dL, C, ds, w);
+    ZV_LAUNCH_CHECK();
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    rec[2] = (int)grid.x; rec[3] = 256;
+    dev.down(a->out, d, (size_t)(Md + 2 * G) * C);
+  } else if (kind == ZV_SE_UPSAMPLE) {
+    ZV_REQUIRE(a->w && a->orig && a->out, "zv_stackedge_check: upsample needs the scale, orig and out");
+    const float* d = dev.up(a->x, (size_t)Md * C);
+    const float* sc = dev.up(a->w, (size_t)C);
+    float* o = up32(M, a->orig);                     // in place over orig, as the engine's stream
+    float* main = o + (size_t)G * C;
+    if (C % 4 == 0 && 256 % (C / 4) == 0) {          // (zv_engine::zipformer's choice)
+      const long rows_per_block = 4L * (256 / (C / 4));
+      const dim3 grid((unsigned)((M + rows_per_block - 1) / rows_per_block));
+      hipLaunchKernelGGL(zv_upsample_combine_kernel, grid, dim3(256), 0, s, main, d, sc, main, B, L, dL, C, ds);
+      rec[1] = 0; rec[2] = (int)grid.x;
+    } else {
+      const dim3 grid = grid1d(M * C);
+      hipLaunchKernelGGL(zv_upsample_combine_any_kernel, grid, dim3(256), 0, s, main, d, sc, main, B, L, dL, C, ds);
+      rec[1] = 1; rec[2] = (int)grid.x;
+    }
+    ZV_LAUNCH_CHECK();
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    rec[3] = 256;
+    dev.down(a->out, o, (size_t)(M + 2 * G) * C);
+  } else if (kind == ZV_SE_MASK) {
+    ZV_REQUIRE(a->mask && a->mout, "zv_stackedge_check: the mask and its output");
+    const uint8_t* in = dev.up(a->mask, (size_t)M);
+    uint8_t* o = dev.up(a->mout, (size_t)(Md + 2 * G));
+    const dim3 grid = grid1d(Md);
+    hipLaunchKernelGGL(zv_mask_downsample_kernel, grid, dim3(256), 0, s, in, o + G, B, L, dL, ds);
+    ZV_LAUNCH_CHECK();
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    rec[2] = (int)grid.x; rec[3] = 256;
+    dev.down(a->mout, o, (size_t)(Md + 2 * G));
+  } else if (kind == ZV_SE_ENTRY) {
+    ZV_REQUIRE(a->h && a->h2 && a->ldact >= C && a->ldact % 4 == 0 && (!a->rowvec || a->rows_per_group > 0),
+               "zv_stackedge_check: stack entry writes h (src) and h2 (cur), rows of a multiple of 4");
+    const float* src = dev.up(a->x, (size_t)M * C);
+    const float* rv = a->rowvec ? dev.up(a->rowvec, (size_t)cdiv(M, a->rows_per_group) * C) : nullptr;
+    float* cur = a->out ? up32(M, nullptr) : nullptr;
+    bf16 *h = up16(a->h, M), *l = up16(a->l, M), *h2 = up16(a->h2, M), *l2 = up16(a->l2, M);
+    const dim3 grid = grid1d(M * C);
+    hipLaunchKernelGGL(zv_stack_entry_kernel, grid, dim3(256), 0, s, src, rv, cur ? cur + (size_t)G * C : nullptr,
+                       in16(h), in16(l), in16(h2), in16(l2), (long)a->ldact, M, C,
+                       rv ? a->rows_per_group : 1);
+    ZV_LAUNCH_CHECK();
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    rec[2] = (int)grid.x; rec[3] = 256;
+    if (cur) dev.down(a->out, cur, (size_t)(M + 2 * G) * C);
+    down16(a->h, h, M); down16(a->l, l, M); down16(a->h2, h2, M); down16(a->l2, l2, M);
+  } else {   // BiasNorm + bypass, in place over orig (zv_engine::layer's launch)
+    ZV_REQUIRE(a->nb && a->w && a->orig && a->out && a->h && a->ldact >= C && a->ldact % 4 == 0 &&
+                   (!a->l2 || a->h2) && (!a->rowvec || a->rows_per_group > 0),
+               "zv_stackedge_check: BiasNorm needs nb, the bypass scale, orig, out and h");
+    ZV_REQUIRE(!a->q2 || (a->h2 && a->qs2 && C % 256 == 0 && a->ldq >= C && a->ldq % MX8_KSTEP == 0),
+               "zv_stackedge_check: the fp8 copy belongs to h2, channels a multiple of 256");
+    const float* x = dev.up(a->x, (size_t)M * C);
+    const float* nb = dev.up(a->nb, (size_t)C);
+    const float* byp = dev.up(a->w, (size_t)C);
+    const float* rv = a->rowvec ? dev.up(a->rowvec, (size_t)cdiv(M, a->rows_per_group) * C) : nullptr;
+    float* o = up32(M, a->orig);
+    float* src = o + (size_t)G * C;
+    bf16 *h = up16(a->h, M), *l = up16(a->l, M), *h2 = up16(a->h2, M), *l2 = up16(a->l2, M);
+    const long ldqs = a->ldq / MX8_BLOCK;
+    uint8_t* q2 = a->q2 ? dev.up(a->q2, (size_t)(M + 2 * G) * a->ldq) : nullptr;
+    uint8_t* qs2 = a->q2 ? dev.up(a->qs2, (size_t)(M + 2 * G) * ldqs) : nullptr;
+    uint8_t* q2i = q2 ? q2 + (size_t)G * a->ldq : nullptr;
+    uint8_t* qs2i = qs2 ? qs2 + (size_t)G * ldqs : nullptr;
+    const int rpg = rv ? a->rows_per_group : 1;
+    if (C == 512) {
+      hipLaunchKernelGGL(zv_biasnorm_bypass_v_kernel<2>, dim3(cdiv(M, 8)), dim3(512), 0, s, x, src, nb, a->log_scale,
+                         byp, src, in16(h), in16(l), (float*)nullptr, in16(h2), in16(l2), (long)a->ldact, rv, rpg,
+                         M, q2i, qs2i, (long)a->ldq);
+      rec[1] = 1; rec[2] = (int)cdiv(M, 8); rec[3] = 512;
+    } else {
+      hipLaunchKernelGGL(zv_biasnorm_bypass_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, x, src, nb, a->log_scale,
+                         byp, src, in16(h), in16(l), (float*)nullptr, in16(h2), in16(l2), (long)a->ldact, rv, rpg,
+                         M, C, q2i, qs2i, (long)a->ldq);
+      rec[1] = 0; rec[2] = (int)cdiv(M, 4); rec[3] = 256;
+    }
+    ZV_LAUNCH_CHECK();
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    dev.down(a->out, o, (size_t)(M + 2 * G) * C);
+    down16(a->h, h, M); down16(a->l, l, M); down16(a->h2, h2, M); down16(a->l2, l2, M);
+    if (q2) {
+      dev.down(a->q2, q2, (size_t)(M + 2 * G) * a->ldq);
+      dev.down(a->qs2, qs2, (size_t)(M + 2 * G) * ldqs);
+    }
+  }
+  memcpy(a->launch, rec, sizeof(rec));
+  a->num_cus = zv_num_cus();
   ZV_API_END
 }
 

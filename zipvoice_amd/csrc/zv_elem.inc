@@ -216,6 +216,9 @@ __global__ __launch_bounds__(256) void zv_small_linear_rows_kernel(
 
 // ---- depthwise conv1d ("same" padding, bias) + SwooshR (zipformer.py:1672, ----
 // scaling.py:1185-1191).  in/out: bf16 hi/lo activations (B, L, C), row stride ld.
+// The four kernels below are pinned against float64 through launch_dwconv's own dispatch
+// (zv_dwconv_check, tests/test_gpu_dwconv_ref.py): every kernel-size instantiation, every
+// utterance edge, the LDS forms' tile and chunk edges.
 // One workgroup = (64 frames, 64 channels, item): the input window incl. the
 // (ks-1) halo frames is staged once in LDS as fp32, each thread then produces
 // 16 frames of one channel from registers-held taps.
@@ -509,6 +512,9 @@ static void launch_dwconv(const bf16* ih, const bf16* il, long ldin, const float
   const dim3 pgrid(C / 128, cdiv(ntile, nft), B);
 #define ZV_DWP(K) hipLaunchKernelGGL((zv_dwconv_pipe_kernel<K>), pgrid, dim3(512), 0, s, ih, ldin, w, bias, \
                                      oh, ldout, L, nft, reinterpret_cast<const bf16*>(zv_epi_zero()))
+  // (the LDS form has no k = 31 instantiation: `lds` requires ks <= 15)
+  const bool model_ks = ks == 7 || ks == 9 || ks == 15 || ks == 31;
+  const int kind = pok && model_ks ? 3 : lds && model_ks ? 2 : win && model_ks ? 1 : 0;
   if (pok && ks == 7) ZV_DWP(7);
   else if (pok && ks == 9) ZV_DWP(9);
   else if (pok && ks == 15) ZV_DWP(15);
@@ -516,12 +522,16 @@ static void launch_dwconv(const bf16* ih, const bf16* il, long ldin, const float
   else if (lds && ks == 7) ZV_DWL(7);
   else if (lds && ks == 9) ZV_DWL(9);
   else if (lds && ks == 15) ZV_DWL(15);
-  else if (lds && ks == 31) ZV_DWL(31);
   else if (win && ks == 7) ZV_DWW(7);
   else if (win && ks == 9) ZV_DWW(9);
   else if (win && ks == 15) ZV_DWW(15);
   else if (win && ks == 31) ZV_DWW(31);
   else ZV_DW(0);
+  {   // which kernel and grid (test infrastructure, zv_dwconv_check): {0 generic / 1 register-window /
+      // 2 LDS / 3 pipe, k, lo halves, fp8 copy, grid x, y, z, frame tiles per pipe chunk}
+    const dim3 gk = kind == 3 ? pgrid : kind == 2 ? dim3(C / 128, cdiv(L, DWL_FT), B) : kind == 1 ? wgrid : grid;
+    g_zv_last_launch = ZvLaunchRec{kind, ks, il ? 3 : 1, q ? 1 : 0, (int)gk.x, (int)gk.y, (int)gk.z, kind == 3 ? nft : 0};
+  }
 #undef ZV_DW
 #undef ZV_DWW
 #undef ZV_DWL

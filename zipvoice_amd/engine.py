@@ -60,7 +60,9 @@ class ZvLinearCheckArgs(ctypes.Structure):
     """zv_linear_check_args (test infrastructure; tests/test_gpu_linear_ref.py)."""
     _fields_ = [(n, ctypes.c_int) for n in ("M", "N", "K", "split", "form", "act", "rows_per_group",
                                             "rpb", "guard")] + [
-        (n, ctypes.c_void_p) for n in ("A", "W", "bias", "resid", "orig", "byp", "rowvec", "rowmask")] + [
+        (n, ctypes.c_void_p) for n in ("A", "W", "bias", "resid", "orig", "byp", "rowvec", "rowmask",
+                                       "dw_w", "dw_b")] + [
+        ("dw_ks", ctypes.c_int), ("dw_L", ctypes.c_int),
         ("C", ctypes.c_void_p), ("ldc", ctypes.c_int64),
         ("Ch", ctypes.c_void_p), ("Cl", ctypes.c_void_p), ("ldch", ctypes.c_int64),
         ("Cth", ctypes.c_void_p), ("Ctl", ctypes.c_void_p), ("ldct", ctypes.c_int64),
@@ -75,6 +77,27 @@ class ZvFfnCheckArgs(ctypes.Structure):
         ("C", ctypes.c_void_p), ("ldc", ctypes.c_int64),
         ("Ch", ctypes.c_void_p), ("Cl", ctypes.c_void_p), ("C2h", ctypes.c_void_p), ("C2l", ctypes.c_void_p),
         ("ldch", ctypes.c_int64),
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+
+
+class ZvDwconvCheckArgs(ctypes.Structure):
+    """zv_dwconv_check_args (test infrastructure; tests/test_gpu_dwconv_ref.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "L", "C", "ks", "split", "guard")] + [
+        (n, ctypes.c_void_p) for n in ("g", "w", "bias")] + [
+        ("ldin", ctypes.c_int64),
+        ("Oh", ctypes.c_void_p), ("Ol", ctypes.c_void_p), ("ldout", ctypes.c_int64),
+        ("q", ctypes.c_void_p), ("qs", ctypes.c_void_p), ("ldq", ctypes.c_int64),
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+
+
+class ZvStackedgeCheckArgs(ctypes.Structure):
+    """zv_stackedge_check_args (test infrastructure; tests/test_gpu_stackedge_ref.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kind", "B", "L", "C", "ds", "guard", "rows_per_group")] + [
+        ("log_scale", ctypes.c_float)] + [
+        (n, ctypes.c_void_p) for n in ("x", "w", "nb", "orig", "rowvec", "mask", "out", "mout",
+                                       "h", "l", "h2", "l2")] + [
+        ("ldact", ctypes.c_int64),
+        ("q2", ctypes.c_void_p), ("qs2", ctypes.c_void_p), ("ldq", ctypes.c_int64),
         ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
 
 
@@ -96,6 +119,8 @@ SIGNATURES = {
     "zv_gemm_selftest": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "zv_linear_check": (_I, [ctypes.POINTER(ZvLinearCheckArgs)]),
     "zv_ffn_check": (_I, [ctypes.POINTER(ZvFfnCheckArgs)]),
+    "zv_dwconv_check": (_I, [ctypes.POINTER(ZvDwconvCheckArgs)]),
+    "zv_stackedge_check": (_I, [ctypes.POINTER(ZvStackedgeCheckArgs)]),
     "zv_profile_report": (_I, [ctypes.c_char_p, _I]),
     "zv_host_block_count": (ctypes.c_int64, []),
     "zv_attn_fallbacks": (_I, [_P, _I, _P]),
