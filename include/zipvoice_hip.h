@@ -552,6 +552,39 @@ void zv_wavjoin_destroy(zv_wavjoin_handle h);
 int zv_wavjoin_apply(zv_wavjoin_handle h, const float* wav, int64_t wav_ld, const int32_t* lens,
                      const float* gains, int B, int C, float* out, int64_t out_ld, int64_t out_cap,
                      int64_t* out_len, int32_t* spans, void* stream);
+/* The segmented join: the B chunks form D documents, and every document is joined on its
+ * own into its own output row, so chunks of several texts share one batch (D == B: a
+ * per-row pause trim).
+ *
+ * Documents.  doc_ptr is a device array of D + 1 int32 with doc_ptr[0] = 0, doc_ptr[D] = B,
+ * non-decreasing; document d owns the consecutive chunks [doc_ptr[d], doc_ptr[d + 1]), a
+ * range that may be empty.  Frames, kept frames and the trimmed chunks y_b are as above.
+ * Join.  The rule above is applied to each document's chunks on their own, as a separate
+ * zv_wavjoin_apply over just those chunks would apply it: the first non-empty chunk of a
+ * document has F = 0 and off = 0, whatever precedes it in the batch, and the last
+ * non-empty chunk of a document gives up no tail.
+ * Output.  out: [D, C, out_ld]; row d may be written in columns [0, out_cap) only
+ * (out_cap <= out_ld).  out_len: D device int64 and always receives the true N_d.
+ * Columns [N_d, out_cap) of every row d are zero-filled; an empty document has N_d = 0 and
+ * an all-zero row.  spans: [B, 3] device int32 {m_b, off_b, F_b}, or NULL, with off_b
+ * relative to the chunk's own document row and -1 for an empty chunk.
+ * doc_ptr == NULL is allowed with D == 1 only and means one document of all B chunks:
+ * zv_wavjoin_apply(...) is zv_wavjoin_apply_docs(..., NULL, 1, ...).
+ *
+ * Rejected: a null handle, C not 1 or 2, B < 0, D < 0, D == 0 with B > 0, doc_ptr NULL
+ * with D != 1, out_cap > out_ld.  B == 0 (any D >= 0) succeeds and writes out_len[d] = 0
+ * and zero rows.  The contents of doc_ptr are a precondition (the library cannot read them
+ * without a host wait, so the caller checks them): the kernels read every bound clamped
+ * into [0, B] with hi >= lo and keep every store inside columns [0, out_cap) of a row < D
+ * and inside the scratch, whatever the array holds; the result is then unspecified.
+ * The properties of zv_wavjoin_apply hold: no atomics, every output column written exactly
+ * once, bitwise reproducible results that do not depend on the launch geometry, bit copies
+ * outside overlaps at gain 1, 64-bit positions, scratch owned by the handle (4 more bytes
+ * per chunk for its document), no host-blocking runtime call in a warm call. */
+int zv_wavjoin_apply_docs(zv_wavjoin_handle h, const float* wav, int64_t wav_ld, const int32_t* lens,
+                          const float* gains, int B, int C, const int32_t* doc_ptr, int D,
+                          float* out, int64_t out_ld, int64_t out_cap, int64_t* out_len,
+                          int32_t* spans, void* stream);
 int64_t zv_wavjoin_device_bytes(zv_wavjoin_handle h);
 
 #ifdef __cplusplus

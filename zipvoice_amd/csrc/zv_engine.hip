@@ -1825,20 +1825,32 @@ zv_wavjoin_handle zv_wavjoin_create(int frame, float thr, int keep_edge, int max
 
 void zv_wavjoin_destroy(zv_wavjoin_handle h) { delete h; }
 
-int zv_wavjoin_apply(zv_wavjoin_handle h, const float* wav, int64_t wav_ld, const int32_t* lens,
-                     const float* gains, int B, int C, float* out, int64_t out_ld, int64_t out_cap,
-                     int64_t* out_len, int32_t* spans, void* stream) {
+int zv_wavjoin_apply_docs(zv_wavjoin_handle h, const float* wav, int64_t wav_ld, const int32_t* lens,
+                          const float* gains, int B, int C, const int32_t* doc_ptr, int D,
+                          float* out, int64_t out_ld, int64_t out_cap, int64_t* out_len,
+                          int32_t* spans, void* stream) {
   ZV_API_BEGIN
   ZV_REQUIRE(h != nullptr, "null wavjoin handle");
   ZV_REQUIRE(C == 1 || C == 2, "C must be 1 or 2");
   ZV_REQUIRE(B >= 0, "B must be non-negative");
+  ZV_REQUIRE(D >= 0, "D must be non-negative");
+  ZV_REQUIRE(D > 0 || B == 0, "D must be positive when B > 0");
+  ZV_REQUIRE(doc_ptr || D == 1, "doc_ptr is NULL but D is not 1");
   ZV_REQUIRE(out_cap <= out_ld, "out_cap exceeds out_ld");
   ZV_REQUIRE(out_cap >= 0 && wav_ld >= 0 && wav_ld <= 0x7fffffffLL, "bad out_cap / wav_ld");
-  ZV_REQUIRE(out_len && (out || out_cap == 0) && ((wav && lens) || B == 0), "null argument");
+  ZV_REQUIRE((out_len || D == 0) && (out || out_cap == 0 || D == 0) && ((wav && lens) || B == 0),
+             "null argument");
   static_assert(sizeof(long) == sizeof(int64_t), "64-bit positions");
-  h->apply(wav, (long)wav_ld, lens, gains, B, C, out, (long)out_ld, (long)out_cap,
+  h->apply(wav, (long)wav_ld, lens, gains, B, C, doc_ptr, D, out, (long)out_ld, (long)out_cap,
            reinterpret_cast<long*>(out_len), spans, (hipStream_t)stream);
   ZV_API_END
+}
+
+int zv_wavjoin_apply(zv_wavjoin_handle h, const float* wav, int64_t wav_ld, const int32_t* lens,
+                     const float* gains, int B, int C, float* out, int64_t out_ld, int64_t out_cap,
+                     int64_t* out_len, int32_t* spans, void* stream) {
+  return zv_wavjoin_apply_docs(h, wav, wav_ld, lens, gains, B, C, nullptr, 1, out, out_ld, out_cap,
+                               out_len, spans, stream);
 }
 
 int64_t zv_wavjoin_device_bytes(zv_wavjoin_handle h) { return h ? (int64_t)h->bytes : 0; }

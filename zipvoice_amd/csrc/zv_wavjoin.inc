@@ -1,7 +1,8 @@
 // Long-form join for gfx950: trim the pauses of a batch of chunk waveforms and glue the
-// trimmed chunks into one waveform with linear cross-fades (zipvoice_amd/longform.py
-// WavJoiner).  No reference counterpart: the reference has no long-form path; the behaviour
-// is defined in include/zipvoice_hip.h and restated in float64 by tests/wavjoin_ref.py.
+// trimmed chunks of every document (a run of consecutive chunks, doc_ptr) into that
+// document's waveform with linear cross-fades (zipvoice_amd/longform.py WavJoiner).  No
+// reference counterpart: the reference has no long-form path; the behaviour is defined in
+// include/zipvoice_hip.h and restated in float64 by tests/wavjoin_ref.py.
 //
 // Four passes over wav [B, C, wav_ld], all memory-bound, no atomics, every result
 // independent of the launch geometry (12 B per input sample: 4 read by the energy pass,
@@ -14,16 +15,22 @@
 //            prefix sum of the kept frames' sample counts, pre [B, nfmax + 1]
 //            (pre[b, nf] = m_b).  Every thread owns a contiguous segment of frames; the
 //            segments' summaries meet in LDS.
-//   offsets  one workgroup over B: F_b, off_b, the previous non-empty chunk and the overlap
-//            with the next one; out_len and spans.
-//   gather   a thread owns 4 consecutive input samples; kept samples go to
-//            off_b + pre[b, f] + (s - f * frame).  Owner rule for an overlap: the chunk that
-//            fades in writes it (and finds the fading-out sample of the previous chunk by a
-//            binary search in that chunk's pre); a chunk skips the samples of its own tail
-//            that the next chunk owns.  Outside overlaps 4 samples of one frame move as one
-//            dwordx4 load and store (dword-aligned: row starts and destinations are
-//            arbitrary), and a gain of exactly 1 copies the bits.
-//   zero     columns [N, out_cap).
+//   offsets  one workgroup per document, over its chunks only, so the chain of non-empty
+//            chunks never crosses a document boundary: F_b, off_b (in the document's row),
+//            the previous non-empty chunk and the overlap with the next one, the chunk's
+//            document; out_len[d] and spans.
+//   gather   a thread owns 4 consecutive input samples; kept samples go to column
+//            off_b + pre[b, f] + (s - f * frame) of the chunk's document row.  Owner rule
+//            for an overlap: the chunk that fades in writes it (and finds the fading-out
+//            sample of the previous chunk by a binary search in that chunk's pre); a chunk
+//            skips the samples of its own tail that the next chunk owns.  Outside overlaps
+//            4 samples of one frame move as one dwordx4 load and store (dword-aligned: row
+//            starts and destinations are arbitrary), and a gain of exactly 1 copies the bits.
+//   zero     columns [N_d, out_cap) of every document row.
+// doc_ptr is read on the device only, so its contents cannot be rejected: every bound is
+// clamped into [0, B] with hi >= lo, and the gather pass moves a chunk only if the document
+// recorded for it is below D and owns it by those bounds, so no store leaves columns
+// [0, out_cap) of a row < D or the scratch, whatever the array holds.
 #pragma once
 
 constexpr int WJ_THREADS = 256;
@@ -33,6 +40,15 @@ typedef float wj_f32x4 __attribute__((ext_vector_type(4), aligned(4)));
 
 __device__ __forceinline__ long wj_len(const int* lens, int b, long wav_ld) {
   return min(max((long)lens[b], 0L), wav_ld);
+}
+
+// chunks [lo, hi) of document d; doc_ptr == nullptr: one document of all B chunks
+__device__ __forceinline__ void wj_doc_range(const int* doc_ptr, int d, int B, int& lo, int& hi) {
+  lo = 0; hi = B;
+  if (doc_ptr) {
+    lo = min(max(doc_ptr[d], 0), B);
+    hi = min(max(doc_ptr[d + 1], lo), B);
+  }
 }
 
 __global__ __launch_bounds__(WJ_THREADS) void zv_wavjoin_energy_kernel(
@@ -122,15 +138,17 @@ __global__ __launch_bounds__(WJ_THREADS) void zv_wavjoin_plan_kernel(
 }
 
 __global__ __launch_bounds__(WJ_THREADS) void zv_wavjoin_offsets_kernel(
-    const int* m, int B, int fade, long* off, int* F, int* Fn, int* prevc, long* out_len,
-    int* spans) {
+    const int* m, int B, const int* doc_ptr, int fade, long* off, int* F, int* Fn, int* prevc,
+    int* doc, long* out_len, int* spans) {
   __shared__ long s_off[WJ_OFF_BLOCK];
   __shared__ int s_m[WJ_OFF_BLOCK], s_F[WJ_OFF_BLOCK], s_prev[WJ_OFF_BLOCK];
-  const int t = threadIdx.x;
+  const int d = blockIdx.x, t = threadIdx.x;
+  int lo, hi;
+  wj_doc_range(doc_ptr, d, B, lo, hi);
   int p = -1, mp = 0;                                    // thread 0: the last non-empty chunk
   long offp = 0;
-  for (int b0 = 0; b0 < B; b0 += WJ_OFF_BLOCK) {
-    const int nb = min(WJ_OFF_BLOCK, B - b0);
+  for (int b0 = lo; b0 < hi; b0 += WJ_OFF_BLOCK) {
+    const int nb = min(WJ_OFF_BLOCK, hi - b0);
     for (int i = t; i < nb; i += WJ_THREADS) s_m[i] = m[b0 + i];
     __syncthreads();
     if (t == 0)
@@ -146,7 +164,7 @@ __global__ __launch_bounds__(WJ_THREADS) void zv_wavjoin_offsets_kernel(
       }
     __syncthreads();
     for (int i = t; i < nb; i += WJ_THREADS) {
-      off[b0 + i] = s_off[i]; F[b0 + i] = s_F[i]; prevc[b0 + i] = s_prev[i];
+      off[b0 + i] = s_off[i]; F[b0 + i] = s_F[i]; prevc[b0 + i] = s_prev[i]; doc[b0 + i] = d;
       if (spans) {
         int* sp = spans + 3L * (b0 + i);
         sp[0] = s_m[i]; sp[1] = (int)s_off[i]; sp[2] = s_F[i];
@@ -154,16 +172,21 @@ __global__ __launch_bounds__(WJ_THREADS) void zv_wavjoin_offsets_kernel(
     }
     __syncthreads();
   }
-  if (t == 0) *out_len = p < 0 ? 0 : offp + mp;
+  if (t == 0) out_len[d] = p < 0 ? 0 : offp + mp;
 }
 
 __global__ __launch_bounds__(WJ_THREADS) void zv_wavjoin_gather_kernel(
     const float* wav, long wav_ld, const int* lens, const float* gains, int C, int frame,
     int nfmax, int tiles, const int* pre, const int* m, const long* off, const int* F,
-    const int* Fn, const int* prevc, float* out, long out_ld, long out_cap) {
+    const int* Fn, const int* prevc, const int* doc, const int* doc_ptr, int B, int D,
+    float* out, long out_ld, long out_cap) {
   const int b = blockIdx.x / tiles;
-  const int mb = m[b];
-  if (mb == 0) return;
+  const int mb = m[b], d = doc[b];                       // d is stale if no document owns b
+  if (mb == 0 || (unsigned)d >= (unsigned)D) return;
+  int lo, hi;
+  wj_doc_range(doc_ptr, d, B, lo, hi);
+  if (b < lo || b >= hi) return;
+  out += (long)d * C * out_ld;
   const long len = wj_len(lens, b, wav_ld);
   const long s0 = ((long)(blockIdx.x % tiles) * WJ_THREADS + threadIdx.x) * 4;
   if (s0 >= len) return;
@@ -208,6 +231,7 @@ __global__ __launch_bounds__(WJ_THREADS) void zv_wavjoin_gather_kernel(
     // fade-in of this chunk over the fade-out of the previous non-empty chunk p:
     // its trimmed sample tp lies in the last frame fp with pre[p, fp] <= tp
     const int p = prevc[b];
+    if (p < 0 || Fb > m[p]) continue;                    // only with overlapping documents
     const int tp = m[p] - Fb + t;
     const int* prp = pre + (long)p * (nfmax + 1);
     long flo = 0, fhi = (wj_len(lens, p, wav_ld) + frame - 1) / frame;
@@ -225,10 +249,12 @@ __global__ __launch_bounds__(WJ_THREADS) void zv_wavjoin_gather_kernel(
 }
 
 __global__ __launch_bounds__(WJ_THREADS) void zv_wavjoin_zero_kernel(
-    const long* out_len, int C, float* out, long out_ld, long out_cap) {
-  const long N = *out_len;
-  const long i0 = ((long)blockIdx.x * WJ_THREADS + threadIdx.x) * 4;
+    const long* out_len, int C, int tiles, float* out, long out_ld, long out_cap) {
+  const int d = blockIdx.x / tiles;
+  const long N = out_len[d];
+  const long i0 = ((long)(blockIdx.x % tiles) * WJ_THREADS + threadIdx.x) * 4;
   if (i0 + 4 <= N || i0 >= out_cap) return;
+  out += (long)d * C * out_ld;
   for (int c = 0; c < C; ++c) {
     float* o = out + c * out_ld;
     if (i0 >= N && i0 + 4 <= out_cap) {
@@ -256,17 +282,18 @@ struct zv_wavjoin {
     frame = frame_; thr = thr_; keep_edge = keep_edge_; max_gap = max_gap_; fade = fade_;
   }
   void apply(const float* wav, long wav_ld, const int* lens, const float* gains, int B, int C,
-             float* out, long out_ld, long out_cap, long* out_len, int* spans, hipStream_t s) {
+             const int* doc_ptr, int D, float* out, long out_ld, long out_cap, long* out_len,
+             int* spans, hipStream_t s) {
     const long nfmax = std::max(1L, (wav_ld + frame - 1) / frame);
     const long etiles = (nfmax + WJ_THREADS / 64 - 1) / (WJ_THREADS / 64);
     const long gtiles = std::max(1L, (wav_ld + WJ_TILE - 1) / WJ_TILE);
     const long ztiles = (out_cap + WJ_TILE - 1) / WJ_TILE;
     ZV_REQUIRE(nfmax < 0x7fffffffL && B * etiles <= 0x7fffffffL && B * gtiles <= 0x7fffffffL &&
-                   ztiles <= 0x7fffffffL,
+                   ztiles <= 0x7fffffffL && D * ztiles <= 0x7fffffffL,
                "batch too large for one launch");
-    // off [B] int64 | m, F, Fn, prev [B] int32 | pre [B, nfmax + 1] int32 | flags [B, nfmax]
+    // off [B] int64 | m, F, Fn, prev, doc [B] int32 | pre [B, nfmax + 1] int32 | flags [B, nfmax]
     const size_t nB = (size_t)std::max(B, 1);
-    const size_t need = nB * 8 + 4 * nB * 4 + nB * (size_t)(nfmax + 1) * 4 + nB * (size_t)nfmax;
+    const size_t need = nB * 8 + 5 * nB * 4 + nB * (size_t)(nfmax + 1) * 4 + nB * (size_t)nfmax;
     if (need > bytes) {
       if (buf) {
         ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
@@ -278,7 +305,7 @@ struct zv_wavjoin {
     }
     long* off = reinterpret_cast<long*>(buf);
     int* m = reinterpret_cast<int*>(off + nB);
-    int *F = m + nB, *Fn = F + nB, *prevc = Fn + nB, *pre = prevc + nB;
+    int *F = m + nB, *Fn = F + nB, *prevc = Fn + nB, *doc = prevc + nB, *pre = doc + nB;
     uint8_t* flags = reinterpret_cast<uint8_t*>(pre + nB * (size_t)(nfmax + 1));
     const dim3 blk(WJ_THREADS);
     if (B > 0) {
@@ -289,18 +316,20 @@ struct zv_wavjoin {
                          keep_edge, max_gap, (int)nfmax, flags, pre, m);
       ZV_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(zv_wavjoin_offsets_kernel, dim3(1), blk, 0, s, m, B, fade, off, F, Fn,
-                       prevc, out_len, spans);
-    ZV_LAUNCH_CHECK();
+    if (D > 0) {
+      hipLaunchKernelGGL(zv_wavjoin_offsets_kernel, dim3(D), blk, 0, s, m, B, doc_ptr, fade, off,
+                         F, Fn, prevc, doc, out_len, spans);
+      ZV_LAUNCH_CHECK();
+    }
     if (B > 0 && out_cap > 0) {
       hipLaunchKernelGGL(zv_wavjoin_gather_kernel, dim3((unsigned)(B * gtiles)), blk, 0, s, wav,
                          wav_ld, lens, gains, C, frame, (int)nfmax, (int)gtiles, pre, m, off, F,
-                         Fn, prevc, out, out_ld, out_cap);
+                         Fn, prevc, doc, doc_ptr, B, D, out, out_ld, out_cap);
       ZV_LAUNCH_CHECK();
     }
-    if (out_cap > 0) {
-      hipLaunchKernelGGL(zv_wavjoin_zero_kernel, dim3((unsigned)ztiles), blk, 0, s, out_len, C,
-                         out, out_ld, out_cap);
+    if (D > 0 && out_cap > 0) {
+      hipLaunchKernelGGL(zv_wavjoin_zero_kernel, dim3((unsigned)(D * ztiles)), blk, 0, s, out_len,
+                         C, (int)ztiles, out, out_ld, out_cap);
       ZV_LAUNCH_CHECK();
     }
   }

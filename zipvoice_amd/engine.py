@@ -164,6 +164,8 @@ SIGNATURES = {
     "zv_wavjoin_destroy": (None, [_P]),
     "zv_wavjoin_apply": (_I, [_P, _P, ctypes.c_int64, _P, _P, _I, _I, _P, ctypes.c_int64,
                               ctypes.c_int64, _P, _P, _P]),
+    "zv_wavjoin_apply_docs": (_I, [_P, _P, ctypes.c_int64, _P, _P, _I, _I, _P, _I, _P,
+                                   ctypes.c_int64, ctypes.c_int64, _P, _P, _P]),
     "zv_wavjoin_device_bytes": (ctypes.c_int64, [_P]),
 }
 

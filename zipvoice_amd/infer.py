@@ -148,18 +148,12 @@ def generate_sentence(tokens: List[int], prompt_tokens: List[int], prompt_wav, m
     return wav, metrics
 
 
-@torch.inference_mode()
-def generate_batch(items: Sequence[tuple], model, vocoder,
-                   feature_extractor, num_step: int = 16, guidance_scale: float = 1.0,
-                   speed: float = 1.0, t_shift: float = 0.5, target_rms: float = 0.1,
-                   feat_scale: float = 0.1, feat_bias: float = 0.0, x0=None
-                   ) -> Tuple[List[torch.Tensor], Dict[str, float]]:
-    """Batched serving form: items = [(tokens, prompt_tokens, prompt_wav), ...] with 24 kHz
-    prompts, or (tokens, prompt_tokens, prompt_wav, prompt_sampling_rate); prompts at
-    other rates are resampled on the device, one batched call per distinct rate.
-    Each output equals what ``generate_sentence`` would produce for that item with
-    the same initial noise (per-utterance lengths and masks throughout)."""
-    dev = model.device
+def _prepare_prompts(items: Sequence[tuple], feature_extractor, target_rms: float, dev):
+    """The prompts of items = [(tokens, prompt_tokens, prompt_wav[, prompt_sampling_rate]), ...]
+    as ``generate_batch`` prepares them: one batched resample per distinct rate, host RMS
+    normalisation, one ``extract_batch``.  Returns (features (B, T, n_mels) before scale and
+    bias, frame counts (B,) on the device, the prompts' RMS before normalisation, their
+    sample counts at the model's rate)."""
     B = len(items)
     sampling_rate = feature_extractor.config.sampling_rate
     prompts = [torch.as_tensor(np.asarray(it[2]), dtype=torch.float32).reshape(-1) for it in items]
@@ -187,7 +181,37 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
         wb[i, :len(w)] = w
     lens = torch.tensor([len(w) for w in wavs])
     feats, nfr = feature_extractor.extract_batch(wb.to(dev), lens)
+    return feats, nfr, rms, [len(w) for w in wavs]
+
+
+@torch.inference_mode()
+def generate_batch(items: Sequence[tuple], model, vocoder,
+                   feature_extractor, num_step: int = 16, guidance_scale: float = 1.0,
+                   speed: float = 1.0, t_shift: float = 0.5, target_rms: float = 0.1,
+                   feat_scale: float = 0.1, feat_bias: float = 0.0, x0=None,
+                   remove_long_sil: bool = False, joiner=None
+                   ) -> Tuple[List[torch.Tensor], Dict[str, float]]:
+    """Batched serving form: items = [(tokens, prompt_tokens, prompt_wav), ...] with 24 kHz
+    prompts, or (tokens, prompt_tokens, prompt_wav, prompt_sampling_rate); prompts at
+    other rates are resampled on the device, one batched call per distinct rate.
+    Each output equals what ``generate_sentence`` would produce for that item with
+    the same initial noise (per-utterance lengths and masks throughout).
+
+    ``remove_long_sil`` (upstream ZipVoice's ``--remove-long-sil``; mono and one-channel
+    Dialog models, stereo is out of scope): every decoded row goes through
+    ``longform.WavJoiner.trim`` (``joiner``, default ``WavJoiner()``), which drops the
+    silence at its edges and cuts over-long pauses inside, with the RMS restore folded in
+    as the row's gain; each waveform is then (1, N_i) and ``wav_seconds`` / ``rtf`` use
+    the trimmed lengths."""
+    dev = model.device
+    B = len(items)
+    feats, nfr, rms, _ = _prepare_prompts(items, feature_extractor, target_rms, dev)
     prompt_features = (feats + feat_bias) * feat_scale
+    if remove_long_sil:
+        from .longform import WavJoiner
+        joiner = joiner if joiner is not None else WavJoiner()
+        gains = torch.tensor([r / target_rms if r < target_rms else 1.0 for r in rms],
+                             dtype=torch.float32).to(dev)
     torch.cuda.synchronize(dev)
     t0 = dt.datetime.now()
     pred, pred_lens, _, _ = model.sample(
@@ -197,8 +221,16 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
         x0=x0)
     out = vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale, feat_bias=feat_bias,
                                   clamp=True)
+    if remove_long_sil:
+        out, out_lens = joiner.trim(out, (pred_lens * vocoder.cfg.hop_length).to(torch.int32),
+                                    gains)
     torch.cuda.synchronize(dev)
     t = (dt.datetime.now() - t0).total_seconds()
+    if remove_long_sil:
+        ns = out_lens.tolist()
+        secs = sum(ns) / 24000
+        return ([out[i, :ns[i]].unsqueeze(0) for i in range(B)],
+                {"t": t, "wav_seconds": secs, "rtf": t / secs if secs else float("inf")})
     hop = vocoder.cfg.hop_length
     res = []
     for i in range(B):

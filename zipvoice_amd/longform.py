@@ -1,19 +1,25 @@
 """Long-form synthesis: text longer than the model speaks in one pass.
 
 The reference has no long-form path, so nothing here mirrors it; the behaviour is this
-module's own (and ``include/zipvoice_hip.h`` for the join).  Three parts:
+module's own (and ``include/zipvoice_hip.h`` for the join).  Its parts:
 
 * ``chunk_tokens`` / ``chunk_budget``: split a token list at the caller's sentence-end ids
   into chunks whose predicted duration fits the model (host, pure Python; the engine takes
   token ids and knows no tokenizer).
 * ``WavJoiner``: the engine's ``zv_wavjoin_*`` kernels: trim the pauses the model puts at
   chunk edges (and over-long pauses inside), then glue the trimmed chunks with linear
-  cross-fades, all on the device.
+  cross-fades, all on the device.  ``join_docs`` joins the chunks of several documents in
+  one call, each document into its own waveform; ``trim`` is the one-chunk-per-document
+  case, a pause trim per row.
 * ``generate_long``: prompt -> chunks -> ``model.sample`` in batches that share the one
   prompt -> vocoder -> one join.
+* ``plan_long_batch`` / ``generate_long_batch``: several texts with their own prompts; the
+  chunks of all of them are pooled into the ``model.sample`` batches, and one ``join_docs``
+  writes one waveform per text.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import datetime as dt
 import math
@@ -143,13 +149,11 @@ class WavJoiner:
         """Scratch the handles hold (0 before the first call)."""
         return sum(int(self._lib.zv_wavjoin_device_bytes(h)) for h in self._handles.values())
 
-    @torch.inference_mode()
-    def __call__(self, wavs: torch.Tensor, lens, gains=None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """wavs (B, n) or (B, C, n) fp32 (C in {1, 2}), lens (B,) sample counts (host
-        values), gains (B,) or None -> (out (C, N) on the device, spans (B, 3) int32 on the
-        device: trimmed length m_b, start off_b in ``out`` (-1 for an empty chunk), overlap
-        F_b with the previous non-empty chunk).  Allocates cap = sum(lens) columns and waits
-        for the host once, to read N."""
+    def _prepare(self, wavs, lens, gains):
+        """The arguments of one call on the device: (handle, wavs (B, C, n) fp32, host lens or
+        None for a device ``lens``, lens int32 on the device, gains fp32 on the device or
+        None).  Host values are checked; tensors already on the device are taken as they
+        are (the kernels clamp every length into [0, n]), so they cost no host wait."""
         if wavs.dim() == 2:
             wavs = wavs.unsqueeze(1)
         if wavs.dim() != 3 or wavs.shape[1] not in (1, 2):
@@ -159,16 +163,34 @@ class WavJoiner:
         h = self._handle(dev)
         wavs = wavs.to(dev, torch.float32).contiguous()
         B, C, n = wavs.shape
-        lens_host = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
-        if len(lens_host) != B or (B and (min(lens_host) < 0 or max(lens_host) > n)):
-            raise ValueError("lens must hold B sample counts in [0, n]")
-        cap = sum(lens_host)
-        ln = torch.tensor(lens_host, dtype=torch.int32, device=dev)
+        if torch.is_tensor(lens) and lens.is_cuda:
+            if lens.shape != (B,):
+                raise ValueError("lens must hold B sample counts in [0, n]")
+            lens_host, ln = None, lens.to(dev, torch.int32).contiguous()
+        else:
+            lens_host = [int(v) for v in (lens.tolist() if torch.is_tensor(lens) else lens)]
+            if len(lens_host) != B or (B and (min(lens_host) < 0 or max(lens_host) > n)):
+                raise ValueError("lens must hold B sample counts in [0, n]")
+            ln = torch.tensor(lens_host, dtype=torch.int32, device=dev)
         g = None
         if gains is not None:
             g = torch.as_tensor(gains, dtype=torch.float32).to(dev).contiguous()
             if g.shape != (B,):
                 raise ValueError("gains must have shape (B,)")
+        return h, dev, wavs, lens_host, ln, g
+
+    @torch.inference_mode()
+    def __call__(self, wavs: torch.Tensor, lens, gains=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """wavs (B, n) or (B, C, n) fp32 (C in {1, 2}), lens (B,) sample counts (host
+        values), gains (B,) or None -> (out (C, N) on the device, spans (B, 3) int32 on the
+        device: trimmed length m_b, start off_b in ``out`` (-1 for an empty chunk), overlap
+        F_b with the previous non-empty chunk).  Allocates cap = sum(lens) columns and waits
+        for the host once, to read N."""
+        if torch.is_tensor(lens):
+            lens = lens.tolist()
+        h, dev, wavs, lens_host, ln, g = self._prepare(wavs, lens, gains)
+        B, C, n = wavs.shape
+        cap = sum(lens_host)
         out = torch.empty((C, max(cap, 1)), dtype=torch.float32, device=dev)
         out_len = torch.empty(1, dtype=torch.int64, device=dev)
         spans = torch.empty((max(B, 1), 3), dtype=torch.int32, device=dev)
@@ -181,6 +203,65 @@ class WavJoiner:
         if N > cap:
             raise RuntimeError(f"joined length {N} exceeds the allocated {cap} samples")
         return out[:, :N], spans[:B]
+
+    @torch.inference_mode()
+    def join_docs(self, wavs: torch.Tensor, lens, doc_sizes, gains=None
+                  ) -> Tuple[List[torch.Tensor], torch.Tensor]:
+        """The chunks of D documents in one call (``zv_wavjoin_apply_docs``): wavs, lens and
+        gains as in ``__call__``; ``doc_sizes`` a host list of D non-negative chunk counts
+        that sum to B, document d owning the next ``doc_sizes[d]`` chunks.  Every document
+        is trimmed and joined on its own, as a separate ``__call__`` on its chunks would do
+        it.  Returns (outs: D views (C, N_d) of one (D, C, cap) device tensor, cap = the
+        largest per-document sum of lens; spans (B, 3) int32 on the device, with off_b
+        relative to the chunk's document).  Waits for the host once, to read the D lengths
+        in one transfer."""
+        if torch.is_tensor(lens):
+            lens = lens.tolist()
+        h, dev, wavs, lens_host, ln, g = self._prepare(wavs, lens, gains)
+        B, C, n = wavs.shape
+        sizes = [int(v) for v in (doc_sizes.tolist() if torch.is_tensor(doc_sizes) else doc_sizes)]
+        if any(v < 0 for v in sizes) or sum(sizes) != B:
+            raise ValueError(f"doc_sizes must hold non-negative chunk counts that sum to B = {B}, "
+                             f"got {sizes}")
+        D = len(sizes)
+        ptr = [0]
+        for v in sizes:
+            ptr.append(ptr[-1] + v)
+        cap = max([sum(lens_host[ptr[d]:ptr[d + 1]]) for d in range(D)] + [1])
+        doc_ptr = torch.tensor(ptr, dtype=torch.int32, device=dev)
+        out = torch.empty((D, C, cap), dtype=torch.float32, device=dev)
+        out_len = torch.empty(max(D, 1), dtype=torch.int64, device=dev)
+        spans = torch.empty((max(B, 1), 3), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _eng._check(self._lib.zv_wavjoin_apply_docs(
+                h, _eng._ptr(wavs), n, _eng._ptr(ln), _eng._ptr(g), B, C, _eng._ptr(doc_ptr), D,
+                _eng._ptr(out), cap, cap, _eng._ptr(out_len), _eng._ptr(spans), _eng._stream()),
+                self._lib)
+        Ns = out_len[:D].tolist()                     # the one host wait: N_d depends on the data
+        if Ns and max(Ns) > cap:
+            raise RuntimeError(f"joined length {max(Ns)} exceeds the allocated {cap} samples")
+        return [out[d, :, :Ns[d]] for d in range(D)], spans[:B]
+
+    @torch.inference_mode()
+    def trim(self, wavs: torch.Tensor, lens, gains=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """A pause trim per row: every row is its own document (D = B), so nothing is
+        cross-faded; the silence at a row's edges goes and over-long pauses inside are cut
+        (usable on decoded batches and on prompts).  wavs (B, n) or (B, C, n), lens and
+        gains as in ``__call__`` or tensors on the device -> (out of the input's shape on
+        the device, row b holding its N_b kept samples times its gain, then zeros; out_lens
+        (B,) int64 on the device).  No host wait: with ``lens`` and ``gains`` already on
+        the device nothing here blocks the host, and the lengths stay there."""
+        squeeze = wavs.dim() == 2
+        h, dev, wavs, _, ln, g = self._prepare(wavs, lens, gains)
+        B, C, n = wavs.shape
+        doc_ptr = torch.arange(B + 1, dtype=torch.int32, device=dev)
+        out = torch.empty((B, C, n), dtype=torch.float32, device=dev)
+        out_len = torch.empty(B, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _eng._check(self._lib.zv_wavjoin_apply_docs(
+                h, _eng._ptr(wavs), n, _eng._ptr(ln), _eng._ptr(g), B, C, _eng._ptr(doc_ptr), B,
+                _eng._ptr(out), n, n, _eng._ptr(out_len), None, _eng._stream()), self._lib)
+        return (out[:, 0] if squeeze else out), out_len
 
 
 # ------------------------------------------------------------------------------ pipeline
@@ -260,3 +341,143 @@ def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model
     if return_chunks:
         return out, metrics, [batch[i, :lens_host[i]] for i in range(K)], spans
     return out, metrics
+
+
+# ------------------------------------------------------------------------------ pooled
+LongPlan = collections.namedtuple("LongPlan", "chunks doc_sizes doc_of frames groups")
+
+
+def plan_long_batch(texts: Sequence[Sequence[int]], prompt_tokens_lens: Sequence[int],
+                    prompt_samples: Sequence[int], break_ids, soft_break_ids=(),
+                    max_seconds: float = 25.0, batch_size: int = 32, speed: float = 1.0,
+                    sort_by_length: bool = True, sampling_rate: int = 24000,
+                    hop: int = 256) -> LongPlan:
+    """The chunks of several texts and the ``model.sample`` calls that speak them (host only).
+
+    Text d, with a prompt of ``prompt_tokens_lens[d]`` tokens and ``prompt_samples[d]``
+    samples at ``sampling_rate``, is cut by ``chunk_budget`` and ``chunk_tokens`` as
+    ``generate_long`` cuts it.  Returns LongPlan(chunks: all chunks in join order, text by
+    text; doc_sizes: chunks per text; doc_of: the text of every chunk; frames: the total
+    frames (prompt + speech) ``model.sample`` will use for every chunk, from
+    ``feature.compute_num_frames`` and ``common.predict_features_lens``; groups: the
+    ``model.sample`` calls in order, as lists of indices into ``chunks``).
+
+    With ``sort_by_length`` the indices are sorted by ``frames`` descending (ties by index
+    ascending) and cut into consecutive groups of ``batch_size``: rows of like length share a
+    batch, so less attention and feed-forward work goes to padding, and the first call has
+    the largest shape, so the engine's workspace grows once.  Without it the groups are
+    consecutive in join order; for a single text these are ``generate_long``'s groups."""
+    from .common import predict_features_lens
+    from .feature import compute_num_frames
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1")
+    if not len(texts) == len(prompt_tokens_lens) == len(prompt_samples):
+        raise ValueError("texts, prompt_tokens_lens and prompt_samples must have one entry per "
+                         "text")
+    chunks: List[List[int]] = []
+    doc_sizes, doc_of = [], []
+    for d, text in enumerate(texts):
+        try:
+            budget = chunk_budget(int(prompt_tokens_lens[d]),
+                                  int(prompt_samples[d]) / sampling_rate, max_seconds, speed)
+        except ValueError as e:
+            raise ValueError(f"text {d}: {e}") from None
+        cs = chunk_tokens(text, break_ids, budget, soft_break_ids)
+        if not cs:
+            raise ValueError(f"text {d}: no tokens to synthesise")
+        chunks += cs
+        doc_sizes.append(len(cs))
+        doc_of += [d] * len(cs)
+    frames: List[int] = []
+    if chunks:
+        P = torch.tensor([compute_num_frames(int(prompt_samples[d]), hop) for d in doc_of],
+                         dtype=torch.int64)
+        ptl = torch.tensor([int(prompt_tokens_lens[d]) for d in doc_of], dtype=torch.int64)
+        tl = torch.tensor([len(c) for c in chunks], dtype=torch.int64)
+        frames = [int(v) for v in predict_features_lens(P, ptl, tl, speed).tolist()]
+    order = list(range(len(chunks)))
+    if sort_by_length:
+        order.sort(key=lambda i: (-frames[i], i))
+    groups = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+    return LongPlan(chunks, doc_sizes, doc_of, frames, groups)
+
+
+@torch.inference_mode()
+def generate_long_batch(requests: Sequence[tuple], model, vocoder, feature_extractor, break_ids,
+                        soft_break_ids=(), max_seconds: float = 25.0, batch_size: int = 32,
+                        joiner: Optional[WavJoiner] = None, x0=None, return_chunks: bool = False,
+                        sort_by_length: bool = True, num_step: int = 16,
+                        guidance_scale: float = 1.0, speed: float = 1.0, t_shift: float = 0.5,
+                        target_rms: float = 0.1, feat_scale: float = 0.1, feat_bias: float = 0.0):
+    """Several texts of any length, each with its own prompt, with their chunks pooled into
+    shared ``model.sample`` batches (mono and one-channel Dialog models; stereo is out of
+    scope).
+
+    requests = [(tokens, prompt_tokens, prompt_wav), ...] with prompts at the model's rate, or
+    (tokens, prompt_tokens, prompt_wav, prompt_sampling_rate).  The prompts are prepared as
+    ``infer.generate_batch`` prepares its items (one batched resample per distinct rate, host
+    RMS normalisation, one ``extract_batch``); ``plan_long_batch`` cuts the texts and forms
+    the groups; every group is one ``model.sample`` call whose rows carry their own request's
+    prompt features, prompt length and prompt tokens (``x0``: None, or one initial-noise
+    tensor per group in plan order), then ``vocoder.decode_features``; the decoded rows go
+    into one (K, n) batch in join order, and one ``WavJoiner.join_docs`` call trims and joins
+    them per request, with each request's RMS restore folded in as its chunks' gain.
+    Returns (a list of R waveforms (1, N_d) on the device, metrics with t, wav_seconds, rtf,
+    num_chunks, num_batches, num_requests); with ``return_chunks`` also the per-chunk
+    waveforms in join order (untrimmed, before the gain), the joiner's spans and the plan."""
+    from .infer import _prepare_prompts
+    dev = model.device
+    R = len(requests)
+    if R == 0:
+        raise ValueError("no requests to synthesise")
+    sampling_rate = feature_extractor.config.sampling_rate
+    feats, nfr, rms, nsamp = _prepare_prompts(requests, feature_extractor, target_rms, dev)
+    prompt_features = (feats + feat_bias) * feat_scale
+    plan = plan_long_batch([r[0] for r in requests], [len(r[1]) for r in requests], nsamp,
+                           break_ids, soft_break_ids, max_seconds, batch_size, speed,
+                           sort_by_length, sampling_rate, feature_extractor.config.hop_length)
+    if x0 is not None and len(x0) != len(plan.groups):
+        raise ValueError(f"x0 must hold one tensor per sample() call ({len(plan.groups)}), got "
+                         f"{len(x0)}")
+    joiner = joiner if joiner is not None else WavJoiner()
+    hop = vocoder.cfg.hop_length
+    K = len(plan.chunks)
+    P = [int(v) for v in nfr.tolist()]
+
+    torch.cuda.synchronize(dev)
+    t0 = dt.datetime.now()
+    wavs, lens, rows = [], [], []
+    for gi, grp in enumerate(plan.groups):
+        docs = [plan.doc_of[i] for i in grp]
+        di = torch.tensor(docs, dtype=torch.int64, device=dev)
+        pred, pred_lens, _, _ = model.sample(
+            tokens=[plan.chunks[i] for i in grp], prompt_tokens=[requests[d][1] for d in docs],
+            prompt_features=prompt_features.index_select(0, di)[:, :max(P[d] for d in docs)]
+            .contiguous(),
+            prompt_features_lens=nfr.index_select(0, di), speed=speed, t_shift=t_shift,
+            duration="predict", num_step=num_step, guidance_scale=guidance_scale,
+            x0=None if x0 is None else x0[gi])
+        wavs.append(vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale,
+                                            feat_bias=feat_bias, clamp=True))
+        lens.append(pred_lens)
+        rows.append(torch.tensor(grp, dtype=torch.int64, device=dev))
+    n = max(x.shape[1] for x in wavs)
+    batch = torch.zeros((K, n), dtype=torch.float32, device=dev)
+    for x, r in zip(wavs, rows):                      # group order -> join order
+        batch[:, :x.shape[1]].index_copy_(0, r, x)
+    lens_dev = torch.empty(K, dtype=torch.int64, device=dev).index_copy_(
+        0, torch.cat(rows), torch.cat(lens).to(torch.int64))
+    lens_host = [int(v) * hop for v in lens_dev.tolist()]
+    gains = None
+    if any(r < target_rms for r in rms):
+        gains = [rms[d] / target_rms if rms[d] < target_rms else 1.0 for d in plan.doc_of]
+    outs, spans = joiner.join_docs(batch, lens_host, plan.doc_sizes, gains)
+    torch.cuda.synchronize(dev)
+    t = (dt.datetime.now() - t0).total_seconds()
+    secs = sum(o.shape[1] for o in outs) / sampling_rate
+    metrics = {"t": t, "wav_seconds": secs, "rtf": t / secs if secs else float("inf"),
+               "num_chunks": K, "num_batches": len(plan.groups), "num_requests": R}
+    if return_chunks:
+        return outs, metrics, [batch[i, :lens_host[i]] for i in range(K)], spans, plan
+    return outs, metrics
