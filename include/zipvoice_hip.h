@@ -305,6 +305,62 @@ typedef struct {
 } zv_stackedge_check_args;
 int zv_stackedge_check(zv_stackedge_check_args* a);
 
+/* The BigVGAN kernels one at a time, and one AMP step, through the launches and weight relayouts that
+ * zv_bigvgan's finalize / decode use (test infrastructure: pins csrc/zv_bigvgan.inc, the implicit-conv
+ * GEMM and the conv_pre im2col against float64 in tests/test_gpu_bigvgan_ref.py; builds no zv_bigvgan;
+ * synchronous).  split 1 / 3: 16-bit operands without / with their lo halves.  A stage stream holds
+ * utterance b in rows b * Lp + [0, Lmax), Lp = round_up(Lmax + halo, 8); halo is a positive multiple
+ * of 8.  lens (B) or NULL; an utterance's length is min(lens[b] * scale, Lmax).  fp32 outputs have
+ * guard rows only, 16-bit ones the row stride stated; all are canary-filled by the caller, and what
+ * the caller puts in rows / columns the kernel leaves alone comes back as it was.  Everything the
+ * call allocates besides (16-bit operands, their padding columns and halo rows, fp32 scratch) starts
+ * from a finite, non-zero pattern seeded by `stale`, never zeros: a result that depends on unwritten
+ * memory changes with the seed.  Non-finite stale data is outside the kernels' contract.
+ *   ZV_BV_FILTER  out = the BvFilter (up_even[6], up_odd[6], down[12]) of the 12 taps `taps`, or of
+ *                 the kaiser-sinc filter when taps is NULL
+ *   ZV_BV_ACT     zv_bv_act_kernel<mode> (0 / 2): x (B * Lp, C), alpha, ibeta (C), taps or NULL ->
+ *                 mode 0: out (guard + B * Lp + guard, C); mode 2: oh / ol (guard + halo + B * Lp +
+ *                 halo + guard, round_up(C, 32)): the operand as decode allocates it, both outer halos
+ *                 included (the kernel never writes the trailing one)
+ *   ZV_BV_CONV    w (Cout, C, ks), bias, dilation d; ah / al (halo + B * Lp + halo, round_up(C, 32)):
+ *                 the operand with its halos; resid (B * Lp, Cout) or NULL -> out (guard + B * Lp +
+ *                 guard, Cout), through the Conv1d relayout and the implicit-conv dispatch
+ *   ZV_BV_CONVT   ConvTranspose1d (k = ks, stride u, padding (k - u) / 2) of utterances of Lmax frames
+ *                 at rows b * Ls: flag 1: x (B * Ls, C), w (C, Cout, k) through the relayout and the
+ *                 plain GEMM; flag 0: x = P (B * Ls, k * Cout), the gather alone; bias (Cout), scale =
+ *                 the input lengths' scale -> out (guard + B * Lo + guard, Cout), Lo = round_up(Lmax *
+ *                 u + halo, 8)
+ *   ZV_BV_AVG     (x + x1 + x2) / n over M = B * Lmax rows of C -> out (guard + M + guard, C) and
+ *                 oh / ol (guard + M + guard, ld) where given
+ *   ZV_BV_POST    conv_post + clamp (flag 0) / tanh (flag 1): x (B * Ls, C), w (C, 7), bias0 -> out
+ *                 (guard + B * Lmax + guard); fails when the LDS window exceeds 64 KiB
+ *   ZV_BV_IM2COL  zv_voc_im2col_kernel: x (B, C, Lmax) (layout 0) or (B, Lmax, C) (1), div, sub ->
+ *                 oh / ol (guard + B * Lmax + guard, round_up(C * ks, 64)); flag 1: then conv_pre's
+ *                 GEMM with w (Cout, C, ks), bias -> out (guard + B * Lmax + guard, Cout)
+ *   ZV_BV_STEP    one AMP step as decode runs it: out = x + conv2(act2(conv1_d(act1(x)))), x (B * Lp, C),
+ *                 alpha / ibeta, w / bias (conv1, dilation d), alpha2 / ibeta2, w2 / bias2 (conv2)
+ *                 -> out (guard + B * Lp + guard, C); rows outside [0, len) are unspecified
+ * launch: the last GEMM's record as zv_linear_check's, with launch[5] = its K step (0: no GEMM). */
+enum zv_bigvgan_check_kind { ZV_BV_FILTER = 0, ZV_BV_ACT = 1, ZV_BV_CONV = 2, ZV_BV_CONVT = 3, ZV_BV_AVG = 4,
+                             ZV_BV_POST = 5, ZV_BV_IM2COL = 6, ZV_BV_STEP = 7 };
+typedef struct {
+  int kind, split, mode, guard;
+  int B, Lmax, Ls, halo, scale;
+  int C, Cout, ks, d, u, n, layout, flag;
+  float div, sub, bias0;
+  unsigned stale;
+  const int* lens;
+  const float* x; const float* x1; const float* x2;
+  const float* w; const float* bias; const float* alpha; const float* ibeta;
+  const float* w2; const float* bias2; const float* alpha2; const float* ibeta2;
+  const float* taps; const float* resid;
+  const uint16_t* ah; const uint16_t* al;
+  float* out; uint16_t* oh; uint16_t* ol; int64_t ld;
+  int launch[8];
+  int num_cus;
+} zv_bigvgan_check_args;
+int zv_bigvgan_check(zv_bigvgan_check_args* a);
+
 /* Attention plan (host only, no GPU; test infrastructure): the LDS bytes of the fused
  * attention consumers a layer of sequence length L would launch — SelfAttention (sa_plo < 0:
  * the plain kernel, 0 / 1: the Toeplitz kernel without / with the table's lo half),

@@ -1,7 +1,8 @@
 """Float64 references for the engine's linear and fused FeedForward kernels (csrc/zv_gemm.inc,
 zv_gemm256.inc, zv_ffn.inc), the ConvolutionModule's depthwise conv (zv_elem.inc's four kernels and
-the fused GLU + conv launch) and the kernels at the stack boundaries (the sections at the end, with
-their case lists, which the CPU and the GPU tests share); a helper, not a test.  numpy only.
+the fused GLU + conv launch) and the kernels at the stack boundaries (with their case lists, which the CPU and the GPU tests share),
+and the BigVGAN kernels with the implicit-conv GEMM (the last section; its case lists are in
+tests/bigvgan_cases.py); a helper, not a test.  numpy only.
 
 Number formats: the 16-bit operand format of a library is "bf16" (8 significant bits) or "f16"
 (IEEE half, 11); round16 is round-to-nearest-even from float64, split16 the engine's hi / lo pair.
@@ -666,3 +667,327 @@ def upsample_combine_ref(orig, d, sc, B, L, ds, exact=False):
 def mask_downsample_ref(mask, B, L, ds):
     """mask[..., ::ds] (zipformer.py:857-858)."""
     return mask.reshape(B, L)[:, ::ds].reshape(-1)
+
+
+# --------------------------------------------------------------------------- BigVGAN
+# (csrc/zv_bigvgan.inc's kernels, the implicit-conv GEMM and conv_pre's im2col, one launch at a time
+# through zv_bigvgan_check; tests/test_gpu_bigvgan_ref.py.)  Every reference handles each utterance
+# on its own: raggedness is "decode this utterance alone".  A stage stream holds utterance b in rows
+# b * Lp + [0, Lmax), Lp = round_up(Lmax + halo, 8); its length is min(lens[b] * scale, Lmax).
+#
+# Classes and bounds (u = 2^-24; "2 u" carries dot_tol's factor 2 for an FMA chain in any order):
+#  ACT   exact: small-integer x, the dyadic taps BV_TAPS_EXACT, ibeta = 0 (the sine is evaluated and
+#        multiplied by 0): every partial sum is an fp32 value (asserted), tolerance 0; the 16-bit
+#        copies equal split16 of it.
+#        general: y = 2x upsample, 6-term FMA chain: dy = 6 * 2u * sum|f||x| (+ the input's own
+#        uncertainty through sum|f|); t = sin^2(a y): dt = 2 |s| a dy + (a dy)^2 + E_TERM, where
+#        E_TERM = BV_ETERM[class] is the measured error of the kernel's sin^2(a y) at an exact y
+#        (the fp32 product, the hardware sine behind __sinf and the square), 2x the measured maximum
+#        over the class's argument range; v = y + ib t: dv = dy + ib dt + 2u (ib t) + 2u |v|;
+#        z = 12-term chain: dz = sum|d| dv + 12 * 2u * sum|d||v|.
+#  CONV  exact: dyadic operands, assert_exact_dot; general: dot_tol with K = ks * Cp plus the
+#        epilogue's roundings (std_epilogue's count).
+#  CONVT gather alone: small integers, exact.  With the GEMM: per gathered term dot_tol of P plus one
+#        rounding of the running sum, one more for the bias.
+#  POST  clamp: (7 C + 2) u (sum|w||a| + |bias|); tanh: that bound through tanh's slope (<= 1) plus
+#        TRANS_FACTOR * ERR_TANH.
+#  AVG / IM2COL: fp32 numpy in the kernel's operation order, one rounding (u) per operation allowed.
+# The sine term's allowance was measured on an MI355X through ZV_BV_ACT with a one-tap filter
+# (z[t] = 2 x[t] + ib sin^2(2 a x[t]), a single evaluation per output; profiles/bigvgan_ref_pin.txt).
+BV_TAPS_EXACT = np.array([1, -2, 3, -4, 5, 6, 7, -3, 2, -1, 4, -5]) / 16.0
+BV_ARG_GENERAL = 16.0                  # |alpha y| of the general class, radians
+BV_ARG_WIDE = 64 * 2 * np.pi           # ... of the wide class: 64 turns
+# |error| of the kernel's sin^2(alpha y) for an exact y, measured: 1.30e-6 up to 16 rad, 3.50e-5 up to
+# 64 turns (it grows with the argument: the fp32 product alpha y and its conversion to turns each
+# round at 2^-24 |arg|); the allowance is twice that
+BV_ETERM = {"general": 2 * 1.30e-6, "wide": 2 * 3.50e-5}
+
+
+def encode16(x, fmt):
+    """float64 values that are numbers of the format -> uint16 bit patterns (decode16's inverse)."""
+    x = np.asarray(x, np.float64)
+    assert np.array_equal(round16(x, fmt), x), "not values of the format"
+    if fmt == "f16":
+        return x.astype(np.float16).view(np.uint16)
+    return (x.astype(np.float32).view(np.uint32) >> 16).astype(np.uint16)
+
+
+def bv_rows(Lmax, halo):
+    return -(-(Lmax + halo) // 8) * 8
+
+
+def bv_lens(lens, scale, Lmax, B):
+    return [Lmax if lens is None else min(int(lens[b]) * scale, Lmax) for b in range(B)]
+
+
+def bv_upsample(x, f, absf=False):
+    """UpSample1d(2) of one utterance x (T, C): replicate pad 5, 2 * conv_transpose1d(stride 2) with
+    the 12 taps, crop 15 at both ends -> (2 T, C).  Plain loops over the taps."""
+    T = x.shape[0]
+    xp = np.concatenate([np.repeat(x[:1], 5, 0), x, np.repeat(x[-1:], 5, 0)], 0)
+    full = np.zeros((2 * (T + 10 - 1) + 12, x.shape[1]))
+    for j in range(12):                                 # frame i lands on sample 2 i + j
+        full[j:j + 2 * (T + 10):2] += xp * (abs(f[j]) if absf else f[j])
+    return 2.0 * full[15:full.shape[0] - 15]
+
+
+def bv_downsample(y, f, absf=False):
+    """DownSample1d(2) of one utterance y (2 T, C): replicate pad (5, 6), stride-2 correlation."""
+    T = y.shape[0] // 2
+    yp = np.concatenate([np.repeat(y[:1], 5, 0), y, np.repeat(y[-1:], 6, 0)], 0)
+    z = np.zeros((T, y.shape[1]))
+    for j in range(12):
+        z += yp[j:j + 2 * T:2] * (abs(f[j]) if absf else f[j])
+    return z
+
+
+def bv_filter_ref(f):
+    """The kernel's polyphase arguments, derived from the transposed convolution itself: the
+    response of bv_upsample to a unit impulse at frame p gives the coefficient of x[p] in every
+    y[s].  up_even[m] multiplies x[t + m - 3] in y[2 t], up_odd[m] multiplies x[t + m - 2] in
+    y[2 t + 1]; down = the taps."""
+    f = np.asarray(f, np.float64)
+    p, T = 8, 17
+    imp = np.zeros((T, 1))
+    imp[p] = 1.0
+    y = bv_upsample(imp, f)[:, 0]
+    even = [y[2 * (p - (m - 3))] for m in range(6)]
+    odd = [y[2 * (p - (m - 2)) + 1] for m in range(6)]
+    # every other coefficient of the response is covered by the 6 + 6: nothing is left out
+    assert np.isclose(sum(even) + sum(odd), y.sum())
+    return np.array(even + odd + list(f))
+
+
+def bv_act_ref(x, lens, scale, B, Lmax, Lp, alpha, ibeta, f, klass="general", tol_x=None, bug=None):
+    """Activation1d(SnakeBeta) over a stage stream x (B * Lp, C) -> (z, tol) (B * Lp, C), zero
+    outside each utterance's [0, len).  alpha = e^log_alpha, ibeta = 1 / (e^log_beta + 1e-9) as the
+    kernel takes them.  klass "exact": asserts every partial result is an fp32 value, tol 0.
+    bug: a deliberate off-by-one for the visibility tests ("clamp": the replicate clamp reaches
+    frame len instead of len - 1; "neighbour": utterance b reads utterance b - 1's last frame in
+    place of its own first)."""
+    C = x.shape[1]
+    z, tol = np.zeros((B * Lp, C)), np.zeros((B * Lp, C))
+    ls = bv_lens(lens, scale, Lmax, B)
+    u2 = 2.0 ** -23
+    for b in range(B):
+        n = ls[b]
+        if n == 0:
+            continue
+        xs = x[b * Lp:b * Lp + n].copy()
+        tx = np.zeros_like(xs) if tol_x is None else tol_x[b * Lp:b * Lp + n]
+        if bug == "clamp":
+            xs = x[b * Lp:b * Lp + n + 1].copy()      # the clamp's last frame is row len
+        if bug == "neighbour" and b > 0:
+            xs[0] = x[b * Lp - 1]
+        y = bv_upsample(xs, f)
+        if bug == "clamp":
+            y = y[:2 * n]
+            xs = xs[:n]
+        ymag = bv_upsample(np.abs(xs), f, True)
+        if klass == "exact":
+            assert_fp32_exact(y, "upsampled y")
+            assert ymag.max() / (_lsb(xs) * _lsb(2 * f)) < 2.0 ** 24
+        dy = 6 * u2 * ymag + bv_upsample(tx, f, True)
+        arg = y * alpha
+        s = np.sin(arg)
+        v = y + ibeta * s * s
+        if klass == "exact":
+            assert np.all(ibeta == 0)
+            dv = np.zeros_like(v)
+        else:
+            ds = alpha * dy
+            ds2 = 2 * np.abs(s) * ds + ds * ds + BV_ETERM[klass]
+            dv = dy + ibeta * ds2 + u2 * ibeta * s * s + u2 * np.abs(v)
+        zz = bv_downsample(v, f)
+        zmag = bv_downsample(np.abs(v), f, True)
+        if klass == "exact":
+            assert_fp32_exact(zz, "z")
+            assert zmag.max() / (_lsb(v) * _lsb(f)) < 2.0 ** 24
+            dz = np.zeros_like(zz)
+        else:
+            dz = bv_downsample(dv, f, True) + 12 * u2 * zmag
+        z[b * Lp:b * Lp + n], tol[b * Lp:b * Lp + n] = zz, dz
+    return z, tol
+
+
+def bv_conv_cols(a, n, ks, d, Cp):
+    """The im2col matrix of one utterance's n valid frames a (n, C): (n, ks * Cp), zeros outside
+    [0, n) and in the padded channels; tap-major like the GEMM's K."""
+    C = a.shape[1]
+    pad = d * (ks - 1) // 2
+    cols = np.zeros((n, ks * Cp))
+    for tap in range(ks):
+        for t in range(n):
+            s = t + tap * d - pad
+            if 0 <= s < n:
+                cols[t, tap * Cp:tap * Cp + C] = a[s]
+    return cols
+
+
+def bv_conv_wmat(w, Cp):
+    """(Cout, Cin, ks) -> (Cout, ks * Cp), [o][tap * Cp + c]: what the reference's conv multiplies
+    against bv_conv_cols (written from the definition, not from the engine's relayout)."""
+    Cout, Cin, ks = w.shape
+    m = np.zeros((Cout, ks * Cp))
+    for tap in range(ks):
+        m[:, tap * Cp:tap * Cp + Cin] = w[:, :, tap]
+    return m
+
+
+def bv_conv_ref(a, w, bias, d, lens, scale, B, Lmax, Lp, split, fmt, resid=None, klass="general", tol_a=None,
+                bug=None):
+    """Conv1d (dilation d, "same" zero padding inside each utterance) of the stream a (B * Lp, C)
+    as the split kernel multiplies it (operands / dot_kernel) -> (out, tol, valid mask) with
+    out (B * Lp, Cout); rows outside [0, len) are left 0 and are not part of the contract.
+    tol_a: uncertainty of the operand's value (STEP), carried through sum |w|.
+    bug "neighbour": the zero padding replaced by the stream's own rows beyond the utterance."""
+    Cout, C, ks = w.shape
+    Cp = -(-C // 32) * 32
+    out, tol = np.zeros((B * Lp, Cout)), np.zeros((B * Lp, Cout))
+    valid = np.zeros(B * Lp, bool)
+    wm = bv_conv_wmat(w, Cp)
+    ls = bv_lens(lens, scale, Lmax, B)
+    for b in range(B):
+        n = ls[b]
+        if n == 0:
+            continue
+        r0 = b * Lp
+        cols = bv_conv_cols(a[r0:r0 + n], n, ks, d, Cp)
+        if bug == "neighbour":
+            pad = d * (ks - 1) // 2
+            ext = np.zeros((n + 2 * pad, C))
+            lo, hi = max(r0 - pad, 0), min(r0 + n + pad, a.shape[0])
+            ext[lo - (r0 - pad):hi - (r0 - pad)] = a[lo:hi]
+            cols = bv_conv_cols(ext, n + 2 * pad, ks, d, Cp)[pad:pad + n]
+        As, Ws = operands(cols, wm, split, fmt)
+        acc = assert_exact_dot(As, Ws) if klass == "exact" else dot_kernel(As, Ws)
+        rs = None if resid is None else resid[r0:r0 + n]
+        v, mag, nops = std_epilogue(acc, bias, resid=rs, exact=klass == "exact")
+        out[r0:r0 + n] = v
+        valid[r0:r0 + n] = True
+        if klass != "exact":
+            t = dot_tol(cols, wm, split) + 2 * nops * U32 * mag
+            if tol_a is not None:
+                t = t + bv_conv_cols(tol_a[r0:r0 + n], n, ks, d, Cp) @ np.abs(wm).T
+            tol[r0:r0 + n] = t
+    return out, tol, valid
+
+
+def bv_convt_ref(x, w, bias, u, lens, scale, B, Lin, Lin_s, Lo_s, split=None, fmt=None, klass="general",
+                 bug=None):
+    """ConvTranspose1d (Cin, Cout, k), stride u, padding (k - u) / 2, of each utterance's len_in
+    frames alone: out[t] = bias + sum over (s, j) with s u + j - pad = t of x[s] . w[:, :, j], for
+    t < len_in u; 0 beyond -> (out, tol) (B * Lo_s, Cout).  split None: x and w as they are (the
+    gather's exact class feeds products P); else the operands' roundings.
+    bug "le": frame len_in (the next row of the stream) is gathered too."""
+    Cin, Cout, k = w.shape
+    pad = (k - u) // 2
+    out, tol = np.zeros((B * Lo_s, Cout)), np.zeros((B * Lo_s, Cout))
+    ls = bv_lens(lens, scale, Lin, B)
+    for b in range(B):
+        n = ls[b]
+        nsrc = n + 1 if (bug == "le" and b * Lin_s + n < x.shape[0]) else n
+        xs = x[b * Lin_s:b * Lin_s + nsrc]
+        acc, mag, cnt = np.zeros((n * u, Cout)), np.zeros((n * u, Cout)), np.zeros((n * u, 1))
+        terr = np.zeros((n * u, Cout))
+        for j in range(k):
+            wj = w[:, :, j].T                                  # (Cout, Cin)
+            if split is None:
+                p = xs @ wj.T
+                pt = np.zeros_like(p)
+            else:
+                As, Ws = operands(xs, wj, split, fmt)
+                p = assert_exact_dot(As, Ws) if klass == "exact" else dot_kernel(As, Ws)
+                pt = np.zeros_like(p) if klass == "exact" else dot_tol(xs, wj, split)
+            for s in range(nsrc):
+                t = s * u + j - pad
+                if 0 <= t < n * u:
+                    acc[t] += p[s]
+                    mag[t] += np.abs(p[s])
+                    terr[t] += pt[s]
+                    cnt[t] += 1
+        v = acc + bias
+        if klass == "exact":
+            assert_fp32_exact(v, "convt"), assert_fp32_exact(mag + np.abs(bias), "convt partial sums")
+        out[b * Lo_s:b * Lo_s + n * u] = v
+        tol[b * Lo_s:b * Lo_s + n * u] = 0 if klass == "exact" else terr + (cnt + 1) * 2 * U32 * (mag + np.abs(bias))
+    return out, tol
+
+
+def bv_post_ref(a, w, bias, lens, scale, B, Lmax, Ls, use_tanh, klass="general", bug=None):
+    """conv_post (C -> 1, 7 taps, zero padding inside [0, len)) + clamp(-1, 1) / tanh -> (wav, tol)
+    (B * Lmax,); 0 for t >= len.  w (C, 7).  bug "short": the window ends one frame early."""
+    C = a.shape[1]
+    wav, tol = np.zeros(B * Lmax), np.zeros(B * Lmax)
+    ls = bv_lens(lens, scale, Lmax, B)
+    for b in range(B):
+        n = ls[b]
+        for t in range(n):
+            acc = mag = 0.0
+            for tap in range(7):
+                s = t + tap - 3
+                if 0 <= s < (n - 1 if bug == "short" else n):
+                    acc += float(a[b * Ls + s] @ w[:, tap])
+                    mag += float(np.abs(a[b * Ls + s]) @ np.abs(w[:, tap]))
+            pre = acc + bias
+            if klass == "exact":
+                assert_fp32_exact(np.array([pre, mag + abs(bias)]), "post")
+            tp = 0.0 if klass == "exact" else (7 * C + 2) * U32 * (mag + abs(bias))
+            if use_tanh:
+                wav[b * Lmax + t], tol[b * Lmax + t] = np.tanh(pre), tp + TRANS_FACTOR * ERR_TANH
+            else:
+                wav[b * Lmax + t], tol[b * Lmax + t] = min(max(pre, -1.0), 1.0), tp
+    return wav, tol
+
+
+def bv_avg_ref(ys):
+    """(y0 + y1 + y2) / n in the kernel's order -> (value, tol): one rounding per operation."""
+    s, mag = ys[0].copy(), np.abs(ys[0])
+    for y in ys[1:]:
+        s, mag = s + y, mag + np.abs(y)
+    n = len(ys)
+    return s / n, n * U32 * mag
+
+
+def im2col_ref(x, layout, div, sub, lens, B, T, C, ks):
+    """zv_voc_im2col_kernel: v = x / div - sub; A[b T + t][tap C + c] = v[b, c, t + tap - ks // 2],
+    0 where the source frame is outside [0, len_b) -> (A (B * T, ks * C), tol, zero mask)."""
+    x3 = np.asarray(x, np.float64).reshape((B, C, T) if layout == 0 else (B, T, C))
+    if layout == 0:
+        x3 = x3.transpose(0, 2, 1)
+    A, tol = np.zeros((B * T, ks * C)), np.zeros((B * T, ks * C))
+    zero = np.ones((B * T, ks * C), bool)
+    for b in range(B):
+        n = T if lens is None else int(lens[b])
+        for t in range(T):
+            for tap in range(ks):
+                ts = t + tap - ks // 2
+                if 0 <= ts < n:
+                    A[b * T + t, tap * C:(tap + 1) * C] = x3[b, ts] / div - sub
+                    tol[b * T + t, tap * C:(tap + 1) * C] = 2 * U32 * (np.abs(x3[b, ts] / div) + abs(sub))
+                    zero[b * T + t, tap * C:(tap + 1) * C] = False
+    return A, tol, zero
+
+
+def bv_operand_tol(z, tol, split, fmt):
+    """How far the value a 16-bit operand holds may be from the value the reference's operand holds,
+    when the fp32 value behind it is within tol of z.  split 1: nothing unless tol straddles a
+    rounding boundary, then one 16-bit ulp; split 3: tol plus the pair's own resolution, 2^-(2 p)
+    relative (|x - hi| <= 2^-p |x|, and lo rounds that remainder to p bits)."""
+    if split == 1:
+        amb = round16(z - tol, fmt) != round16(z + tol, fmt)
+        return np.where(amb, ulp16(np.abs(z) + tol, fmt), 0.0)
+    return tol + 2.0 ** (-2 * PREC[fmt]) * np.abs(z)
+
+
+def bv_step_ref(c, split, fmt):
+    """One AMP step, the references composed: out = x + conv2(act2(conv1_d(act1(x)))) -> (out, tol,
+    valid rows).  The bounds add up: each activation's own bound, its operand's rounding, carried
+    through the conv's sum |w|, the conv's dot_tol, and so on through the second pair."""
+    B, Lmax, Lp, d, lens = c["B"], c["Lmax"], c["Lp"], c["d"], c["lens"]
+    z1, t1 = bv_act_ref(c["x"], lens, 1, B, Lmax, Lp, c["alpha"], c["ibeta"], c["f"])
+    h1, th1 = bv_conv_ref(z1, c["w"], c["bias"], d, lens, 1, B, Lmax, Lp, split, fmt,
+                          tol_a=bv_operand_tol(z1, t1, split, fmt))[:2]
+    z2, t2 = bv_act_ref(h1, lens, 1, B, Lmax, Lp, c["alpha2"], c["ibeta2"], c["f"], tol_x=th1)
+    return bv_conv_ref(z2, c["w2"], c["bias2"], 1, lens, 1, B, Lmax, Lp, split, fmt, resid=c["x"],
+                       tol_a=bv_operand_tol(z2, t2, split, fmt))

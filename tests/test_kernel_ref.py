@@ -3,7 +3,9 @@ test_gpu_linear_ref.py / test_gpu_ffn_ref.py rely on: the 16-bit rounding helper
 the exact class's exactness argument, the fp32-formula error table the transcendental tolerances
 come from, the FeedForward tolerance's 2 % cap, and for test_gpu_dwconv_ref.py / test_gpu_stackedge_ref.py
 the conv reference against independent formulations, the exact class's exactness, SwooshR's error over
-the conv's range and the ambiguity cap of every case's inputs."""
+the conv's range and the ambiguity cap of every case's inputs; for test_gpu_bigvgan_ref.py the BigVGAN
+references against oracle/bigvgan_np.py and torch in float64, the exact classes' exactness, the
+visibility of an off-by-one at an utterance edge in every case, and the ambiguity cap."""
 import numpy as np
 import pytest
 
@@ -280,3 +282,193 @@ def test_stackedge_refs():
             m = rng.integers(0, 2, B * L).astype(np.uint8)
             md = kr.mask_downsample_ref(m, B, L, ds)
             assert md.shape == (B * dL,) and all(md[b * dL + i] == m[b * L + i * ds] for b in range(B) for i in range(dL))
+
+
+# --------------------------------------------------------------------------- BigVGAN references
+# (tests/test_gpu_bigvgan_ref.py; case lists in tests/bigvgan_cases.py)
+import bigvgan_cases as bc  # noqa: E402
+from oracle import bigvgan_np as bvo  # noqa: E402
+
+BV_F = bvo.anti_alias_filter(2).astype(np.float32).astype(np.float64)
+
+
+def _torch_act(x, la, lb, f):
+    """Activation1d with torch's own ops in float64: F.pad(replicate), conv_transpose1d, conv1d."""
+    F = torch.nn.functional
+    xt = torch.from_numpy(x.T.copy())[None]                         # (1, C, T)
+    C = xt.shape[1]
+    ft = torch.from_numpy(f)[None, None].expand(C, 1, 12)
+    y = 2 * F.conv_transpose1d(F.pad(xt, (5, 5), mode="replicate"), ft, stride=2, groups=C)[..., 15:-15]
+    y = y + (1.0 / (torch.exp(torch.from_numpy(lb)) + 1e-9))[:, None] * torch.sin(y * torch.exp(torch.from_numpy(la))[:, None]) ** 2
+    z = F.conv1d(F.pad(y, (5, 6), mode="replicate"), ft, stride=2, groups=C)
+    return z[0].numpy().T
+
+
+@pytest.mark.parametrize("T", [1, 2, 3, 5, 6, 7, 20])
+def test_bv_act_ref_matches_oracle_and_torch(T):
+    rng = np.random.default_rng(T)
+    C = 5
+    x, la, lb = rng.standard_normal((T, C)), rng.uniform(-0.3, 0.3, C), rng.uniform(-0.3, 0.3, C)
+    z, _ = kr.bv_act_ref(x, None, 1, 1, T, T, np.exp(la), 1.0 / (np.exp(lb) + 1e-9), BV_F)
+    assert np.abs(z - bvo.activation1d_snakebeta(x.T, la, lb, BV_F).T).max() < 1e-13
+    assert np.abs(z - _torch_act(x, la, lb, BV_F)).max() < 1e-13
+
+
+def test_bv_filter_ref_is_the_polyphase_form_of_the_upsampler():
+    """The 6 + 6 coefficients, derived from impulse responses, reproduce the transposed convolution
+    inside a signal; the fp32 taps are anti_alias_filter(2) rounded once."""
+    rng = np.random.default_rng(3)
+    for f in (BV_F, kr.BV_TAPS_EXACT):
+        r = kr.bv_filter_ref(f)
+        x = rng.standard_normal((30, 1))
+        y = kr.bv_upsample(x, f)[:, 0]
+        for t in range(3, 26):
+            assert np.isclose(y[2 * t], sum(r[m] * x[t + m - 3, 0] for m in range(6)), atol=1e-13)
+            assert np.isclose(y[2 * t + 1], sum(r[6 + m] * x[t + m - 2, 0] for m in range(6)), atol=1e-13)
+        assert np.array_equal(r[12:], f)
+    assert np.abs(BV_F - bvo.anti_alias_filter(2)).max() <= 2.0 ** -25 * np.abs(BV_F).max() * 2
+
+
+@pytest.mark.parametrize("ks,d", bc.CONV_KD)
+def test_bv_conv_ref_matches_oracle_and_torch(ks, d):
+    rng = np.random.default_rng(ks * 10 + d)
+    C, Co = 6, 4
+    for n in (1, 2, 9):
+        a = kr.round16(rng.standard_normal((n, C)), "bf16")
+        w = kr.round16(rng.standard_normal((Co, C, ks)), "bf16")
+        bias = rng.standard_normal(Co)
+        pad = d * (ks - 1) // 2
+        got = kr.bv_conv_ref(a, w, bias, d, None, 1, 1, n, n, 1, "bf16")[0]
+        assert np.abs(got - bvo.conv1d(a.T, w, bias, d, pad).T).max() < 1e-12
+        t = torch.nn.functional.conv1d(torch.from_numpy(a.T.copy())[None], torch.from_numpy(w),
+                                       torch.from_numpy(bias), dilation=d, padding=pad)[0].numpy().T
+        assert np.abs(got - t).max() < 1e-12
+
+
+@pytest.mark.parametrize("u,k", bc.CONVT_UK)
+def test_bv_convt_ref_matches_oracle_and_torch(u, k):
+    rng = np.random.default_rng(u * 10 + k)
+    Cin, Co = 5, 3
+    for n in (1, 2, 5):
+        x, w, bias = rng.standard_normal((n, Cin)), rng.standard_normal((Cin, Co, k)), rng.standard_normal(Co)
+        Lo = kr.bv_rows(n * u, 8)
+        got = kr.bv_convt_ref(x, w, bias, u, None, 1, 1, n, n, Lo)[0]
+        assert (got[n * u:] == 0).all()
+        assert np.abs(got[:n * u] - bvo.conv_transpose1d(x.T, w, bias, u, (k - u) // 2).T).max() < 1e-12
+        t = torch.nn.functional.conv_transpose1d(torch.from_numpy(x.T.copy())[None], torch.from_numpy(w),
+                                                 torch.from_numpy(bias), stride=u, padding=(k - u) // 2)[0].numpy().T
+        assert np.abs(got[:n * u] - t).max() < 1e-12
+
+
+def test_bv_post_and_im2col_refs_match_torch():
+    rng = np.random.default_rng(9)
+    C = 4
+    for n in (1, 3, 10):
+        a, w = rng.standard_normal((n, C)), rng.standard_normal((C, 7))
+        got = kr.bv_post_ref(a, w, 0.25, None, 1, 1, n, n, 0)[0]
+        t = torch.nn.functional.conv1d(torch.from_numpy(a.T.copy())[None], torch.from_numpy(w)[None], padding=3)[0, 0]
+        assert np.abs(got - np.clip(t.numpy() + 0.25, -1, 1)).max() < 1e-13
+        assert np.abs(kr.bv_post_ref(a, w, 0.25, None, 1, 1, n, n, 1)[0] - np.tanh(t.numpy() + 0.25)).max() < 1e-13
+        # im2col . W == conv1d, in both layouts
+        for layout in (0, 1):
+            x = rng.standard_normal((1, C, n) if layout == 0 else (1, n, C))
+            A = kr.im2col_ref(x, layout, 0.5, -1.0, None, 1, n, C, 7)[0]
+            wc = rng.standard_normal((3, C, 7))
+            v = (x[0] if layout == 0 else x[0].T) / 0.5 + 1.0
+            want = bvo.conv1d(v, wc, None, 1, 3).T
+            assert np.abs(A @ np.concatenate([wc[:, :, t] for t in range(7)], 1).T - want).max() < 1e-12
+
+
+def _visible(true, bugged, tol, valid, what):
+    """A deliberate off-by-one differs from the reference by >= 1000 tolerances (>= 1 where the
+    class is exact) on some valid output."""
+    diff = np.abs(true - bugged)[valid]
+    lim = np.maximum(1000 * tol[valid], 1e-30)
+    assert (diff >= np.where(tol[valid] > 0, lim, 1.0)).any(), f"{what}: the edge mistake is invisible"
+
+
+@pytest.mark.parametrize("C", bc.ACT_C)
+@pytest.mark.parametrize("Lmax", bc.ACT_LMAX + ["scaled"])
+def test_bv_act_cases(Lmax, C):
+    """Exactness of the exact class (asserted inside the reference), visibility of a clamp to len and
+    of the neighbouring utterance's frame, and the ambiguity cap of the 16-bit operand."""
+    for halo in (8, 32):
+        for klass in ("exact", "general"):
+            c = bc.act_case(Lmax, C, halo, klass)
+            a = (c["x"], c["lens"], c["scale"], c["B"], c["Lmax"], c["Lp"], c["alpha"], c["ibeta"], c["f"], klass)
+            z, tol = kr.bv_act_ref(*a)
+            valid = np.zeros(z.shape, bool)
+            for b, n in enumerate(kr.bv_lens(c["lens"], c["scale"], c["Lmax"], c["B"])):
+                valid[b * c["Lp"]:b * c["Lp"] + n] = True
+            assert (z[~valid] == 0).all() and valid.any()
+            for bug in ("clamp", "neighbour"):
+                _visible(z, kr.bv_act_ref(*a, bug=bug)[0], tol, valid, f"ACT {klass} {bug} Lmax={Lmax} halo={halo}")
+            if klass == "general":
+                assert np.abs(c["alpha"] * kr.bv_upsample(np.abs(c["x"]), c["f"], True)).max() <= kr.BV_ARG_GENERAL
+                w = bc.act_case(Lmax, C, halo, "wide")
+                top = np.abs(w["alpha"] * kr.bv_upsample(np.abs(w["x"]), w["f"], True)).max()
+                assert 0.9 * kr.BV_ARG_WIDE <= top <= kr.BV_ARG_WIDE
+                for fmt in ("bf16", "f16"):
+                    assert kr.amb16(z[valid], tol[valid], fmt)[0].mean() <= kr.AMB_CAP
+
+
+@pytest.mark.parametrize("C", bc.CONV_C)
+def test_bv_conv_cases(C):
+    seen = set()
+    for case in bc.conv_cases(C):
+        for klass in ("exact", "general"):
+            c = bc.conv_inputs(case, klass, 1, "bf16")
+            a = (c["a"], c["w"], c["bias"], c["d"], c["lens"], 1, c["B"], c["Lmax"], c["Lp"], 1, "bf16", c["resid"], klass)
+            ref, tol, valid = kr.bv_conv_ref(*a)           # (the exact class asserts its exactness)
+            bug = kr.bv_conv_ref(*a[:-1], "general", bug="neighbour")[0]
+            _visible(ref, bug, tol, np.repeat(valid[:, None], C, 1), f"CONV {klass} {case}")
+        seen.add((case[1], case[2]))
+        M = 2 * kr.bv_rows(case[3], c["halo"])
+        seen.add(("M", np.sign(M - 2 * bc.conv_predict(C, 1)[0]) if case[3] > 3 else "short"))
+    assert seen >= set(bc.CONV_KD) | {("M", -1), ("M", 0), ("M", 1), ("M", "short")}
+
+
+@pytest.mark.parametrize("u,k", bc.CONVT_UK)
+def test_bv_convt_cases(u, k):
+    for Lin in (1, 2, 5):
+        for stage0 in (True, False):
+            c = bc.convt_inputs(u, k, Lin, 8, stage0)
+            a = (c["bias"], u, c["lens"], c["scale"], c["B"], Lin, c["Ls"], c["Lo"])
+            ref, _ = kr.bv_convt_ref(c["P"], c["eye"], *a, klass="exact")
+            bug, _ = kr.bv_convt_ref(c["P"], c["eye"], *a, bug="le")
+            # (k = u: frame len_in lands on outputs t >= len_in * u only, which the kernel zeroes anyway)
+            edge = k > u and c["Ls"] > min(kr.bv_lens(c["lens"], c["scale"], Lin, c["B"]))
+            if edge:
+                assert np.abs(ref - bug).max() >= 1.0, f"CONVT u={u} k={k} Lin={Lin}: s <= len_in is invisible"
+            for klass in ("exact", "general"):
+                r, t = kr.bv_convt_ref(c["x"][klass], c["w"][klass], *a, 1, "bf16", klass)
+                b = kr.bv_convt_ref(c["x"][klass], c["w"][klass], *a, 1, "bf16", "general", bug="le")[0]
+                if edge:
+                    _visible(r, b, t, t >= 0, f"CONVT {klass} u={u} k={k} Lin={Lin} stage0={stage0}")
+
+
+@pytest.mark.parametrize("Lmax", bc.POST_LMAX)
+def test_bv_post_cases(Lmax):
+    for klass in ("exact", "general"):
+        c = bc.post_inputs(Lmax, 16, klass)
+        a = (c["a"], c["w"], c["bias0"], c["lens"], c["scale"], c["B"], Lmax, c["Ls"])
+        for use_tanh in (0, 1):
+            ref, tol = kr.bv_post_ref(*a, use_tanh, klass)
+            bug = kr.bv_post_ref(*a, use_tanh, "general", bug="short")[0]
+            if Lmax > 1 and use_tanh:              # (the clamp can hide a difference past +-1)
+                _visible(ref, bug, tol, np.ones(ref.shape, bool), f"POST {klass} Lmax={Lmax}")
+
+
+def test_bv_step_reference_composes():
+    c = bc.step_inputs(24, 3, 1)
+    ref, tol, valid = kr.bv_step_ref(c, 3, "bf16")
+    # against the oracle's own composition on the first utterance, in float64 without operand rounding
+    n = c["Lmax"]
+    x = c["x"][:n].T
+    la, lb = np.log(c["alpha"]), np.log(1.0 / c["ibeta"] - 1e-9)
+    t = bvo.activation1d_snakebeta(x, la, lb, c["f"])
+    t = bvo.conv1d(t, c["w"], c["bias"], 1, 1)
+    t = bvo.activation1d_snakebeta(t, np.log(c["alpha2"]), np.log(1.0 / c["ibeta2"] - 1e-9), c["f"])
+    want = (bvo.conv1d(t, c["w2"], c["bias2"], 1, 1) + x).T
+    assert np.abs(ref[:n] - want).max() < 1e-3 and (np.abs(ref[:n] - want) <= 50 * tol[:n] + 1e-4).all()
+    assert valid.sum() == sum(c["lens"]) and (tol[valid] > 0).all()

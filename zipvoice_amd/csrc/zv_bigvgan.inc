@@ -201,6 +201,124 @@ __global__ __launch_bounds__(BV_POST_T) void zv_bv_post_kernel(
 // ===========================================================================
 struct BvAct { float* alpha = nullptr; float* ibeta = nullptr; };
 
+// The host pieces zv_bigvgan (finalize / decode) and zv_bigvgan_check share: the weight
+// relayouts, the alias-free filter, the halo rule and the launches with a choice in them.
+struct BvHost {
+  // zero rows around each utterance of an implicit-conv operand: >= the conv's padding, whole
+  // 8-frame groups of the activation kernel; a stage stream's rows per utterance
+  static int halo_for(int halo, int ks, int d) { return std::max(halo, (int)round_up(d * (ks - 1) / 2, 8)); }
+  static int stage_rows(int L, int halo) { return (int)round_up(L + halo, 8); }
+
+  // Conv1d weight (Cout, Cin, k) -> GEMM rows [o][tap * Cp + c]
+  // (input channels zero-padded to Cp: the implicit-conv operand's row width)
+  static std::vector<float> conv_rows(const float* w, int Cout, int Cin, int k, int Cp) {
+    std::vector<float> w2((size_t)Cout * Cp * k, 0.f);
+    for (int o = 0; o < Cout; ++o)
+      for (int c = 0; c < Cin; ++c)
+        for (int t = 0; t < k; ++t) w2[(size_t)o * Cp * k + (size_t)t * Cp + c] = w[((size_t)o * Cin + c) * k + t];
+    return w2;
+  }
+  // ConvTranspose1d weight (Cin, Cout, k) -> GEMM rows [j * Cout + o][c]
+  static std::vector<float> convt_rows(const float* w, int Cin, int Cout, int k) {
+    std::vector<float> w2((size_t)k * Cout * Cin);
+    for (int c = 0; c < Cin; ++c)
+      for (int o = 0; o < Cout; ++o)
+        for (int j = 0; j < k; ++j) w2[((size_t)j * Cout + o) * Cin + c] = w[((size_t)c * Cout + o) * k + j];
+    return w2;
+  }
+
+  // the kernel's filter arguments from the 12 low-pass taps
+  // upsample: y[2t] = 2 sum_m f[5-2m] x[t+m] (m=-3..2), y[2t+1] = 2 sum_m f[6-2m] x[t+m] (m=-2..3)
+  static BvFilter filter_of(const float* f32) {
+    BvFilter filt{};
+    for (int m = 0; m < 6; ++m) {
+      filt.up_even[m] = 2.0f * f32[5 - 2 * (m - 3)];
+      filt.up_odd[m] = 2.0f * f32[6 - 2 * (m - 2)];
+    }
+    for (int n = 0; n < 12; ++n) filt.down[n] = f32[n];
+    return filt;
+  }
+  // alias_free_activation filter.py: kaiser-windowed sinc, cutoff 0.25, half width 0.3,
+  // 12 taps, normalised to unit DC gain (double, rounded once to fp32 like the buffer)
+  static BvFilter make_filter() {
+    const int ks = 12, half = 6;
+    const double cutoff = 0.25, delta_f = 4 * 0.3;
+    const double A = 2.285 * (half - 1) * M_PI * delta_f + 7.95;
+    const double beta = A > 50.0 ? 0.1102 * (A - 8.7)
+                        : (A >= 21.0 ? 0.5842 * pow(A - 21.0, 0.4) + 0.07886 * (A - 21.0) : 0.0);
+    double fd[12], sum = 0.0;
+    for (int n = 0; n < ks; ++n) {
+      const double r = 2.0 * n / (ks - 1) - 1.0;
+      const double win = std::cyl_bessel_i(0.0, beta * sqrt(1.0 - r * r)) / std::cyl_bessel_i(0.0, beta);
+      const double tm = (n - half) + 0.5;
+      const double arg = 2.0 * cutoff * tm;
+      const double sinc = arg == 0.0 ? 1.0 : sin(M_PI * arg) / (M_PI * arg);
+      fd[n] = 2.0 * cutoff * win * sinc;
+      sum += fd[n];
+    }
+    float f32[12];
+    for (int n = 0; n < ks; ++n) f32[n] = (float)(fd[n] / sum);
+    return filter_of(f32);
+  }
+
+  // W . A (+ bias, + resid) -> C and / or the 16-bit copy `out`; CONV: the implicit-conv A loader
+  // over the (rows, conv_c) operand.  Returns the K step of the instantiation it launched.
+  template <int SPLIT, int CONV = 0>
+  static int gemm(const Linear& W, const Act& A, long M, float* C, long ldc, Act out, const float* resid,
+                  hipStream_t s, const char* tag, int conv_c = 0, int conv_d = 1, int conv_pad = 0) {
+    GemmParams p{};
+    p.M = (int)M; p.N = W.N; p.K = W.K; p.nz2 = 1; p.Brows = W.Npad;
+    p.Ah = A.h; p.Al = A.l; p.lda = A.ld;
+    p.Bh = W.hi; p.Bl = W.lo; p.ldb = W.Kpad;
+    p.bias = W.b; p.rows_per_group = 1; p.rpb = 1;
+    p.resid = resid;
+    p.C = C; p.ldc = ldc;
+    p.Ch = out.h; p.Cl = out.l; p.ldch = out.ld;
+    p.conv_c = conv_c; p.conv_d = conv_d; p.conv_pad = conv_pad;
+    if constexpr (CONV) {
+      // tile width matched to the narrow late stages (N = C), K step to the padded
+      // channel count (Cp = round_up(C, 32): 64-deep steps when Cp % 64 == 0)
+      if (conv_c % 64 == 0) {
+        if (W.N <= 48)
+          launch_gemm<256, 48, 4, 1, SPLIT, EPI_STD, 2, 2, 64, 0, 1>(p, 1, s, tag, true, -1);
+        else if (W.N <= 64)
+          launch_gemm<64, 64, 2, 2, SPLIT, EPI_STD, 2, 2, 64, 0, 1>(p, 1, s, tag, true, -1);
+        else
+          launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, 64, 0, 1>(p, 1, s, tag);
+        return 64;
+      }
+      if (W.N <= 32)
+        launch_gemm<256, 32, 4, 1, SPLIT, EPI_STD, 2, 2, 32, 0, 1>(p, 1, s, tag, true, -1);
+      else if (W.N <= 96)
+        launch_gemm<128, 96, 2, 2, SPLIT, EPI_STD, 2, 2, 32, 0, 1>(p, 1, s, tag, true, -1);
+      else
+        launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, 32, 0, 1>(p, 1, s, tag);
+      return 32;
+    } else {
+      launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD>(p, 1, s, tag);
+      return GEMM_BK;
+    }
+  }
+
+  template <int MODE>
+  static void act(const BvAct& a, const BvFilter& filt, int halo, const float* in, const int* lens, int scale,
+                  int B, int Lmax, int Lp, int C, float* out, Act o, hipStream_t s) {
+    constexpr int TT = 8;
+    const int rows = Lp + (MODE == 2 ? halo : 0);
+    const long n = (long)B * cdiv(rows, TT) * C;
+    hipLaunchKernelGGL((zv_bv_act_kernel<MODE, TT>), grid1d(n), dim3(256), 0, s, in, lens, scale,
+                       B, Lmax, Lp, halo, C, a.alpha, a.ibeta, filt, out, o.h, o.l, o.ld);
+    ZV_LAUNCH_CHECK();
+  }
+
+  // conv_post's LDS window must fit; returns its bytes
+  static size_t post_lds(int C) {
+    const size_t b = (size_t)(BV_POST_T + 6) * C * sizeof(float);
+    ZV_REQUIRE(b <= 64 * 1024, "conv_post input channels too wide for the LDS window");
+    return b;
+  }
+};
+
 struct zv_bigvgan {
   zv_bigvgan_config cfg;
   WeightStore store;
@@ -233,15 +351,9 @@ struct zv_bigvgan {
     if (ev_fork) (void)ZV_BLOCKING(hipEventDestroy(ev_fork));
   }
 
-  // Conv1d weight (Cout, Cin, k) -> GEMM rows [o][tap * Cin + c]
-  // (input channels zero-padded to Cp: the implicit-conv operand's row width)
   Linear conv_linear(const std::string& p, int Cout, int Cin, int k, bool bias, int Cp = 0) {
     if (Cp < Cin) Cp = Cin;
-    const auto& w = store.take(p + ".weight", (size_t)Cout * Cin * k);
-    std::vector<float> w2((size_t)Cout * Cp * k, 0.f);
-    for (int o = 0; o < Cout; ++o)
-      for (int c = 0; c < Cin; ++c)
-        for (int t = 0; t < k; ++t) w2[(size_t)o * Cp * k + (size_t)t * Cp + c] = w[((size_t)o * Cin + c) * k + t];
+    const std::vector<float> w2 = BvHost::conv_rows(store.take(p + ".weight", (size_t)Cout * Cin * k).data(), Cout, Cin, k, Cp);
     return store.make_linear(w2.data(), Cout, Cp * k, bias ? store.take(p + ".bias", Cout).data() : nullptr);
   }
   BvAct snake(const std::string& p, int C) {
@@ -256,38 +368,10 @@ struct zv_bigvgan {
     return BvAct{store.upload(ea), store.upload(ib)};
   }
 
-  // alias_free_activation filter.py: kaiser-windowed sinc, cutoff 0.25, half width 0.3,
-  // 12 taps, normalised to unit DC gain (double, rounded once to fp32 like the buffer)
-  void make_filter() {
-    const int ks = 12, half = 6;
-    const double cutoff = 0.25, delta_f = 4 * 0.3;
-    const double A = 2.285 * (half - 1) * M_PI * delta_f + 7.95;
-    const double beta = A > 50.0 ? 0.1102 * (A - 8.7)
-                        : (A >= 21.0 ? 0.5842 * pow(A - 21.0, 0.4) + 0.07886 * (A - 21.0) : 0.0);
-    double fd[12], sum = 0.0;
-    for (int n = 0; n < ks; ++n) {
-      const double r = 2.0 * n / (ks - 1) - 1.0;
-      const double win = std::cyl_bessel_i(0.0, beta * sqrt(1.0 - r * r)) / std::cyl_bessel_i(0.0, beta);
-      const double tm = (n - half) + 0.5;
-      const double arg = 2.0 * cutoff * tm;
-      const double sinc = arg == 0.0 ? 1.0 : sin(M_PI * arg) / (M_PI * arg);
-      fd[n] = 2.0 * cutoff * win * sinc;
-      sum += fd[n];
-    }
-    float f32[12];
-    for (int n = 0; n < ks; ++n) f32[n] = (float)(fd[n] / sum);
-    // upsample: y[2t] = 2 sum_m f[5-2m] x[t+m] (m=-3..2), y[2t+1] = 2 sum_m f[6-2m] x[t+m] (m=-2..3)
-    for (int m = 0; m < 6; ++m) {
-      filt.up_even[m] = 2.0f * f32[5 - 2 * (m - 3)];
-      filt.up_odd[m] = 2.0f * f32[6 - 2 * (m - 2)];
-    }
-    for (int n = 0; n < ks; ++n) filt.down[n] = f32[n];
-  }
-
   void finalize() {
     const int nu = cfg.num_upsamples, nk = cfg.num_kernels;
     ZV_REQUIRE(nu >= 1 && nu <= 8 && nk >= 1 && nk <= 3, "bad num_upsamples / num_kernels");
-    make_filter();
+    filt = BvHost::make_filter();
     const int C0 = cfg.upsample_initial_channel, nm = cfg.num_mels;
     conv_pre = conv_linear("conv_pre", C0, nm, 7, true);
     int C = C0;
@@ -297,11 +381,7 @@ struct zv_bigvgan {
       ZV_REQUIRE(u >= 1 && k >= u && (k - u) % 2 == 0, "upsample kernel / rate must satisfy k >= u, k - u even");
       ZV_REQUIRE(C % 2 == 0, "channel count must halve per stage");
       const std::string p = "ups." + std::to_string(i) + ".0.";
-      const auto& w = store.take(p + "weight", (size_t)C * Co * k);   // (Cin, Cout, k)
-      std::vector<float> w2((size_t)k * Co * C);
-      for (int c = 0; c < C; ++c)
-        for (int o = 0; o < Co; ++o)
-          for (int j = 0; j < k; ++j) w2[((size_t)j * Co + o) * C + c] = w[((size_t)c * Co + o) * k + j];
+      const std::vector<float> w2 = BvHost::convt_rows(store.take(p + "weight", (size_t)C * Co * k).data(), C, Co, k);
       ups.push_back(store.make_linear(w2.data(), k * Co, C, nullptr));
       ups_b.push_back(store.upload_key(p + "bias", Co));
       expected += 2;
@@ -316,7 +396,7 @@ struct zv_bigvgan {
         for (int n = 0; n < 3; ++n) {
           const int d = cfg.resblock_dilation_sizes[j][n];
           ZV_REQUIRE(d >= 1, "bad dilation");
-          halo = std::max(halo, (int)round_up(d * (ks - 1) / 2, 8));
+          halo = BvHost::halo_for(halo, ks, d);
           const int Cp = (int)round_up(C, 32);
           a1.push_back(conv_linear(rp + "convs1." + std::to_string(n), C, C, ks, true, Cp));
           a2.push_back(conv_linear(rp + "convs2." + std::to_string(n), C, C, ks, true, Cp));
@@ -366,47 +446,12 @@ struct zv_bigvgan {
   template <int SPLIT, int CONV = 0>
   void gemm(const Linear& W, const Act& A, long M, float* C, long ldc, Act out, const float* resid,
             hipStream_t s, const char* tag, int conv_c = 0, int conv_d = 1, int conv_pad = 0) {
-    GemmParams p{};
-    p.M = (int)M; p.N = W.N; p.K = W.K; p.nz2 = 1; p.Brows = W.Npad;
-    p.Ah = A.h; p.Al = A.l; p.lda = A.ld;
-    p.Bh = W.hi; p.Bl = W.lo; p.ldb = W.Kpad;
-    p.bias = W.b; p.rows_per_group = 1; p.rpb = 1;
-    p.resid = resid;
-    p.C = C; p.ldc = ldc;
-    p.Ch = out.h; p.Cl = out.l; p.ldch = out.ld;
-    p.conv_c = conv_c; p.conv_d = conv_d; p.conv_pad = conv_pad;
-    if constexpr (CONV) {
-      // tile width matched to the narrow late stages (N = C), K step to the padded
-      // channel count (Cp = round_up(C, 32): 64-deep steps when Cp % 64 == 0)
-      if (conv_c % 64 == 0) {
-        if (W.N <= 48)
-          launch_gemm<256, 48, 4, 1, SPLIT, EPI_STD, 2, 2, 64, 0, 1>(p, 1, s, tag, true, -1);
-        else if (W.N <= 64)
-          launch_gemm<64, 64, 2, 2, SPLIT, EPI_STD, 2, 2, 64, 0, 1>(p, 1, s, tag, true, -1);
-        else
-          launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, 64, 0, 1>(p, 1, s, tag);
-      } else {
-        if (W.N <= 32)
-          launch_gemm<256, 32, 4, 1, SPLIT, EPI_STD, 2, 2, 32, 0, 1>(p, 1, s, tag, true, -1);
-        else if (W.N <= 96)
-          launch_gemm<128, 96, 2, 2, SPLIT, EPI_STD, 2, 2, 32, 0, 1>(p, 1, s, tag, true, -1);
-        else
-          launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD, 2, 2, 32, 0, 1>(p, 1, s, tag);
-      }
-    } else {
-      launch_gemm<128, 128, 2, 2, SPLIT, EPI_STD>(p, 1, s, tag);
-    }
+    BvHost::gemm<SPLIT, CONV>(W, A, M, C, ldc, out, resid, s, tag, conv_c, conv_d, conv_pad);
   }
-
   template <int MODE>
   void act(const BvAct& a, const float* in, const int* lens, int scale, int B, int Lmax, int Lp,
            int C, float* out, Act o, hipStream_t s) {
-    constexpr int TT = 8;
-    const int rows = Lp + (MODE == 2 ? halo : 0);
-    const long n = (long)B * cdiv(rows, TT) * C;
-    hipLaunchKernelGGL((zv_bv_act_kernel<MODE, TT>), grid1d(n), dim3(256), 0, s, in, lens, scale,
-                       B, Lmax, Lp, halo, C, a.alpha, a.ibeta, filt, out, o.h, o.l, o.ld);
-    ZV_LAUNCH_CHECK();
+    BvHost::act<MODE>(a, filt, halo, in, lens, scale, B, Lmax, Lp, C, out, o, s);
   }
 
   // Stage streams: utterance b at rows b*Lp + [0, Lmax), Lp = round_up(Lmax + halo, 8);
@@ -438,7 +483,7 @@ struct zv_bigvgan {
       const long Min = (long)B * Ls;
       float* Pb = P.get<float>((size_t)Min * k * Co);
       gemm<SPLIT>(ups[i], xcur, Min, Pb, (long)k * Co, Act{}, nullptr, s, tg);
-      const int Lo = L * u, Lp = (int)round_up(Lo + halo, 8);
+      const int Lo = L * u, Lp = BvHost::stage_rows(Lo, halo);
       const long M = (long)B * Lp;
       xs = x.get<float>((size_t)M * Co);
       hipLaunchKernelGGL(zv_bv_convt_gather_kernel, grid1d(M * Co), dim3(256), 0, s, Pb,
@@ -484,8 +529,7 @@ struct zv_bigvgan {
     const long M = (long)B * Ls;
     float* ab = post.get<float>((size_t)M * C);
     act<0>(act_post, xs, lens, scale, B, L, Ls, C, ab, Act{}, s);
-    const size_t post_lds = (size_t)(BV_POST_T + 6) * C * sizeof(float);
-    ZV_REQUIRE(post_lds <= 64 * 1024, "conv_post input channels too wide for the LDS window");
+    const size_t post_lds = BvHost::post_lds(C);
     hipLaunchKernelGGL(zv_bv_post_kernel, dim3(B * cdiv(L, BV_POST_T)), dim3(BV_POST_T), post_lds, s,
                        ab, lens, scale, B, L, Ls, C, post_w, post_b, cfg.use_tanh_at_final, wav);
     ZV_LAUNCH_CHECK();

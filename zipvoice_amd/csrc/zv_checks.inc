@@ -1,6 +1,6 @@
 // Test-infrastructure and microbenchmark entry points of the C ABI: zv_bench_gemm, zv_gemm_selftest,
 // zv_attn_plan, zv_attn2_check, zv_mx8_quantize, zv_mx8_gemm_check, zv_linear_check, zv_ffn_check,
-// zv_dwconv_check, zv_stackedge_check.
+// zv_dwconv_check, zv_stackedge_check, zv_bigvgan_check.
 // None of them builds an engine: each runs one launch (or a timed loop of one launch) of a kernel the
 // engine, the vocoder or BigVGAN dispatch also instantiates, on operands it makes itself.  Included by
 // zv_engine.hip after zv_engine (zv_linear_check uses its perm_na / perm_glu) and the ZV_API_* helpers.
@@ -793,6 +793,290 @@ int zv_stackedge_check(zv_stackedge_check_args* a) {
   }
   memcpy(a->launch, rec, sizeof(rec));
   a->num_cus = zv_num_cus();
+  ZV_API_END
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// zv_bigvgan_check: the BigVGAN kernels one at a time (and one AMP step), through the launches
+// and relayouts zv_bigvgan::finalize / decode use (BvHost), on host arrays with canary-guarded
+// outputs.  Everything the call allocates besides its inputs -- 16-bit operands, their padding
+// columns and halo rows, fp32 scratch -- starts from a finite, non-zero pattern seeded by
+// `stale`: a result that depends on unwritten memory changes with the seed.  (Non-finite stale
+// data is outside the kernels' contract: 0 * inf in a padding column would be NaN.)
+// ---------------------------------------------------------------------------
+namespace {
+inline unsigned chk_hash(size_t i, unsigned seed) {
+  unsigned x = (unsigned)i * 2654435761u ^ (seed * 0x9E3779B9u + 0x7F4A7C15u);
+  x ^= x >> 13; x *= 0x5bd1e995u; x ^= x >> 15;
+  return x;
+}
+// 16-bit patterns that are finite and non-zero as bf16 and as fp16, of either sign
+inline uint16_t chk_stale16(size_t i, unsigned seed) {
+  const unsigned x = chk_hash(i, seed);
+  return (uint16_t)(0x3C00u | (x & 0x3FFu) | ((x >> 16 & 1u) << 15));
+}
+inline float chk_stale32(size_t i, unsigned seed) {
+  const unsigned x = chk_hash(i, seed);
+  return ((x >> 20 & 1u) ? -1.f : 1.f) * (1.f + (float)(x & 0xFFFFu) / 16384.f);
+}
+bf16* chk_stale_dev16(ChkDev& dev, size_t n, unsigned seed) {
+  std::vector<uint16_t> h(n);
+  for (size_t i = 0; i < n; ++i) h[i] = chk_stale16(i, seed);
+  return reinterpret_cast<bf16*>(dev.up(h.data(), n));
+}
+float* chk_stale_dev32(ChkDev& dev, size_t n, unsigned seed) {
+  std::vector<float> h(n);
+  for (size_t i = 0; i < n; ++i) h[i] = chk_stale32(i, seed);
+  return dev.up(h.data(), n);
+}
+// chk_act with the stale pattern in the padding columns [cols, ld)
+Act chk_act_stale(ChkDev& dev, const float* x, long rows, int cols, long ld, bool lo, unsigned seed) {
+  std::vector<bf16> h, l;
+  chk_act(x, rows, cols, ld, lo, h, l);
+  uint16_t* hu = reinterpret_cast<uint16_t*>(h.data());
+  uint16_t* lu = lo ? reinterpret_cast<uint16_t*>(l.data()) : nullptr;
+  for (long r = 0; r < rows; ++r)
+    for (long c = cols; c < ld; ++c) {
+      hu[r * ld + c] = chk_stale16((size_t)(r * ld + c), seed);
+      if (lu) lu[r * ld + c] = chk_stale16((size_t)(r * ld + c), seed + 1);
+    }
+  Act a;
+  a.ld = ld;
+  a.h = dev.up(h.data(), h.size());
+  if (lo) a.l = dev.up(l.data(), l.size());
+  return a;
+}
+template <int SPLIT>
+void bv_check_run(zv_bigvgan_check_args* a) {
+  const int kind = a->kind, B = a->B, L = a->Lmax, C = a->C, G = a->guard, halo = a->halo;
+  const bool split = SPLIT == 3;
+  const unsigned seed = a->stale;
+  ChkDev dev;
+  WeightStore store;
+  hipStream_t s = nullptr;
+  const int* lens = a->lens ? dev.up(a->lens, (size_t)B) : nullptr;
+  const BvFilter filt = a->taps ? BvHost::filter_of(a->taps) : BvHost::make_filter();
+  auto snake = [&](const float* al, const float* ib) {
+    return BvAct{dev.up(al, (size_t)C), dev.up(ib, (size_t)C)};
+  };
+  auto out32 = [&](long rows, int cols) { return dev.up(a->out, (size_t)(rows + 2 * G) * cols); };
+  auto down32 = [&](float* d, long rows, int cols) { dev.down(a->out, d, (size_t)(rows + 2 * G) * cols); };
+  // the implicit-conv operand as decode allocates it: M + 2 * halo rows, base advanced by halo
+  auto operand = [&](long M, int Cp, unsigned sd) {
+    Act o;
+    o.ld = Cp;
+    o.h = chk_stale_dev16(dev, (size_t)(M + 2 * halo) * Cp, sd) + (long)halo * Cp;
+    if (split) o.l = chk_stale_dev16(dev, (size_t)(M + 2 * halo) * Cp, sd + 1) + (long)halo * Cp;
+    return o;
+  };
+  int rec5 = 0;
+  if (kind == ZV_BV_ACT) {
+    const int Lp = BvHost::stage_rows(L, halo);
+    const long M = (long)B * Lp;
+    const float* x = dev.up(a->x, (size_t)M * C);
+    const BvAct sn = snake(a->alpha, a->ibeta);
+    if (a->mode == 0) {
+      float* o = out32(M, C);
+      BvHost::act<0>(sn, filt, halo, x, lens, a->scale, B, L, Lp, C, o + (size_t)G * C, Act{}, s);
+      ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+      down32(o, M, C);
+    } else {
+      const int Cp = (int)round_up(C, 32);
+      const size_t n = (size_t)(M + 2 * halo + 2 * G) * Cp;
+      uint16_t* oh = dev.up(a->oh, n);
+      uint16_t* ol = split ? dev.up(a->ol, n) : nullptr;
+      Act o;
+      o.ld = Cp;
+      o.h = reinterpret_cast<bf16*>(oh) + (size_t)(G + halo) * Cp;
+      if (ol) o.l = reinterpret_cast<bf16*>(ol) + (size_t)(G + halo) * Cp;
+      BvHost::act<2>(sn, filt, halo, x, lens, a->scale, B, L, Lp, C, nullptr, o, s);
+      ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+      dev.down(a->oh, oh, n);
+      if (ol) dev.down(a->ol, ol, n);
+    }
+  } else if (kind == ZV_BV_CONV) {
+    const int Lp = BvHost::stage_rows(L, halo), Cp = (int)round_up(C, 32), Co = a->Cout;
+    const long M = (long)B * Lp;
+    const std::vector<float> w2 = BvHost::conv_rows(a->w, Co, C, a->ks, Cp);
+    const Linear W = store.make_linear(w2.data(), Co, Cp * a->ks, a->bias);
+    const size_t n = (size_t)(M + 2 * halo) * Cp;
+    Act A;
+    A.ld = Cp;
+    A.h = reinterpret_cast<bf16*>(dev.up(a->ah, n)) + (long)halo * Cp;
+    if (split) A.l = reinterpret_cast<bf16*>(dev.up(a->al, n)) + (long)halo * Cp;
+    std::vector<float> hc(a->out, a->out + (size_t)(M + 2 * G) * Co);
+    if (a->resid) memcpy(&hc[(size_t)G * Co], a->resid, (size_t)M * Co * sizeof(float));
+    float* o = dev.up(hc.data(), hc.size());
+    float* oi = o + (size_t)G * Co;                   // the residual in place, as decode's blocks 1, 2
+    rec5 = BvHost::gemm<SPLIT, 1>(W, A, M, oi, Co, Act{}, a->resid ? oi : nullptr, s, "bigvgan_check", Cp, a->d,
+                                  a->d * (a->ks - 1) / 2);
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    down32(o, M, Co);
+  } else if (kind == ZV_BV_CONVT) {
+    const int Co = a->Cout, k = a->ks, u = a->u, Ls = a->Ls;
+    const int Lo_s = BvHost::stage_rows(L * u, halo);
+    const long Min = (long)B * Ls, M = (long)B * Lo_s, ldp = (long)k * Co;
+    const float* bias = dev.up(a->bias, (size_t)Co);
+    const float* Pb;
+    if (a->flag) {
+      const std::vector<float> w2 = BvHost::convt_rows(a->w, C, Co, k);
+      const Linear W = store.make_linear(w2.data(), k * Co, C, nullptr);
+      const Act A = chk_act_stale(dev, a->x, Min, C, round_up(C, W_KPAD), split, seed);
+      float* P = chk_stale_dev32(dev, (size_t)(Min + 1) * ldp, seed + 2);   // (one spare row, as below)
+      rec5 = BvHost::gemm<SPLIT>(W, A, Min, P, ldp, Act{}, nullptr, s, "bigvgan_check");
+      Pb = P;
+    } else {
+      // one spare stale row behind P: a gather that reads frame len_in of the last utterance stays
+      // inside the buffer, and the test sees a wrong value
+      float* P = chk_stale_dev32(dev, (size_t)(Min + 1) * ldp, seed + 2);
+      ZV_CHECK(ZV_BLOCKING(hipMemcpy(P, a->x, (size_t)Min * ldp * sizeof(float), hipMemcpyHostToDevice)));
+      Pb = P;
+    }
+    float* o = out32(M, Co);
+    hipLaunchKernelGGL(zv_bv_convt_gather_kernel, grid1d(M * Co), dim3(256), 0, s, Pb, ldp, bias, lens, a->scale,
+                       B, L, Ls, u, k, (k - u) / 2, Co, Lo_s, o + (size_t)G * Co);
+    ZV_LAUNCH_CHECK();
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    down32(o, M, Co);
+  } else if (kind == ZV_BV_AVG) {
+    const long M = (long)B * L;
+    const float* y0 = dev.up(a->x, (size_t)M * C);
+    const float* y1 = a->n > 1 ? dev.up(a->x1, (size_t)M * C) : nullptr;
+    const float* y2 = a->n > 2 ? dev.up(a->x2, (size_t)M * C) : nullptr;
+    float* o = out32(M, C);
+    const size_t n16 = (size_t)(M + 2 * G) * a->ld;
+    uint16_t* oh = a->oh ? dev.up(a->oh, n16) : nullptr;
+    uint16_t* ol = a->ol ? dev.up(a->ol, n16) : nullptr;
+    hipLaunchKernelGGL(zv_bv_avg_kernel, grid1d(M * C), dim3(256), 0, s, y0, y1, y2, a->n, M, C, o + (size_t)G * C,
+                       oh ? reinterpret_cast<bf16*>(oh) + (size_t)G * a->ld : nullptr,
+                       ol ? reinterpret_cast<bf16*>(ol) + (size_t)G * a->ld : nullptr, (long)a->ld);
+    ZV_LAUNCH_CHECK();
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    down32(o, M, C);
+    if (oh) dev.down(a->oh, oh, n16);
+    if (ol) dev.down(a->ol, ol, n16);
+  } else if (kind == ZV_BV_POST) {
+    const size_t lds = BvHost::post_lds(C);
+    const float* x = dev.up(a->x, (size_t)B * a->Ls * C);
+    const float* w = dev.up(a->w, (size_t)C * 7);
+    float* o = out32((long)B * L, 1);
+    hipLaunchKernelGGL(zv_bv_post_kernel, dim3(B * cdiv(L, BV_POST_T)), dim3(BV_POST_T), lds, s, x, lens, a->scale, B,
+                       L, a->Ls, C, w, a->bias0, a->flag, o + G);
+    ZV_LAUNCH_CHECK();
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    down32(o, (long)B * L, 1);
+  } else if (kind == ZV_BV_IM2COL) {
+    const long M = (long)B * L;
+    const int K = C * a->ks;
+    const long ld = round_up((long)K, W_KPAD);
+    const float* in = dev.up(a->x, (size_t)M * C);
+    const size_t n16 = (size_t)(M + 2 * G) * ld;
+    uint16_t* oh = dev.up(a->oh, n16);
+    uint16_t* ol = split ? dev.up(a->ol, n16) : nullptr;
+    Act A;
+    A.ld = ld;
+    A.h = reinterpret_cast<bf16*>(oh) + (size_t)G * ld;
+    if (ol) A.l = reinterpret_cast<bf16*>(ol) + (size_t)G * ld;
+    hipLaunchKernelGGL(zv_voc_im2col_kernel, grid1d(M * K), dim3(256), 0, s, in, a->layout, a->div, a->sub, lens, B, L,
+                       C, a->ks, A.h, A.l, ld);
+    ZV_LAUNCH_CHECK();
+    float* o = nullptr;
+    if (a->flag) {
+      const std::vector<float> w2 = BvHost::conv_rows(a->w, a->Cout, C, a->ks, C);
+      const Linear W = store.make_linear(w2.data(), a->Cout, K, a->bias);
+      o = out32(M, a->Cout);
+      rec5 = BvHost::gemm<SPLIT>(W, A, M, o + (size_t)G * a->Cout, a->Cout, Act{}, nullptr, s, "bigvgan_check");
+    }
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    dev.down(a->oh, oh, n16);
+    if (ol) dev.down(a->ol, ol, n16);
+    if (o) down32(o, M, a->Cout);
+  } else {   // ZV_BV_STEP: x += conv2(act2(conv1_d(act1(x)))) of one AMP block, as decode runs it
+    const int Lp = BvHost::stage_rows(L, halo), Cp = (int)round_up(C, 32), ks = a->ks;
+    const long M = (long)B * Lp;
+    const float* x = dev.up(a->x, (size_t)M * C);
+    const BvAct s1 = snake(a->alpha, a->ibeta), s2 = snake(a->alpha2, a->ibeta2);
+    const std::vector<float> wa = BvHost::conv_rows(a->w, C, C, ks, Cp), wb = BvHost::conv_rows(a->w2, C, C, ks, Cp);
+    const Linear W1 = store.make_linear(wa.data(), C, Cp * ks, a->bias);
+    const Linear W2 = store.make_linear(wb.data(), C, Cp * ks, a->bias2);
+    const Act ca = operand(M, Cp, seed);
+    float* t1 = chk_stale_dev32(dev, (size_t)M * C, seed + 2);
+    float* o = out32(M, C);
+    float* y = o + (size_t)G * C;
+    BvHost::act<2>(s1, filt, halo, x, lens, a->scale, B, L, Lp, C, nullptr, ca, s);
+    BvHost::gemm<SPLIT, 1>(W1, ca, M, t1, C, Act{}, nullptr, s, "bigvgan_check", Cp, a->d, a->d * (ks - 1) / 2);
+    BvHost::act<2>(s2, filt, halo, t1, lens, a->scale, B, L, Lp, C, nullptr, ca, s);
+    rec5 = BvHost::gemm<SPLIT, 1>(W2, ca, M, y, C, Act{}, x, s, "bigvgan_check", Cp, 1, (ks - 1) / 2);
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    down32(o, M, C);
+  }
+  chk_record(a->launch, &a->num_cus);
+  a->launch[5] = rec5;                                 // the K step of the last GEMM (0: none ran)
+}
+}  // namespace
+
+extern "C" {
+
+int zv_bigvgan_check(zv_bigvgan_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && a->kind >= ZV_BV_FILTER && a->kind <= ZV_BV_STEP, "zv_bigvgan_check: unknown kind");
+  const int kind = a->kind;
+  if (kind == ZV_BV_FILTER) {
+    ZV_REQUIRE(a->out, "zv_bigvgan_check: FILTER writes 24 floats to out");
+    const BvFilter f = a->taps ? BvHost::filter_of(a->taps) : BvHost::make_filter();
+    memcpy(a->out, &f, sizeof(f));
+    return 0;
+  }
+  ZV_REQUIRE((a->split == 1 || a->split == 3) && a->guard >= 0 && a->B > 0 && a->Lmax > 0 && a->C > 0 &&
+                 (a->x || kind == ZV_BV_CONV),
+             "zv_bigvgan_check: bad arguments");
+  ZV_REQUIRE(a->out || (kind == ZV_BV_ACT && a->mode == 2) || (kind == ZV_BV_IM2COL && !a->flag),
+             "zv_bigvgan_check: the fp32 output");
+  const bool needs_halo = kind == ZV_BV_ACT || kind == ZV_BV_CONV || kind == ZV_BV_CONVT || kind == ZV_BV_STEP;
+  ZV_REQUIRE(!needs_halo || (a->halo >= 8 && a->halo % 8 == 0), "zv_bigvgan_check: halo a positive multiple of 8");
+  const bool scaled = kind == ZV_BV_ACT || kind == ZV_BV_CONVT || kind == ZV_BV_POST || kind == ZV_BV_STEP;
+  ZV_REQUIRE(!scaled || a->scale >= 1, "zv_bigvgan_check: scale >= 1");
+  if (a->lens && kind != ZV_BV_AVG && kind != ZV_BV_CONV)
+    for (int b = 0; b < a->B; ++b) ZV_REQUIRE(a->lens[b] >= 0, "zv_bigvgan_check: negative length");
+  switch (kind) {
+    case ZV_BV_ACT:
+      ZV_REQUIRE((a->mode == 0 || a->mode == 2) && a->alpha && a->ibeta, "zv_bigvgan_check: ACT mode 0 / 2, alpha, ibeta");
+      ZV_REQUIRE(a->mode == 0 || (a->oh && (a->ol != nullptr) == (a->split == 3)),
+                 "zv_bigvgan_check: ACT mode 2 writes oh (ol with split 3 only)");
+      break;
+    case ZV_BV_CONV:
+    case ZV_BV_STEP:
+      ZV_REQUIRE(a->Cout > 0 && a->Cout % 4 == 0 && a->ks >= 1 && a->ks % 2 == 1 && a->d >= 1 && a->w && a->bias,
+                 "zv_bigvgan_check: the conv's weight, bias, odd kernel size, dilation, Cout a multiple of 4");
+      ZV_REQUIRE(a->d * (a->ks - 1) / 2 <= a->halo, "zv_bigvgan_check: halo below the conv's padding");
+      if (kind == ZV_BV_CONV)
+        ZV_REQUIRE(a->ah && (a->al != nullptr) == (a->split == 3), "zv_bigvgan_check: CONV operand (al with split 3 only)");
+      else
+        ZV_REQUIRE(a->Cout == a->C && a->w2 && a->bias2 && a->alpha && a->ibeta && a->alpha2 && a->ibeta2,
+                   "zv_bigvgan_check: STEP needs both convs and both activations");
+      break;
+    case ZV_BV_CONVT:
+      ZV_REQUIRE(a->Cout > 0 && a->Cout % 4 == 0 && a->u >= 1 && a->ks >= a->u && (a->ks - a->u) % 2 == 0 && a->Ls >= a->Lmax && a->bias &&
+                     (!a->flag || a->w),
+                 "zv_bigvgan_check: CONVT needs k >= u, k - u even, Ls >= Lmax, bias (and the weight with the GEMM)");
+      break;
+    case ZV_BV_AVG:
+      ZV_REQUIRE(a->n >= 1 && a->n <= 3 && (a->n < 2 || a->x1) && (a->n < 3 || a->x2) && (!a->ol || a->oh) &&
+                     (!a->oh || a->ld >= a->C),
+                 "zv_bigvgan_check: AVG of 1..3 streams, ld >= C");
+      break;
+    case ZV_BV_POST:
+      ZV_REQUIRE(a->w && a->Ls >= a->Lmax, "zv_bigvgan_check: POST needs the weight and Ls >= Lmax");
+      (void)BvHost::post_lds(a->C);
+      break;
+    default:   // ZV_BV_IM2COL
+      ZV_REQUIRE(a->ks >= 1 && (a->layout == 0 || a->layout == 1) && a->div != 0.f && a->oh &&
+                     (a->ol != nullptr) == (a->split == 3) && (!a->flag || (a->w && a->bias && a->Cout > 0 && a->Cout % 4 == 0)),
+                 "zv_bigvgan_check: IM2COL layout 0 / 1, div != 0, oh (ol with split 3 only)");
+  }
+  if (a->split == 3) bv_check_run<3>(a); else bv_check_run<1>(a);
   ZV_API_END
 }
 

@@ -101,6 +101,18 @@ class ZvStackedgeCheckArgs(ctypes.Structure):
         ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
 
 
+class ZvBigvganCheckArgs(ctypes.Structure):
+    """zv_bigvgan_check_args (test infrastructure; tests/test_gpu_bigvgan_ref.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kind", "split", "mode", "guard", "B", "Lmax", "Ls", "halo", "scale",
+                                            "C", "Cout", "ks", "d", "u", "n", "layout", "flag")] + [
+        (n, ctypes.c_float) for n in ("div", "sub", "bias0")] + [
+        ("stale", ctypes.c_uint)] + [
+        (n, ctypes.c_void_p) for n in ("lens", "x", "x1", "x2", "w", "bias", "alpha", "ibeta", "w2", "bias2",
+                                       "alpha2", "ibeta2", "taps", "resid", "ah", "al", "out", "oh", "ol")] + [
+        ("ld", ctypes.c_int64),
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+
+
 # symbol name -> (restype, argtypes); must match include/zipvoice_hip.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -121,6 +133,7 @@ SIGNATURES = {
     "zv_ffn_check": (_I, [ctypes.POINTER(ZvFfnCheckArgs)]),
     "zv_dwconv_check": (_I, [ctypes.POINTER(ZvDwconvCheckArgs)]),
     "zv_stackedge_check": (_I, [ctypes.POINTER(ZvStackedgeCheckArgs)]),
+    "zv_bigvgan_check": (_I, [ctypes.POINTER(ZvBigvganCheckArgs)]),
     "zv_profile_report": (_I, [ctypes.c_char_p, _I]),
     "zv_host_block_count": (ctypes.c_int64, []),
     "zv_attn_fallbacks": (_I, [_P, _I, _P]),
