@@ -311,11 +311,30 @@ struct BvHost {
     ZV_LAUNCH_CHECK();
   }
 
+  // ConvTranspose1d's col2im gather (+ bias) of P (B * Ls rows of k * Co) into the stage stream
+  static void convt_gather(const float* P, const float* bias, const int* lens, int scale, int B, int L, int Ls,
+                           int u, int k, int Co, int Lp, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(zv_bv_convt_gather_kernel, grid1d((long)B * Lp * Co), dim3(256), 0, s, P, (long)k * Co, bias,
+                       lens, scale, B, L, Ls, u, k, (k - u) / 2, Co, Lp, out);
+    ZV_LAUNCH_CHECK();
+  }
+  // mean of the n AMP blocks' streams (+ the next stage's operand o)
+  static void avg(const float* y0, const float* y1, const float* y2, int n, long M, int C, float* out, Act o,
+                  hipStream_t s) {
+    hipLaunchKernelGGL(zv_bv_avg_kernel, grid1d(M * C), dim3(256), 0, s, y0, y1, y2, n, M, C, out, o.h, o.l, o.ld);
+    ZV_LAUNCH_CHECK();
+  }
   // conv_post's LDS window must fit; returns its bytes
   static size_t post_lds(int C) {
     const size_t b = (size_t)(BV_POST_T + 6) * C * sizeof(float);
     ZV_REQUIRE(b <= 64 * 1024, "conv_post input channels too wide for the LDS window");
     return b;
+  }
+  static void post(const float* x, const int* lens, int scale, int B, int L, int Ls, int C, const float* w,
+                   float bias, int use_tanh, float* wav, hipStream_t s) {
+    hipLaunchKernelGGL(zv_bv_post_kernel, dim3(B * cdiv(L, BV_POST_T)), dim3(BV_POST_T), post_lds(C), s, x, lens,
+                       scale, B, L, Ls, C, w, bias, use_tanh, wav);
+    ZV_LAUNCH_CHECK();
   }
 };
 
@@ -470,9 +489,7 @@ struct zv_bigvgan {
     Act xcur;
     {
       Act a0 = col[0].get((long)B * T, round_up((long)nm * 7, W_KPAD), split);
-      hipLaunchKernelGGL(zv_voc_im2col_kernel, grid1d((long)B * T * nm * 7), dim3(256), 0, s, in,
-                         layout, div, sub, lens, B, T, nm, 7, a0.h, a0.l, a0.ld);
-      ZV_LAUNCH_CHECK();
+      launch_voc_im2col(in, layout, div, sub, lens, B, T, nm, 7, a0, s);
       xcur = xa.get((long)B * T, round_up(C, W_KPAD), split);
       gemm<SPLIT>(conv_pre, a0, (long)B * T, nullptr, 0, xcur, nullptr, s, tg);
     }
@@ -486,9 +503,7 @@ struct zv_bigvgan {
       const int Lo = L * u, Lp = BvHost::stage_rows(Lo, halo);
       const long M = (long)B * Lp;
       xs = x.get<float>((size_t)M * Co);
-      hipLaunchKernelGGL(zv_bv_convt_gather_kernel, grid1d(M * Co), dim3(256), 0, s, Pb,
-                         (long)k * Co, ups_b[i], lens, scale, B, L, Ls, u, k, (k - u) / 2, Co, Lp, xs);
-      ZV_LAUNCH_CHECK();
+      BvHost::convt_gather(Pb, ups_b[i], lens, scale, B, L, Ls, u, k, Co, Lp, xs, s);
       C = Co; L = Lo; Ls = Lp; scale *= u;
       const int Cp = (int)round_up(C, 32);
       // AMP blocks, block j on side stream j
@@ -521,18 +536,13 @@ struct zv_bigvgan {
       }
       const bool last = i + 1 == cfg.num_upsamples;
       Act xo = last ? Act{} : xa.get(M, round_up(C, W_KPAD), split);
-      hipLaunchKernelGGL(zv_bv_avg_kernel, grid1d(M * C), dim3(256), 0, s, yb[0], yb[1], yb[2], nk,
-                         M, C, xs, xo.h, xo.l, xo.ld);
-      ZV_LAUNCH_CHECK();
+      BvHost::avg(yb[0], yb[1], yb[2], nk, M, C, xs, xo, s);
       xcur = xo;
     }
     const long M = (long)B * Ls;
     float* ab = post.get<float>((size_t)M * C);
     act<0>(act_post, xs, lens, scale, B, L, Ls, C, ab, Act{}, s);
-    const size_t post_lds = BvHost::post_lds(C);
-    hipLaunchKernelGGL(zv_bv_post_kernel, dim3(B * cdiv(L, BV_POST_T)), dim3(BV_POST_T), post_lds, s,
-                       ab, lens, scale, B, L, Ls, C, post_w, post_b, cfg.use_tanh_at_final, wav);
-    ZV_LAUNCH_CHECK();
+    BvHost::post(ab, lens, scale, B, L, Ls, C, post_w, post_b, cfg.use_tanh_at_final, wav, s);
   }
 
   size_t device_bytes() const {

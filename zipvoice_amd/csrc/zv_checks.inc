@@ -2,7 +2,9 @@
 // zv_attn_plan, zv_attn2_check, zv_mx8_quantize, zv_mx8_gemm_check, zv_linear_check, zv_ffn_check,
 // zv_dwconv_check, zv_stackedge_check, zv_bigvgan_check.
 // None of them builds an engine: each runs one launch (or a timed loop of one launch) of a kernel the
-// engine, the vocoder or BigVGAN dispatch also instantiates, on operands it makes itself.  Included by
+// engine, the vocoder or BigVGAN dispatch also instantiates, on operands it makes itself, through the
+// launch function they launch it through (the form choice, the grid and the argument order exist
+// once, beside the kernel); the only kernels launched here directly are this file's own.  Included by
 // zv_engine.hip after zv_engine (zv_linear_check uses its perm_na / perm_glu) and the ZV_API_* helpers.
 // Every device buffer of a call belongs to its ChkDev, which frees them when the call returns or throws.
 //
@@ -323,22 +325,11 @@ int zv_attn2_check(int kernel, int form, int B, int L, int H, int nv, const floa
   hipStream_t s = nullptr;
   if (kernel == 0) {
     f.vrows_per_head = 16; f.ocol_per_head = nv;
-    const int fm = form ? form : (sa3_qpw(L) == 4 ? 5 : sa3_qpw(L) == 3 ? 4 : sa3_qpw(L) == 2 ? 3 : sa2_qpw(L) == 3 ? 2 : 1);
-    switch (fm) {
-      case 1: launch_attn_sa2<2>(f, s); break;
-      case 2: launch_attn_sa2<3, 1>(f, s); break;
-      case 3: launch_attn_sa3<2>(f, s); break;
-      case 4: launch_attn_sa3<3>(f, s); break;
-      default: launch_attn_sa3<4>(f, s); break;
-    }
+    launch_attn_sa_b2(f, form ? form : sa_b2_form(L), s);
   } else {
     f.vrows_per_head = 0; f.ocol_per_head = 0;
     f.mulh = dev.up(hy.data(), hy.size()); f.ldmul = nv;
-    const int fm = form ? form : (na2_qtiles(L) == 4 ? 1 : 2);
-    if (nv <= 128) { if (fm == 1) launch_attn_na2<1, 4>(f, s); else launch_attn_na2<1>(f, s); }
-    else if (nv <= 256) { if (fm == 1) launch_attn_na2<2, 4>(f, s); else launch_attn_na2<2>(f, s); }
-    else if (fm == 1) launch_attn_na2<3, 4>(f, s);
-    else launch_attn_na2<3>(f, s);
+    launch_attn_na_b2(f, nv, form ? form : na_b2_form(L), s);
   }
   ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
   std::vector<bf16> ho((size_t)M * ldo);
@@ -374,15 +365,15 @@ int zv_mx8_gemm_check(int M, int N, int K, const float* A, const float* W, float
   std::vector<uint8_t> wq((size_t)Np * K), ws((size_t)Np * K / MX8_BLOCK);
   mx8_quantize_host(wp.data(), K, (int)Np, K, wq.data(), K, ws.data());
   ChkDev dev;
-  const bf16* dA = dev.up(ah.data(), ah.size());
   uint8_t* dAq = dev.make<uint8_t>((size_t)M * K);
   uint8_t* dAs = dev.make<uint8_t>((size_t)M * K / MX8_BLOCK);
   const uint8_t* dWq = dev.up(wq.data(), wq.size());
   const uint8_t* dWs = dev.up(ws.data(), ws.size());
   float* dC = dev.zero<float>((size_t)M * N);
-  hipLaunchKernelGGL(zv_mx8_pack_kernel, grid1d((long)M * (K / 8)), dim3(256), 0, s, dA, (long)K, (long)M,
-                     K, dAq, (long)K, dAs);
-  ZV_LAUNCH_CHECK();
+  Act a16;                                 // the bf16 operand and where its MX-fp8 copy goes
+  a16.h = dev.up(ah.data(), ah.size()); a16.ld = K;
+  a16.q = dAq; a16.qs = dAs; a16.ldq = K;
+  LinearPolicy().pack8(a16, M, K, s);
   GemmParams p{};
   p.M = M; p.N = N; p.K = K; p.nz2 = 1; p.Brows = (int)Np;
   p.Ah = reinterpret_cast<const bf16*>(dAq); p.lda = K; p.As = dAs; p.ldas = K / MX8_BLOCK;
@@ -429,7 +420,7 @@ int zv_linear_check(zv_linear_check_args* a) {
                  (a->Ctl != nullptr) == (split3 && wantT),
              "zv_linear_check: the transposed outputs");
   ZV_REQUIRE((form != ZV_LIN_NA || N % 48 == 0) && (!glu || N % 32 == 0), "zv_linear_check: NA / GLU widths");
-  // the fused GLU + depthwise conv: the conditions of zv_engine::layer's conv lambda
+  // the fused GLU + depthwise conv: its argument errors by name (LinearPolicy::glu_dw_fits decides below)
   const int dwk = a->dw_ks;
   ZV_REQUIRE(form != ZV_LIN_GLU_DW || (a->dw_w && a->dw_b && a->dw_L > 0 && M % a->dw_L == 0),
              "zv_linear_check: GLU_DW needs the taps, the conv bias and whole utterances of dw_L rows");
@@ -519,12 +510,9 @@ int zv_linear_check(zv_linear_check_args* a) {
     if (form == ZV_LIN_GLU_DW) {
       p.dw_w = dev.up(a->dw_w, (size_t)(N / 2) * dwk); p.dw_b = dev.up(a->dw_b, (size_t)(N / 2));
       p.dw_out = p.Ch; p.ld_dw = p.ldch; p.dw_L = a->dw_L;
-      ZV_REQUIRE((policy.res_counted & 8) && p.bias && !p.Cl && !p.As && p.lda % 8 == 0 && p.ldb % 8 == 0 &&
-                     p.lda >= round_up(p.K, GEMM_BK) && p.ldb >= round_up(p.K, GEMM_BK) && p.Brows >= p.N,
+      ZV_REQUIRE(policy.glu_dw_fits(p, N / 2, dwk),
                  "zv_linear_check: GLU_DW operands (the engine would take the unfused pair)");
-      if (dwk == 31) launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 31>(p, s, "glu_dw_check", false);
-      else if (dwk == 15) launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 15>(p, s, "glu_dw_check", false);
-      else launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 7>(p, s, "glu_dw_check", false);
+      policy.launch_glu_dw(p, dwk, s, "glu_dw_check");
     } else if (form == ZV_LIN_NA) {
       if (split3) policy.launch_na_in<3>(p, s); else policy.launch_na_in<1>(p, s);
     } else if (form == ZV_LIN_TRANS) {
@@ -566,9 +554,7 @@ int zv_ffn_check(zv_ffn_check_args* a) {
   const long n = (long)H * D;
   bf16* w1f = dev.make<bf16>((size_t)n);
   bf16* w2f = dev.make<bf16>((size_t)n);
-  hipLaunchKernelGGL(zv_ffn_pack_w1_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, L1.hi, (long)L1.Kpad, H, w1f);
-  hipLaunchKernelGGL(zv_ffn_pack_w2_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, L2.hi, (long)L2.Kpad, H, w2f);
-  ZV_LAUNCH_CHECK();
+  ffn_pack_weights(L1, L2, H, w1f, w2f, s);
   FfnParams q{};
   q.H = H; q.nseg = 1;
   FfnSeg& g = q.seg[0];
@@ -681,7 +667,7 @@ int zv_stackedge_check(zv_stackedge_check_args* a) {
   const long M = (long)B * L, Md = (long)B * dL;
   ChkDev dev;
   hipStream_t s = nullptr;
-  int rec[8] = {kind, 0, 0, 0, 0, 0, 0, 0};          // {kind, kernel form, grid blocks, block threads}
+  EdgeLaunch ran{};                                  // kernel form, grid blocks, block threads
   // a canary-guarded fp32 output of `n` rows of C, with `fill` (or nothing) in its interior
   auto up32 = [&](long n, const float* fill) {
     std::vector<float> hc(a->out, a->out + (size_t)(n + 2 * G) * C);
@@ -700,11 +686,8 @@ int zv_stackedge_check(zv_stackedge_check_args* a) {
     const float* in = dev.up(a->x, (size_t)M * C);
     const float* w = dev.up(a->w, (size_t)ds);
     float* d = up32(Md, nullptr);
-    const dim3 grid = grid1d(Md * C);
-    hipLaunchKernelGGL(zv_downsample_kernel, grid, dim3(256), 0, s, in, d + (size_t)G * C, B, L, dL, C, ds, w);
-    ZV_LAUNCH_CHECK();
+    ran = launch_downsample(in, d + (size_t)G * C, B, L, dL, C, ds, w, s);
     ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
-    rec[2] = (int)grid.x; rec[3] = 256;
     dev.down(a->out, d, (size_t)(Md + 2 * G) * C);
   } else if (kind == ZV_SE_UPSAMPLE) {
     ZV_REQUIRE(a->w && a->orig && a->out, "zv_stackedge_check: upsample needs the scale, orig and out");
@@ -712,29 +695,15 @@ int zv_stackedge_check(zv_stackedge_check_args* a) {
     const float* sc = dev.up(a->w, (size_t)C);
     float* o = up32(M, a->orig);                     // in place over orig, as the engine's stream
     float* main = o + (size_t)G * C;
-    if (C % 4 == 0 && 256 % (C / 4) == 0) {          // (zv_engine::zipformer's choice)
-      const long rows_per_block = 4L * (256 / (C / 4));
-      const dim3 grid((unsigned)((M + rows_per_block - 1) / rows_per_block));
-      hipLaunchKernelGGL(zv_upsample_combine_kernel, grid, dim3(256), 0, s, main, d, sc, main, B, L, dL, C, ds);
-      rec[1] = 0; rec[2] = (int)grid.x;
-    } else {
-      const dim3 grid = grid1d(M * C);
-      hipLaunchKernelGGL(zv_upsample_combine_any_kernel, grid, dim3(256), 0, s, main, d, sc, main, B, L, dL, C, ds);
-      rec[1] = 1; rec[2] = (int)grid.x;
-    }
-    ZV_LAUNCH_CHECK();
+    ran = launch_upsample_combine(main, d, sc, main, B, L, dL, C, ds, s);
     ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
-    rec[3] = 256;
     dev.down(a->out, o, (size_t)(M + 2 * G) * C);
   } else if (kind == ZV_SE_MASK) {
     ZV_REQUIRE(a->mask && a->mout, "zv_stackedge_check: the mask and its output");
     const uint8_t* in = dev.up(a->mask, (size_t)M);
     uint8_t* o = dev.up(a->mout, (size_t)(Md + 2 * G));
-    const dim3 grid = grid1d(Md);
-    hipLaunchKernelGGL(zv_mask_downsample_kernel, grid, dim3(256), 0, s, in, o + G, B, L, dL, ds);
-    ZV_LAUNCH_CHECK();
+    ran = launch_mask_downsample(in, o + G, B, L, dL, ds, s);
     ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
-    rec[2] = (int)grid.x; rec[3] = 256;
     dev.down(a->mout, o, (size_t)(Md + 2 * G));
   } else if (kind == ZV_SE_ENTRY) {
     ZV_REQUIRE(a->h && a->h2 && a->ldact >= C && a->ldact % 4 == 0 && (!a->rowvec || a->rows_per_group > 0),
@@ -743,16 +712,12 @@ int zv_stackedge_check(zv_stackedge_check_args* a) {
     const float* rv = a->rowvec ? dev.up(a->rowvec, (size_t)cdiv(M, a->rows_per_group) * C) : nullptr;
     float* cur = a->out ? up32(M, nullptr) : nullptr;
     bf16 *h = up16(a->h, M), *l = up16(a->l, M), *h2 = up16(a->h2, M), *l2 = up16(a->l2, M);
-    const dim3 grid = grid1d(M * C);
-    hipLaunchKernelGGL(zv_stack_entry_kernel, grid, dim3(256), 0, s, src, rv, cur ? cur + (size_t)G * C : nullptr,
-                       in16(h), in16(l), in16(h2), in16(l2), (long)a->ldact, M, C,
-                       rv ? a->rows_per_group : 1);
-    ZV_LAUNCH_CHECK();
+    ran = launch_stack_entry(src, rv, cur ? cur + (size_t)G * C : nullptr, in16(h), in16(l), in16(h2), in16(l2),
+                             a->ldact, M, C, rv ? a->rows_per_group : 1, s);
     ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
-    rec[2] = (int)grid.x; rec[3] = 256;
     if (cur) dev.down(a->out, cur, (size_t)(M + 2 * G) * C);
     down16(a->h, h, M); down16(a->l, l, M); down16(a->h2, h2, M); down16(a->l2, l2, M);
-  } else {   // BiasNorm + bypass, in place over orig (zv_engine::layer's launch)
+  } else {   // BiasNorm + bypass, in place over orig
     ZV_REQUIRE(a->nb && a->w && a->orig && a->out && a->h && a->ldact >= C && a->ldact % 4 == 0 &&
                    (!a->l2 || a->h2) && (!a->rowvec || a->rows_per_group > 0),
                "zv_stackedge_check: BiasNorm needs nb, the bypass scale, orig, out and h");
@@ -770,19 +735,8 @@ int zv_stackedge_check(zv_stackedge_check_args* a) {
     uint8_t* qs2 = a->q2 ? dev.up(a->qs2, (size_t)(M + 2 * G) * ldqs) : nullptr;
     uint8_t* q2i = q2 ? q2 + (size_t)G * a->ldq : nullptr;
     uint8_t* qs2i = qs2 ? qs2 + (size_t)G * ldqs : nullptr;
-    const int rpg = rv ? a->rows_per_group : 1;
-    if (C == 512) {
-      hipLaunchKernelGGL(zv_biasnorm_bypass_v_kernel<2>, dim3(cdiv(M, 8)), dim3(512), 0, s, x, src, nb, a->log_scale,
-                         byp, src, in16(h), in16(l), (float*)nullptr, in16(h2), in16(l2), (long)a->ldact, rv, rpg,
-                         M, q2i, qs2i, (long)a->ldq);
-      rec[1] = 1; rec[2] = (int)cdiv(M, 8); rec[3] = 512;
-    } else {
-      hipLaunchKernelGGL(zv_biasnorm_bypass_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, x, src, nb, a->log_scale,
-                         byp, src, in16(h), in16(l), (float*)nullptr, in16(h2), in16(l2), (long)a->ldact, rv, rpg,
-                         M, C, q2i, qs2i, (long)a->ldq);
-      rec[1] = 0; rec[2] = (int)cdiv(M, 4); rec[3] = 256;
-    }
-    ZV_LAUNCH_CHECK();
+    ran = launch_biasnorm_bypass(x, src, nb, a->log_scale, byp, src, in16(h), in16(l), in16(h2), in16(l2), a->ldact,
+                                 rv, rv ? a->rows_per_group : 1, M, C, q2i, qs2i, a->ldq, s);
     ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
     dev.down(a->out, o, (size_t)(M + 2 * G) * C);
     down16(a->h, h, M); down16(a->l, l, M); down16(a->h2, h2, M); down16(a->l2, l2, M);
@@ -791,6 +745,7 @@ int zv_stackedge_check(zv_stackedge_check_args* a) {
       dev.down(a->qs2, qs2, (size_t)(M + 2 * G) * ldqs);
     }
   }
+  const int rec[8] = {kind, ran.form, ran.blocks, ran.threads, 0, 0, 0, 0};
   memcpy(a->launch, rec, sizeof(rec));
   a->num_cus = zv_num_cus();
   ZV_API_END
@@ -935,9 +890,7 @@ void bv_check_run(zv_bigvgan_check_args* a) {
       Pb = P;
     }
     float* o = out32(M, Co);
-    hipLaunchKernelGGL(zv_bv_convt_gather_kernel, grid1d(M * Co), dim3(256), 0, s, Pb, ldp, bias, lens, a->scale,
-                       B, L, Ls, u, k, (k - u) / 2, Co, Lo_s, o + (size_t)G * Co);
-    ZV_LAUNCH_CHECK();
+    BvHost::convt_gather(Pb, bias, lens, a->scale, B, L, Ls, u, k, Co, Lo_s, o + (size_t)G * Co, s);
     ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
     down32(o, M, Co);
   } else if (kind == ZV_BV_AVG) {
@@ -949,22 +902,20 @@ void bv_check_run(zv_bigvgan_check_args* a) {
     const size_t n16 = (size_t)(M + 2 * G) * a->ld;
     uint16_t* oh = a->oh ? dev.up(a->oh, n16) : nullptr;
     uint16_t* ol = a->ol ? dev.up(a->ol, n16) : nullptr;
-    hipLaunchKernelGGL(zv_bv_avg_kernel, grid1d(M * C), dim3(256), 0, s, y0, y1, y2, a->n, M, C, o + (size_t)G * C,
-                       oh ? reinterpret_cast<bf16*>(oh) + (size_t)G * a->ld : nullptr,
-                       ol ? reinterpret_cast<bf16*>(ol) + (size_t)G * a->ld : nullptr, (long)a->ld);
-    ZV_LAUNCH_CHECK();
+    Act xo;
+    xo.ld = a->ld;
+    if (oh) xo.h = reinterpret_cast<bf16*>(oh) + (size_t)G * a->ld;
+    if (ol) xo.l = reinterpret_cast<bf16*>(ol) + (size_t)G * a->ld;
+    BvHost::avg(y0, y1, y2, a->n, M, C, o + (size_t)G * C, xo, s);
     ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
     down32(o, M, C);
     if (oh) dev.down(a->oh, oh, n16);
     if (ol) dev.down(a->ol, ol, n16);
   } else if (kind == ZV_BV_POST) {
-    const size_t lds = BvHost::post_lds(C);
     const float* x = dev.up(a->x, (size_t)B * a->Ls * C);
     const float* w = dev.up(a->w, (size_t)C * 7);
     float* o = out32((long)B * L, 1);
-    hipLaunchKernelGGL(zv_bv_post_kernel, dim3(B * cdiv(L, BV_POST_T)), dim3(BV_POST_T), lds, s, x, lens, a->scale, B,
-                       L, a->Ls, C, w, a->bias0, a->flag, o + G);
-    ZV_LAUNCH_CHECK();
+    BvHost::post(x, lens, a->scale, B, L, a->Ls, C, w, a->bias0, a->flag, o + G, s);
     ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
     down32(o, (long)B * L, 1);
   } else if (kind == ZV_BV_IM2COL) {
@@ -979,9 +930,7 @@ void bv_check_run(zv_bigvgan_check_args* a) {
     A.ld = ld;
     A.h = reinterpret_cast<bf16*>(oh) + (size_t)G * ld;
     if (ol) A.l = reinterpret_cast<bf16*>(ol) + (size_t)G * ld;
-    hipLaunchKernelGGL(zv_voc_im2col_kernel, grid1d(M * K), dim3(256), 0, s, in, a->layout, a->div, a->sub, lens, B, L,
-                       C, a->ks, A.h, A.l, ld);
-    ZV_LAUNCH_CHECK();
+    launch_voc_im2col(in, a->layout, a->div, a->sub, lens, B, L, C, a->ks, A, s);
     float* o = nullptr;
     if (a->flag) {
       const std::vector<float> w2 = BvHost::conv_rows(a->w, a->Cout, C, a->ks, C);

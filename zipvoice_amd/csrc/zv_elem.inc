@@ -796,6 +796,66 @@ __global__ void zv_mask_downsample_kernel(const uint8_t* in, uint8_t* out, int B
   out[idx] = in[(long)b * L + (long)i * ds];
 }
 
+// ---- the stack-boundary launches (zv_engine and zv_stackedge_check) ---------
+// each returns what it launched: kernel form (0 where there is one), grid blocks, block threads
+struct EdgeLaunch { int form, blocks, threads; };
+
+static EdgeLaunch launch_downsample(const float* in, float* out, int B, int L, int dL, int C, int ds,
+                                    const float* w, hipStream_t s) {
+  const dim3 grid = grid1d((long)B * dL * C);
+  hipLaunchKernelGGL(zv_downsample_kernel, grid, dim3(256), 0, s, in, out, B, L, dL, C, ds, w);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_mask_downsample(const uint8_t* in, uint8_t* out, int B, int L, int dL, int ds,
+                                         hipStream_t s) {
+  const dim3 grid = grid1d((long)B * dL);
+  hipLaunchKernelGGL(zv_mask_downsample_kernel, grid, dim3(256), 0, s, in, out, B, L, dL, ds);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+// form 0: row blocks of whole rows (f32x4 per thread); 1: any other width (e.g. 384, 192)
+static EdgeLaunch launch_upsample_combine(const float* orig, const float* d, const float* sc, float* out,
+                                          int B, int L, int dL, int C, int ds, hipStream_t s) {
+  const long M = (long)B * L;
+  const bool rowwise = C % 4 == 0 && 256 % (C / 4) == 0;
+  const long rows_per_block = rowwise ? 4L * (256 / (C / 4)) : 0;
+  const dim3 grid = rowwise ? dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)) : grid1d(M * C);
+  if (rowwise)
+    hipLaunchKernelGGL(zv_upsample_combine_kernel, grid, dim3(256), 0, s, orig, d, sc, out, B, L, dL, C, ds);
+  else
+    hipLaunchKernelGGL(zv_upsample_combine_any_kernel, grid, dim3(256), 0, s, orig, d, sc, out, B, L, dL, C, ds);
+  ZV_LAUNCH_CHECK();
+  return {rowwise ? 0 : 1, (int)grid.x, 256};
+}
+static EdgeLaunch launch_stack_entry(const float* src, const float* rowvec, float* cur, bf16* srch, bf16* srcl,
+                                     bf16* curh, bf16* curl, long ldact, long M, int C, int rows_per_group,
+                                     hipStream_t s) {
+  const dim3 grid = grid1d(M * C);
+  hipLaunchKernelGGL(zv_stack_entry_kernel, grid, dim3(256), 0, s, src, rowvec, cur, srch, srcl, curh, curl,
+                     ldact, M, C, rows_per_group);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+// form 1: C = 512, all loads of a row up front; 0: the two-pass kernel
+static EdgeLaunch launch_biasnorm_bypass(const float* x, const float* orig, const float* nb, float log_scale,
+                                         const float* c, float* out, bf16* outh, bf16* outl, bf16* out2h,
+                                         bf16* out2l, long ldact, const float* rowvec, int rows_per_group,
+                                         long M, int C, uint8_t* q2, uint8_t* qs2, long ldq, hipStream_t s) {
+  const bool v = C == 512;
+  const int rows = v ? 8 : 4;                        // one wave per row
+  if (v)
+    hipLaunchKernelGGL(zv_biasnorm_bypass_v_kernel<2>, dim3(cdiv(M, rows)), dim3(64 * rows), 0, s, x, orig, nb,
+                       log_scale, c, out, outh, outl, (float*)nullptr, out2h, out2l, ldact, rowvec,
+                       rows_per_group, M, q2, qs2, ldq);
+  else
+    hipLaunchKernelGGL(zv_biasnorm_bypass_kernel, dim3(cdiv(M, rows)), dim3(64 * rows), 0, s, x, orig, nb,
+                       log_scale, c, out, outh, outl, (float*)nullptr, out2h, out2l, ldact, rowvec,
+                       rows_per_group, M, C, q2, qs2, ldq);
+  ZV_LAUNCH_CHECK();
+  return {v ? 1 : 0, cdiv(M, rows), 64 * rows};
+}
+
 // duplicate a (B, L) mask for the CFG batch
 __global__ void zv_copy_u8_kernel(const uint8_t* in, uint8_t* out, long n, int copies) {
   const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;

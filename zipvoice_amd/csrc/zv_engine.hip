@@ -135,7 +135,7 @@ struct Workspace {
   // flag word per CU (zero between launches) and the spin-timeout counter
   DBuf ffn_part, ffn_flag;
   // per-stack positional projections, kept across the Euler steps of one solve (they depend on
-  // the stack's length and weights only; Engine::posp_reuse)
+  // the stack's length and weights only; Pass::posp_reuse)
   static constexpr int POSP_STACKS = 8;
   DBuf posPs[POSP_STACKS];
   // what each posPs slot holds (written with it): a later step reuses it only on a match
@@ -152,6 +152,18 @@ struct Workspace {
       s += b->bytes();
     return s;
   }
+};
+
+// what a forward pass is told by its caller (decoder / text_encode fill it; zipformer, stack and
+// layer read it)
+struct Pass {
+  bool io_split = false;     // ZV_MIXED's decoder: split in/out projections, weight-split
+                             // attention-score projections
+  bool posp_reuse = false;   // the stacks' posP buffers hold this solve's values (euler_loop's
+                             // later steps)
+  long batch_rows = 0;       // the whole batch's rows (N) while a split decoder runs one row block
+                             // (0: not split): the fused / unfused FeedForward choice follows
+                             // the batch, not the row block
 };
 
 // Engine streams come from a per-device process-wide pool of stream sets: an engine takes a set
@@ -235,9 +247,8 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   // C3 / C4 have no stack in [10k, 15k) (profiles/r05_ffn_min_rows_ab.txt)
   long ffn_min_rows = 15000;
   int fp8_fuse = 7;                // ZV_FP8_FUSE (fp8 mode): which bf16 producers write the fp8 copy
-                                   // themselves (2 depthwise conv, 4 BiasNorm; bit 1 is unused since
-                                   // the wave-specialised epilogue's removal); the others are followed
-                                   // by the pack kernel
+                                   // themselves (2 depthwise conv, 4 BiasNorm; no code reads bit 1);
+                                   // the others are followed by the pack kernel
   int sa_tp = 1;                   // ZV_SA_TP: 16-bit modes' SelfAttention with the positional
                                    // term on the MFMA chain (zv_attn_sa_tp_kernel), the head-0
                                    // stats / NonlinAttention scoring too; 0 = VALU forms
@@ -312,17 +323,12 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   // cross-branch waits), while single-stream shapes (one sentence) are launch-bound and
   // need the graph
   int graph_mode = 2;
-  bool posp_reuse = false;         // euler_loop: the stacks' posP buffers hold this solve's values
-  bool io_split = false;           // set per decoder call: ZV_MIXED's split in/out projections
-                                   // and attention-score projections
 
   // ---------------------------------------------------------------- fused FeedForward sites
   // ZV_FFN_PERSIST (default 1): fused FeedForward launches on the persistent line schedule
   // (zv_ffn.inc; results equal to one row block per block bit for bit).  The scratch is sized for
   // one line per CU; launch_ffn never launches more blocks than that (it checks)
   int ffn_persist = 1;
-  long dec_rows_N = 0;             // the whole batch's rows while a split decoder runs (0: not split):
-                                   // the fused / unfused choice follows the batch, not the row block
   void attach_ffn_scratch(FfnParams& q, Workspace& ws) {
     if (!ffn_persist) return;
     const int cus = zv_num_cus();
@@ -508,11 +514,13 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     return L;
   }
 
+  // is_decoder: the flow-matching decoder (the fp8 mode's fp8 weight copies, the fused FeedForward's
+  // packed copies and conv_sa_out belong to it; the text encoder has none)
   void build_zipformer(ZipformerW& Z, const std::string& pre, int dim, int ff, int heads,
                        const std::vector<int>& ds, const std::vector<int>& layers,
                        const std::vector<int>& ks, std::vector<int> in_dims,
                        std::vector<int> out_dims, bool two_stream, int temb_dim, bool guid,
-                       bool fp8_layers = false, bool b2 = false) {
+                       bool is_decoder = false, bool b2 = false) {
     Z.dim = dim; Z.ff = ff; Z.heads = heads; Z.b2 = b2;
     Z.qd = cfg.query_head_dim; Z.pd = cfg.pos_head_dim; Z.vd = cfg.value_head_dim;
     Z.pos_dim = cfg.pos_dim; Z.temb_dim = temb_dim;
@@ -572,18 +580,14 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
         const int hs[3] = {ff * 3 / 4, ff, ff * 5 / 4};
         for (int f = 0; f < 3; ++f) {
           std::string fp = lp + "feed_forward" + std::to_string(f + 1) + ".";
-          W.ff_in[f] = make_linear(fp + "in_proj", hs[f], dim, true, false, nullptr, fp8_layers);
-          W.ff_out[f] = make_linear(fp + "out_proj", dim, hs[f], true, false, nullptr, fp8_layers);
-          if (ffn_fused && fp8_layers && dim == FFN_D && hs[f] % (2 * FFN_HC) == 0 &&
+          W.ff_in[f] = make_linear(fp + "in_proj", hs[f], dim, true, false, nullptr, is_decoder);
+          W.ff_out[f] = make_linear(fp + "out_proj", dim, hs[f], true, false, nullptr, is_decoder);
+          if (ffn_fused && is_decoder && dim == FFN_D && hs[f] % (2 * FFN_HC) == 0 &&
               (cfg.precision == ZV_BF16 || cfg.precision == ZV_MIXED)) {
             const long n = (long)hs[f] * FFN_D;
             W.ffn_w1f[f] = store.dalloc<bf16>(n);
             W.ffn_w2f[f] = store.dalloc<bf16>(n);
-            hipLaunchKernelGGL(zv_ffn_pack_w1_kernel, dim3(cdiv(n, 256)), dim3(256), 0, 0, W.ff_in[f].hi,
-                               (long)W.ff_in[f].Kpad, hs[f], W.ffn_w1f[f]);
-            hipLaunchKernelGGL(zv_ffn_pack_w2_kernel, dim3(cdiv(n, 256)), dim3(256), 0, 0, W.ff_out[f].hi,
-                               (long)W.ff_out[f].Kpad, hs[f], W.ffn_w2f[f]);
-            ZV_LAUNCH_CHECK();
+            ffn_pack_weights(W.ff_in[f], W.ff_out[f], hs[f], W.ffn_w1f[f], W.ffn_w2f[f], nullptr);
             ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
           }
         }
@@ -591,13 +595,13 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
         ZV_REQUIRE(hid % 16 == 0 && dim % 64 == 0, "encoder dim must be a multiple of 64");
         const std::vector<int> pna = perm_na(hid), pglu = perm_glu(dim);
         W.na_in = make_linear(lp + "nonlin_attention.in_proj", 3 * hid, dim, true, false, &pna);
-        W.na_out = make_linear(lp + "nonlin_attention.out_proj", dim, hid, true, false, nullptr, fp8_layers);
+        W.na_out = make_linear(lp + "nonlin_attention.out_proj", dim, hid, true, false, nullptr, is_decoder);
         W.ks = ks[s];
         for (int c = 0; c < 2; ++c) {
           std::string cp = lp + "conv_module" + std::to_string(c + 1) + ".";
-          W.conv_in[c] = make_linear(cp + "in_proj", 2 * dim, dim, true, false, &pglu, fp8_layers);
-          W.conv_out[c] = make_linear(cp + "out_proj", dim, dim, true, false, nullptr, fp8_layers);
-          if (fp8_layers && (cfg.precision == ZV_BF16 || cfg.precision == ZV_MIXED))
+          W.conv_in[c] = make_linear(cp + "in_proj", 2 * dim, dim, true, false, &pglu, is_decoder);
+          W.conv_out[c] = make_linear(cp + "out_proj", dim, dim, true, false, nullptr, is_decoder);
+          if (is_decoder && (cfg.precision == ZV_BF16 || cfg.precision == ZV_MIXED))
             W.conv_sa_out[c] = make_linear_kcat(cp + "out_proj", dim,
                                                 lp + "self_attn" + std::to_string(c + 1) + ".out_proj",
                                                 heads * Z.vd, dim, cfg.precision == ZV_MIXED && mixed_sa);
@@ -639,7 +643,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     std::vector<int> out_dims = stereo() ? std::vector<int>{2 * F, F} : std::vector<int>{F};
     build_zipformer(dec, "fm_decoder.", cfg.fm_decoder_dim, cfg.fm_decoder_feedforward_dim,
                     cfg.fm_decoder_num_heads, ds, nl, ks, in_dims, out_dims, stereo(),
-                    cfg.time_embed_dim, distill(), /*fp8_layers=*/true, attn_b2_dec);
+                    cfg.time_embed_dim, distill(), /*is_decoder=*/true, attn_b2_dec);
     build_zipformer(txt, "text_encoder.", cfg.text_encoder_dim, cfg.text_encoder_feedforward_dim,
                     cfg.text_encoder_num_heads, {1}, {cfg.text_encoder_num_layers},
                     {cfg.text_encoder_cnn_module_kernel}, {cfg.text_embed_dim}, {F}, false, -1,
@@ -701,47 +705,28 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   bool fp8_mode() const { return cfg.precision == ZV_FP8; }
 
   // ---------------------------------------------------------------- fused attention consumers
-  // NonlinAttention's head-0 consumer, by the hidden width: the second-generation kernel (a2), the
-  // Toeplitz MFMA scoring (tp_na) or the VALU form
+  // NonlinAttention's head-0 consumer: the second-generation kernel (a2), the Toeplitz MFMA scoring
+  // (tp_na) or the VALU form
+  template <int SPLIT, int TPM>
+  static void attn_na_v1(const FlashParams& f, int hid, hipStream_t s) {   // by the hidden width
+    constexpr int QTILES = SPLIT == 3 ? 4 : 8;
+    if (hid <= 128) launch_attn_na<SPLIT, 1, QTILES, TPM>(f, s);
+    else if (hid <= 256) launch_attn_na<SPLIT, 2, QTILES, TPM>(f, s);
+    else launch_attn_na<SPLIT, 3, QTILES, TPM>(f, s);
+  }
   template <int SPLIT>
   void attn_na(const FlashParams& f, int hid, bool a2, bool tp_na, hipStream_t s) {
-    constexpr int QTILES = SPLIT == 3 ? 4 : 8;
     if constexpr (SPLIT == 1) {
-      if (a2) {
-        const bool q4 = na2_qtiles(f.L) == 4;
-        if (hid <= 128) { if (q4) launch_attn_na2<1, 4>(f, s); else launch_attn_na2<1>(f, s); }
-        else if (hid <= 256) { if (q4) launch_attn_na2<2, 4>(f, s); else launch_attn_na2<2>(f, s); }
-        else if (q4) launch_attn_na2<3, 4>(f, s);
-        else launch_attn_na2<3>(f, s);
-        return;
-      }
-      if (tp_na) {
-        if (hid <= 128) launch_attn_na<1, 1, QTILES, 1>(f, s);
-        else if (hid <= 256) launch_attn_na<1, 2, QTILES, 1>(f, s);
-        else launch_attn_na<1, 3, QTILES, 1>(f, s);
-        return;
-      }
+      if (a2) return launch_attn_na_b2(f, hid, na_b2_form(f.L), s);
+      if (tp_na) return attn_na_v1<1, 1>(f, hid, s);
     }
-    if (hid <= 128) launch_attn_na<SPLIT, 1, QTILES>(f, s);
-    else if (hid <= 256) launch_attn_na<SPLIT, 2, QTILES>(f, s);
-    else launch_attn_na<SPLIT, 3, QTILES>(f, s);
+    attn_na_v1<SPLIT, 0>(f, hid, s);
   }
   // SelfAttention's consumer
   template <int SPLIT>
   void attn_sa(const FlashParams& f, bool a2, hipStream_t s) {
     if constexpr (SPLIT == 1) {
-      if (a2) {
-        // LDS-staged K / V (sa3) while two blocks fit a CU; the register-fed form past that
-        switch (sa3_qpw(f.L)) {
-          case 4: launch_attn_sa3<4>(f, s); break;
-          case 3: launch_attn_sa3<3>(f, s); break;
-          case 2: launch_attn_sa3<2>(f, s); break;
-          default:
-            if (sa2_qpw(f.L) == 3) launch_attn_sa2<3, 1>(f, s);
-            else launch_attn_sa2<2>(f, s);
-        }
-        return;
-      }
+      if (a2) return launch_attn_sa_b2(f, sa_b2_form(f.L), s);
       if (sa_tp) {                 // positional term as a Toeplitz MFMA product
         if (sa_tp == 3) launch_attn_sa_tp<0, 1>(f, s);   // A/B: the compiler's one-wave register budget
         else launch_attn_sa_tp<0>(f, s);
@@ -756,14 +741,14 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   // src/src_a: layer input (kept as src_orig, overwritten with the output);
   // cur/cur_a: src + temb on entry (working residual stream).
   template <int SPLIT>
-  void layer(const ZipformerW& Z, const LayerW& W, Workspace& ws, float* src, Act src_a,
-             float* cur, Act cur_a, int B, int L, const uint8_t* pad, const float* posP,
+  void layer(const Pass& pass, const ZipformerW& Z, const LayerW& W, Workspace& ws, float* src,
+             Act src_a, float* cur, Act cur_a, int B, int L, const uint8_t* pad, const float* posP,
              const float* temb, bool has_next, hipStream_t s, bool fresh8 = false) {
     const bool split = SPLIT == 3;
     const long M = (long)B * L;
     // the batch's rows: the fused / unfused FeedForward choice must not depend on how the decoder
     // split its rows over streams (every row block makes the same choice; bitwise equal to one stream)
-    const long Mtot = dec_rows_N > 0 ? dec_rows_N * (long)L : M;
+    const long Mtot = pass.batch_rows > 0 ? pass.batch_rows * (long)L : M;
     const int D = Z.dim, H = Z.heads;
     const long Lpad = round_up(L, 64);
     const char* tag_att = split ? "gemm_attn_fp32" : "gemm_attn_bf16";
@@ -775,7 +760,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       // mixed mode: the attention-score projection as a weight-split product (attn_in_wsplit;
       // the fully split form is retired, zv_linear.inc); q, k, p stay 16-bit
       Out o; o.act = qkp;
-      if (SPLIT == 1 && io_split) attn_in_wsplit(W.attn_in, src_a, M, o, s);
+      if (SPLIT == 1 && pass.io_split) attn_in_wsplit(W.attn_in, src_a, M, o, s);
       else linear<SPLIT>(W.attn_in, src_a, M, o, s);
     }
     // head-0 scoring of the stats / NonlinAttention pair: Toeplitz MFMA form in the 16-bit modes
@@ -813,8 +798,8 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     }
     // fp8 mode: the working stream also carries an MX-fp8 copy (the A operand of the fp8
     // feed-forward / convolution in-projections), written by every producer of the stream:
-    // the residual linears' epilogues (fp8 and wave-specialised), the previous layer's
-    // BiasNorm (fresh8); packed here only at a stack's first layer
+    // the residual linears' epilogues, the previous layer's BiasNorm (fresh8); packed here only
+    // at a stack's first layer
     const bool f8 = SPLIT == 1 && fp8_mode() && W.ff_in[0].q8 != nullptr;
     Act c8;
     if (f8) {
@@ -824,15 +809,20 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     }
     Out res;                       // cur = cur + module(cur), with the hi/lo copy
     res.C = cur; res.ldc = D; res.resid = cur; res.act = cur_a;
+    // fused FeedForward module f on the working stream: its operands (a site adds its epilogue's)
+    auto ffn_params = [&](int f) {
+      FfnParams q{};
+      q.H = W.ff_in[f].N; q.nseg = 1;
+      q.seg[0].M = (int)M; q.seg[0].X = cur_a.h; q.ldx = cur_a.ld;
+      q.W1f = W.ffn_w1f[f]; q.b1 = W.ff_in[f].b; q.W2f = W.ffn_w2f[f]; q.b2 = W.ff_out[f].b;
+      return q;
+    };
     auto ff = [&](int f, const Out& oe) {
       if constexpr (SPLIT == 1) {
         if (ffn_fused && W.ffn_w1f[f] && !(f8 && W.ff_in[f].q8) && oe.C && oe.resid &&
             !oe.act.l && !oe.residh && Mtot >= ffn_min_rows && cur_a.ld % 8 == 0) {
-          FfnParams q{};
-          q.H = W.ff_in[f].N; q.nseg = 1;
+          FfnParams q = ffn_params(f);
           FfnSeg& g = q.seg[0];
-          g.M = (int)M; g.X = cur_a.h; q.ldx = cur_a.ld;
-          q.W1f = W.ffn_w1f[f]; q.b1 = W.ff_in[f].b; q.W2f = W.ffn_w2f[f]; q.b2 = W.ff_out[f].b;
           g.resid = oe.resid; g.C = oe.C; q.ldc = oe.ldc; g.Ch = oe.act.h; q.ldch = oe.act.ld;
           g.rowvec = oe.rowvec; q.rowvec_ld = oe.rowvec_ld; q.rows_per_group = oe.rows_per_group;
           g.orig = oe.orig; q.byp = oe.byp;
@@ -895,7 +885,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     Act dwo;
     if (kcat) dwo = ws.dwo.get(M, round_up(W.conv_sa_out[0].K, 64), false);
     // fp16 parity mode's split SelfAttention products (mixed_sa; the weights were built for it)
-    const bool sa_split = kcat && io_split && W.conv_sa_out[0].K == D + 3 * H * Z.vd;
+    const bool sa_split = kcat && pass.io_split && W.conv_sa_out[0].K == D + 3 * H * Z.vd;
     ZV_REQUIRE(!kcat || sa_split || W.conv_sa_out[0].K == D + H * Z.vd, "conv + SelfAttention out-projection width");
     auto self_attn = [&](int a) {                     // SelfAttention (:564-570, :600-606)
       const int vd = Z.vd, HV = H * vd;
@@ -931,41 +921,29 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     };
     auto conv = [&](int c) {                          // ConvolutionModule (:1638-1680)
       const bool g8 = f8 && W.conv_in[c].q8;
+      Act dw = kcat ? dwo : ws.dw.get(M, D, split, f8, D);
+      bool fused = false;
       if constexpr (SPLIT == 1) {
         // in_proj + GLU + masked_fill + depthwise conv + SwooshR in one launch: the GLU output
         // never reaches HBM (zv_gemm256.inc, g256_epi_glu_dw)
-        const int ks = W.ks;
-        if (glu_dw && !f8 && D == 512 && W.conv_in[c].N == 2 * D && (ks == 7 || ks == 15 || ks == 31) &&
-            (res_counted & 8)) {
-          Act dw = kcat ? dwo : ws.dw.get(M, D, split, f8, D);
+        if (glu_dw && !f8) {
           GemmParams p = gp_linear(W.conv_in[c], cur_a, M);
           p.Ch = dw.h; p.ldch = dw.ld; p.rowmask = pad;
           p.dw_w = W.dw_w[c]; p.dw_b = W.dw_b[c]; p.dw_out = dw.h; p.ld_dw = dw.ld; p.dw_L = L;
-          if (p.bias && !p.Cl && !p.As && p.lda % 8 == 0 && p.ldb % 8 == 0 && p.lda >= round_up(p.K, GEMM_BK) &&
-              p.ldb >= round_up(p.K, GEMM_BK) && p.Brows >= p.N && dw.ld % 8 == 0) {
-            if (ks == 31) launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 31>(p, s, "gemm_bf16_glu_dw", false);
-            else if (ks == 15) launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 15>(p, s, "gemm_bf16_glu_dw", false);
-            else launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 7>(p, s, "gemm_bf16_glu_dw", false);
-            if (kcat) {                               // cur += [dw | o] . [conv_out | sa_out]^T + temb
-              Out e = res;
-              e.rowvec = temb; e.rowvec_ld = D; e.rows_per_group = L;
-              linear<SPLIT>(W.conv_sa_out[c], dw, M, e, s);
-            } else {
-              linear<SPLIT>(W.conv_out[c], dw, M, res, s);
-            }
-            return;
-          }
+          fused = glu_dw_fits(p, D, W.ks);
+          if (fused) launch_glu_dw(p, W.ks, s, "gemm_bf16_glu_dw");
         }
       }
-      Act g = ws.glu.get(M, D, split);
-      GemmParams p = g8 ? gp_linear8(W.conv_in[c], cur_a, M) : gp_linear(W.conv_in[c], cur_a, M);
-      p.Ch = g.h; p.Cl = g.l; p.ldch = g.ld; p.rowmask = pad;
-      launch_glu_in<SPLIT>(p, g8, s);
-      Act dw = kcat ? dwo : ws.dw.get(M, D, split, f8, D);
-      const bool dq = f8 && (fp8_fuse & 2);
-      launch_dwconv(g.h, g.l, g.ld, W.dw_w[c], W.dw_b[c], dw.h, dw.l, dw.ld, B, L, D, W.ks, s,
-                    dq ? dw.q : nullptr, dw.qs, dw.ldq);
-      if (f8 && !dq) pack8(dw, M, D, s);
+      if (!fused) {
+        Act g = ws.glu.get(M, D, split);
+        GemmParams p = g8 ? gp_linear8(W.conv_in[c], cur_a, M) : gp_linear(W.conv_in[c], cur_a, M);
+        p.Ch = g.h; p.Cl = g.l; p.ldch = g.ld; p.rowmask = pad;
+        launch_glu_in<SPLIT>(p, g8, s);
+        const bool dq = f8 && (fp8_fuse & 2);
+        launch_dwconv(g.h, g.l, g.ld, W.dw_w[c], W.dw_b[c], dw.h, dw.l, dw.ld, B, L, D, W.ks, s,
+                      dq ? dw.q : nullptr, dw.qs, dw.ldq);
+        if (f8 && !dq) pack8(dw, M, D, s);
+      }
       if (kcat) {                                     // cur += [dw | o] . [conv_out | sa_out]^T + temb
         Out e = res;
         e.rowvec = temb; e.rowvec_ld = D; e.rows_per_group = L;
@@ -988,11 +966,8 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     const bool ffn_norm = SPLIT == 1 && ffn_fused >= 2 && W.ffn_w1f[2] && !f8 && D == FFN_D &&
                           Mtot >= ffn_min_rows && cur_a.ld == src_a.ld && cur_a.ld % 8 == 0;
     if (ffn_norm) {
-      FfnParams q{};
-      q.H = W.ff_in[2].N; q.nseg = 1;
+      FfnParams q = ffn_params(2);
       FfnSeg& g = q.seg[0];
-      g.M = (int)M; g.X = cur_a.h; q.ldx = cur_a.ld;
-      q.W1f = W.ffn_w1f[2]; q.b1 = W.ff_in[2].b; q.W2f = W.ffn_w2f[2]; q.b2 = W.ff_out[2].b;
       g.resid = cur; g.orig = src; g.C = src; q.ldc = D;
       g.Ch = src_a.h; g.Cl = src_a.l; q.ldch = src_a.ld;
       q.byp = W.bypass; q.nb = W.norm_bias; q.log_scale = W.norm_log_scale;
@@ -1005,41 +980,26 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       ff(2, e);
     }
     // BiasNorm + bypass -> src; next layer's working copy (src + temb) -> cur
-    if (ffn_norm) {
-    } else {
+    if (!ffn_norm) {
       // fp8: the next layer's working stream's fp8 copy as well (its fresh8)
       const bool q2 = f8 && has_next && (fp8_fuse & 4);
       ZV_REQUIRE(!q2 || D % 256 == 0, "fp8 BiasNorm copy: channels a multiple of 256");
-      if (D == 512)   // all loads of a row up front
-        hipLaunchKernelGGL(zv_biasnorm_bypass_v_kernel<2>, dim3(cdiv(M, 8)), dim3(512), 0, s, cur, src,
-                           W.norm_bias, W.norm_log_scale, W.bypass, src, src_a.h, src_a.l,
-                           (float*)nullptr, has_next ? cur_a.h : nullptr,
-                           has_next ? cur_a.l : nullptr, (long)D, temb, L, M,
-                           q2 ? c8.q : nullptr, q2 ? c8.qs : nullptr, q2 ? c8.ldq : 0L);
-      else
-        hipLaunchKernelGGL(zv_biasnorm_bypass_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, cur, src,
-                           W.norm_bias, W.norm_log_scale, W.bypass, src, src_a.h, src_a.l,
-                           (float*)nullptr, has_next ? cur_a.h : nullptr,
-                           has_next ? cur_a.l : nullptr,
-                           (long)D, temb, L, M, D,
-                           q2 ? c8.q : nullptr, q2 ? c8.qs : nullptr, q2 ? c8.ldq : 0L);
+      launch_biasnorm_bypass(cur, src, W.norm_bias, W.norm_log_scale, W.bypass, src, src_a.h, src_a.l,
+                             has_next ? cur_a.h : nullptr, has_next ? cur_a.l : nullptr, D, temb, L, M, D,
+                             q2 ? c8.q : nullptr, q2 ? c8.qs : nullptr, q2 ? c8.ldq : 0L, s);
     }
-    ZV_LAUNCH_CHECK();
   }
 
   // ---------------------------------------------------------------- one stack
   template <int SPLIT>
-  void stack(const ZipformerW& Z, const StackW& S, int si, Workspace& ws, float* src, Act src_a, int B,
-             int L, const uint8_t* pad, const float* temb, hipStream_t s) {
+  void stack(const Pass& pass, const ZipformerW& Z, const StackW& S, int si, Workspace& ws, float* src,
+             Act src_a, int B, int L, const uint8_t* pad, const float* temb, hipStream_t s) {
     const long M = (long)B * L;
     const bool split = SPLIT == 3;
     float* cur = ws.cur.get<float>(M * Z.dim);
     Act cur_a = ws.cur_a.get(M, Z.dim, split);
     // the fp32 working stream is not written here: the first layer's FF1 reads src + temb
-    hipLaunchKernelGGL(zv_stack_entry_kernel, grid1d(M * Z.dim), dim3(256), 0, s, src, temb,
-                       (float*)nullptr, src_a.h, src_a.l, cur_a.h, cur_a.l, (long)Z.dim, M,
-                       Z.dim, L);
-    ZV_LAUNCH_CHECK();
+    launch_stack_entry(src, temb, nullptr, src_a.h, src_a.l, cur_a.h, cur_a.l, Z.dim, M, Z.dim, L, s);
     // positional encoding of length L and every layer's linear_pos projection of it, in one
     // launch into the workspace (zipformer.py:983-1056, :1239): no host table, no cache, no
     // synchronisation, graph-capturable.  It depends on L and the stack's weights only: inside
@@ -1052,7 +1012,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     bool reuse = false;
     if (own) {
       Workspace::PosPKey& k = ws.posk[si];
-      reuse = posp_reuse && k.L == L && k.nl == nl && k.w == S.pos_w_all && k.buf == posP;
+      reuse = pass.posp_reuse && k.L == L && k.nl == nl && k.w == S.pos_w_all && k.buf == posP;
       k = Workspace::PosPKey{L, nl, S.pos_w_all, posP};
     }
     if (!reuse) {
@@ -1061,22 +1021,22 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       ZV_LAUNCH_CHECK();
     }
     for (size_t li = 0; li < S.layers.size(); ++li)
-      layer<SPLIT>(Z, S.layers[li], ws, src, src_a, cur, cur_a, B, L, pad,
+      layer<SPLIT>(pass, Z, S.layers[li], ws, src, src_a, cur, cur_a, B, L, pad,
                    posP + li * (size_t)R * HPD, temb, li + 1 < S.layers.size(), s, li > 0);
   }
 
   // ---------------------------------------------------------------- TTSZipformer
   // TTSZipformer.forward (zipformer.py:242-293).  xin: bf16 hi/lo (N*T, Fin); t/g (N).
   template <int SPLIT>
-  void zipformer(const ZipformerW& Z, Workspace& ws, Act xin, int sidx, int N, int T,
-                 const uint8_t* pad, const float* t, const float* g, float* out, hipStream_t s) {
+  void zipformer(const Pass& pass, const ZipformerW& Z, Workspace& ws, Act xin, int sidx, int N,
+                 int T, const uint8_t* pad, const float* t, const float* g, float* out, hipStream_t s) {
     const long M = (long)N * T;
     const int D = Z.dim;
     const bool split = SPLIT == 3;
     float* main = ws.main.get<float>(M * D);
     // mixed mode: the input / output projections as split products (xin and the last
     // BiasNorm's copy main_a carry the lo halves)
-    const bool ios = SPLIT == 1 && io_split;
+    const bool ios = SPLIT == 1 && pass.io_split;
     Act main_a = ws.main_a.get(M, D, split || ios);
     {
       Out o; o.C = main; o.ldc = D;
@@ -1109,32 +1069,19 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       const StackW& S = Z.stacks[si];
       const float* te = tstack ? tstack + si * (size_t)N * D : nullptr;
       if (S.ds == 1) {
-        stack<SPLIT>(Z, S, (int)si, ws, main, main_a, N, T, pad, te, s);
+        stack<SPLIT>(pass, Z, S, (int)si, ws, main, main_a, N, T, pad, te, s);
       } else {
         const int dL = (T + S.ds - 1) / S.ds;
         float* d = ws.dsrc.get<float>((size_t)N * dL * D);
         Act d_a = ws.dsrc_a.get((long)N * dL, D, split || ios);
-        hipLaunchKernelGGL(zv_downsample_kernel, grid1d((long)N * dL * D), dim3(256), 0, s, main, d,
-                           N, T, dL, D, S.ds, S.ds_w);
-        ZV_LAUNCH_CHECK();
+        launch_downsample(main, d, N, T, dL, D, S.ds, S.ds_w, s);
         uint8_t* pds = nullptr;
         if (pad) {
           pds = ws.maskds.get<uint8_t>((size_t)N * dL);
-          hipLaunchKernelGGL(zv_mask_downsample_kernel, grid1d(N * dL), dim3(256), 0, s, pad, pds,
-                             N, T, dL, S.ds);
-          ZV_LAUNCH_CHECK();
+          launch_mask_downsample(pad, pds, N, T, dL, S.ds, s);
         }
-        stack<SPLIT>(Z, S, (int)si, ws, d, d_a, N, dL, pds, te, s);
-        if (D % 4 == 0 && 256 % (D / 4) == 0) {   // row blocks of whole rows (f32x4 per thread)
-          const long rows_per_block = 4L * (256 / (D / 4));
-          hipLaunchKernelGGL(zv_upsample_combine_kernel,
-                             dim3((unsigned)((M + rows_per_block - 1) / rows_per_block)), dim3(256), 0,
-                             s, main, d, S.combiner, main, N, T, dL, D, S.ds);
-        } else {                                  // any other width (e.g. 384, 192)
-          hipLaunchKernelGGL(zv_upsample_combine_any_kernel, grid1d(M * D), dim3(256), 0, s, main, d,
-                             S.combiner, main, N, T, dL, D, S.ds);
-        }
-        ZV_LAUNCH_CHECK();
+        stack<SPLIT>(pass, Z, S, (int)si, ws, d, d_a, N, dL, pds, te, s);
+        launch_upsample_combine(main, d, S.combiner, main, N, T, dL, D, S.ds, s);
       }
     }
     // factors end with 1: the last stack's final BiasNorm wrote main_a
@@ -1162,31 +1109,41 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     return xin;
   }
 
-  void decoder_rows(Workspace& ws, Act xin, int sidx, int N, int T, const uint8_t* pad,
-                    const float* t, const float* g, float* out, hipStream_t s) {
-    if (cfg.precision == ZV_FP32) zipformer<3>(dec, ws, xin, sidx, N, T, pad, t, g, out, s);
-    else zipformer<1>(dec, ws, xin, sidx, N, T, pad, t, g, out, s);
+  void decoder_rows(const Pass& pass, Workspace& ws, Act xin, int sidx, int N, int T,
+                    const uint8_t* pad, const float* t, const float* g, float* out, hipStream_t s) {
+    if (cfg.precision == ZV_FP32) zipformer<3>(pass, dec, ws, xin, sidx, N, T, pad, t, g, out, s);
+    else zipformer<1>(pass, dec, ws, xin, sidx, N, T, pad, t, g, out, s);
   }
 
+  // whether a guided call doubles its rows (conditional + unconditional copies), and whether a
+  // decoder call of N rows of T frames runs its row blocks on their own streams
+  bool cfg_doubles(float g, const float* grows, bool cfg_rows) const {
+    return !distill() && (grows ? cfg_rows : g != 0.0f);
+  }
+  bool splits_rows(long N, int T) const { return split_streams >= 2 && N >= 2 && N * T >= split_min_rows; }
+
+  // posp_reuse: a later Euler step of one solve (Pass::posp_reuse)
   void decoder(Act xin, int Fin, int N, int T, const uint8_t* pad, const float* t, const float* g,
-               float* out, hipStream_t s) {
+               float* out, bool posp_reuse, hipStream_t s) {
     int sidx = 0;
     if (stereo()) sidx = (Fin == dec.in_proj[0].K) ? 0 : 1;
     ZV_REQUIRE(Fin == dec.in_proj[sidx].K, "decoder input width does not match in_proj");
-    io_split = cfg.precision == ZV_MIXED;
+    Pass pass;
+    pass.io_split = cfg.precision == ZV_MIXED;
+    pass.posp_reuse = posp_reuse;
     // (profiled passes run the same launches as the timed ones -- the same row blocks, kernels and
     // shapes -- but one row block after another on the caller's stream, so each launch's events time
     // it alone: with the blocks overlapping on three streams an event pair timed the co-running
     // kernels as well; rocprofv3's kernel trace serialises the dispatches the same way)
-    if (split_streams < 2 || N < 2 || (long)N * T < split_min_rows) {
-      decoder_rows(ws_dec, xin, sidx, N, T, pad, t, g, out, s);
+    if (!splits_rows(N, T)) {
+      decoder_rows(pass, ws_dec, xin, sidx, N, T, pad, t, g, out, s);
       return;
     }
     // Independent row blocks on their own streams (rows never interact on this path): the
     // kernels of one block (GEMMs: MFMA/LDS) co-run with another block's (attention: VALU;
     // epilogues: HBM) instead of the whole batch passing each kernel in lock step.
     // Bitwise equal to the single-stream decoder (tests/test_gpu_split_streams.py): every kernel
-    // choice that depends on a row count takes the batch's (dec_rows_N), not the row block's.
+    // choice that depends on a row count takes the batch's (Pass::batch_rows), not the row block's.
     const int parts = std::min(split_streams, std::min(N, MAX_SPLIT));
     if (!split_fork) {
       ZV_CHECK(ZV_BLOCKING(hipEventCreateWithFlags(&split_fork, hipEventDisableTiming)));
@@ -1197,7 +1154,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       if (!split_stream[i - 1]) split_stream[i - 1] = engine_stream(i - 1);
     const int outN = dec.out_proj[sidx].N;
     ZV_CHECK(hipEventRecord(split_fork, s));
-    dec_rows_N = N;   // every row block makes the batch's fused / unfused FeedForward choice
+    pass.batch_rows = N;   // every row block makes the batch's fused / unfused FeedForward choice
     int r0 = 0;
     for (int i = 0; i < parts; ++i) {
       const int n = N / parts + (i < N % parts ? 1 : 0);
@@ -1213,15 +1170,9 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       const float* ti = t + r0;
       const float* gi = g ? g + r0 : nullptr;
       float* oi = out + rows * outN;
-      try {
-        decoder_rows(*wsi, xi, sidx, n, T, padi, ti, gi, oi, si);
-      } catch (...) {
-        dec_rows_N = 0;
-        throw;
-      }
+      decoder_rows(pass, *wsi, xi, sidx, n, T, padi, ti, gi, oi, si);
       r0 += n;
     }
-    dec_rows_N = 0;
     for (int i = 1; i < parts && !g_zv_prof.on; ++i) {
       ZV_CHECK(hipEventRecord(split_join[i - 1], split_stream[i - 1]));
       ZV_CHECK(hipStreamWaitEvent(s, split_join[i - 1], 0));
@@ -1234,10 +1185,10 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   // ((guidance_scale == 0.0).all() selects the unguided branch, solver.py:71)
   void velocity(float t, float gscale, const float* grows, bool cfg_rows, const float* x,
                 const float* tc, const float* sc, const uint8_t* pad, int B, int T, float* vout,
-                bool euler, float dt, hipStream_t s) {
+                bool euler, float dt, bool posp_reuse, hipStream_t s) {
     const int Fx = stereo() ? 2 * cfg.feat_dim : cfg.feat_dim;
     const int Fin = 2 * Fx + cfg.feat_dim;
-    const bool cfg_on = !distill() && (grows ? cfg_rows : gscale != 0.0f);
+    const bool cfg_on = cfg_doubles(gscale, grows, cfg_rows);
     const int copies = cfg_on ? 2 : 1;
     const int N = copies * B;
     float g = gscale, gmul = 1.0f;
@@ -1271,7 +1222,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     }
     const long n = (long)B * T * Fx;
     float* v = (copies == 2 || euler) ? ws_dec.vout.get<float>((size_t)N * T * Fx) : vout;
-    decoder(xin, Fin, N, T, padN, tv, gv, v, s);
+    decoder(xin, Fin, N, T, padN, tv, gv, v, posp_reuse, s);
     const float* gr = cfg_on ? grows : nullptr;
     if (euler) {
       hipLaunchKernelGGL(zv_euler_update_kernel, grid1d(n), dim3(256), 0, s, const_cast<float*>(x),
@@ -1290,12 +1241,8 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     const int num_step = (int)ts.size() - 1;
     // steps after the first reuse the stacks' positional projections (same shapes and row
     // blocks every step; a graph replays the first step's launches)
-    struct Reset { bool& f; ~Reset() { f = false; } } reset{posp_reuse};
-    for (int k = 0; k < num_step; ++k) {
-      posp_reuse = k > 0;
-      velocity(ts[k], g, grows, cfg_rows, x, tc, sc, pad, B, T, nullptr, true, ts[k + 1] - ts[k],
-               s);
-    }
+    for (int k = 0; k < num_step; ++k)
+      velocity(ts[k], g, grows, cfg_rows, x, tc, sc, pad, B, T, nullptr, true, ts[k + 1] - ts[k], k > 0, s);
   }
 
   // zv_euler_sample body: graph replay when possible, plain launches otherwise
@@ -1304,11 +1251,8 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
                     float shift, hipStream_t s) {
     const std::vector<float> ts = time_steps(t0, t1, num_step, shift);
     bool graph = graph_mode != 0 && !g_zv_prof.on;
-    if (graph && graph_mode == 2) {   // the split test of decoder(), on the CFG-doubled rows
-      const bool cfg_on = !distill() && (grows ? cfg_rows : g != 0.0f);
-      const long N = (cfg_on ? 2L : 1L) * B;
-      graph = !(split_streams >= 2 && N >= 2 && N * T >= split_min_rows);
-    }
+    if (graph && graph_mode == 2)     // no graph where the decoder splits its (CFG-doubled) rows
+      graph = !splits_rows((cfg_doubles(g, grows, cfg_rows) ? 2L : 1L) * B, T);
     if (!graph) {
       euler_loop(x, tc, sc, pad, B, T, ts, g, grows, cfg_rows, s);
       return;
@@ -1393,13 +1337,13 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     const long n = (long)B * S;
     const int E = cfg.text_embed_dim;
     const bool split = cfg.precision == ZV_FP32 || cfg.precision == ZV_MIXED;   // mixed: the text encoder is split too
-    io_split = false;
     Act emb = ws_txt.emb.get(n, round_up(E, 64), split);
     hipLaunchKernelGGL(zv_embed_kernel, grid1d(n * E), dim3(256), 0, s, tok, embed_table, emb.h,
                        emb.l, emb.ld, n, E);
     ZV_LAUNCH_CHECK();
-    if (split) zipformer<3>(txt, ws_txt, emb, 0, B, S, pad, nullptr, nullptr, out, s);
-    else zipformer<1>(txt, ws_txt, emb, 0, B, S, pad, nullptr, nullptr, out, s);
+    const Pass pass;
+    if (split) zipformer<3>(pass, txt, ws_txt, emb, 0, B, S, pad, nullptr, nullptr, out, s);
+    else zipformer<1>(pass, txt, ws_txt, emb, 0, B, S, pad, nullptr, nullptr, out, s);
     if (spk && spk_table) {
       hipLaunchKernelGGL(zv_spk_add_kernel, grid1d(n * cfg.feat_dim), dim3(256), 0, s, out, spk,
                          spk_table, n, cfg.feat_dim);
@@ -1517,7 +1461,7 @@ int zv_reserve(zv_handle h, int max_batch, int max_frames) {
   (void)h->gpad.get<uint8_t>((size_t)max_batch * max_frames);
   (void)h->ggrows.get<float>((size_t)max_batch);
   h->velocity(0.25f, 1.0f, nullptr, false, x, tc, x, pad, max_batch, max_frames, v, false,
-              0.f, nullptr);
+              0.f, false, nullptr);
   ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
   ZV_API_END
 }
@@ -1590,7 +1534,7 @@ int zv_fm_decoder(zv_handle h, const float* t, const float* guidance, const floa
   hipStream_t s = (hipStream_t)stream;
   const int Fin = 2 * Fx + h->cfg.feat_dim;
   Act xin = h->build_xin(h->ws_dec, xt, text_c, speech_c, N, T, Fx, 1, 0, s);
-  h->decoder(xin, Fin, N, T, pad, t, h->distill() ? guidance : nullptr, v_out, s);
+  h->decoder(xin, Fin, N, T, pad, t, h->distill() ? guidance : nullptr, v_out, false, s);
   ZV_API_END
 }
 
@@ -1601,7 +1545,7 @@ int zv_velocity(zv_handle h, float t, float guidance_scale, const float* x, cons
   check_ready(h);
   ZV_REQUIRE(B > 0 && T > 0, "empty batch");
   h->velocity(t, guidance_scale, nullptr, false, x, text_c, speech_c, pad, B, T, v_out, false,
-              0.f, (hipStream_t)stream);
+              0.f, false, (hipStream_t)stream);
   ZV_API_END
 }
 
@@ -1624,7 +1568,7 @@ int zv_velocity_rows(zv_handle h, float t, const float* guidance_rows, const flo
   ZV_REQUIRE(guidance_rows != nullptr, "null guidance_rows");
   hipStream_t s = (hipStream_t)stream;
   const bool on = any_nonzero_rows(guidance_rows, B, s);
-  h->velocity(t, 0.f, guidance_rows, on, x, text_c, speech_c, pad, B, T, v_out, false, 0.f, s);
+  h->velocity(t, 0.f, guidance_rows, on, x, text_c, speech_c, pad, B, T, v_out, false, 0.f, false, s);
   ZV_API_END
 }
 

@@ -66,6 +66,7 @@
 #pragma once
 #include <cstddef>
 #include "zv_gemm256.inc"
+#include "zv_weights.inc"
 
 typedef unsigned v4u32_t __attribute__((ext_vector_type(4)));
 typedef unsigned v2u32_t __attribute__((ext_vector_type(2)));
@@ -1170,6 +1171,13 @@ static __global__ void zv_ffn_pack_w2_kernel(const bf16* W, long ldw, int H, bf1
   const int s = (int)(r & 1); r >>= 1;
   const int jb = (int)(r & 15), c = (int)(r >> 4);
   out[i] = W[(long)(32 * jb + (l & 31)) * ldw + 32 * c + 16 * s + 8 * (j >> 2) + 4 * (l >> 5) + (j & 3)];
+}
+// both packings of one FeedForward (L1: in_proj (H, 512), L2: out_proj (512, H)) into w1f / w2f, H * 512 each
+static void ffn_pack_weights(const Linear& L1, const Linear& L2, int H, bf16* w1f, bf16* w2f, hipStream_t s) {
+  const long n = (long)H * FFN_D;
+  hipLaunchKernelGGL(zv_ffn_pack_w1_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, L1.hi, (long)L1.Kpad, H, w1f);
+  hipLaunchKernelGGL(zv_ffn_pack_w2_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, L2.hi, (long)L2.Kpad, H, w2f);
+  ZV_LAUNCH_CHECK();
 }
 
 // the persistent schedule of a launch: chunk steps per block (w) and blocks, for R row blocks of

@@ -1025,6 +1025,31 @@ static void launch_attn_sa3(const FlashParams& p, hipStream_t s) {
   ZV_LAUNCH_CHECK();
 }
 
+// The consumers' forms (the numbers of zv_attn2_check's ABI) and the form a length runs on.
+// SelfAttention 1 / 2: sa2 with 2 / 3 query tiles per wave, 3 / 4 / 5: sa3 with 2 / 3 / 4: LDS-staged
+// K / V (sa3) while two blocks fit a CU, the register-fed form past that
+inline int sa_b2_form(int L) {
+  const int q3 = sa3_qpw(L);
+  return q3 ? q3 + 1 : sa2_qpw(L) == 3 ? 2 : 1;
+}
+static void launch_attn_sa_b2(const FlashParams& f, int form, hipStream_t s) {
+  switch (form) {
+    case 1: launch_attn_sa2<2>(f, s); break;
+    case 2: launch_attn_sa2<3, 1>(f, s); break;
+    case 3: launch_attn_sa3<2>(f, s); break;
+    case 4: launch_attn_sa3<3>(f, s); break;
+    default: launch_attn_sa3<4>(f, s); break;
+  }
+}
+// NonlinAttention 1 / 2: 4 / 8 query tiles per block; the kernel by the hidden width
+inline int na_b2_form(int L) { return na2_qtiles(L) == 4 ? 1 : 2; }
+static void launch_attn_na_b2(const FlashParams& f, int hid, int form, hipStream_t s) {
+  if (hid <= 128) { if (form == 1) launch_attn_na2<1, 4>(f, s); else launch_attn_na2<1>(f, s); }
+  else if (hid <= 256) { if (form == 1) launch_attn_na2<2, 4>(f, s); else launch_attn_na2<2>(f, s); }
+  else if (form == 1) launch_attn_na2<3, 4>(f, s);
+  else launch_attn_na2<3>(f, s);
+}
+
 // the v2 consumers' LDS images fit one workgroup at this length (else: the materialising path)
 static bool fused_attn2_fits(int L, int nv_na) {
   const size_t lim = 160 * 1024;

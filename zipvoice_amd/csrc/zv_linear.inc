@@ -353,6 +353,19 @@ struct LinearPolicy {
     }
     gemm_tile<128, 128, SPLIT, EPI_GLU, 2, 2, 3>(p, s, tag);
   }
+  // The in-projection with the depthwise conv (+ SwooshR) in its epilogue (zv_gemm256.inc
+  // g256_epi_glu_dw; p.dw_* set, dw_out == Ch): the counted GLU epilogue at D = 512 channels, a
+  // kernel size with an instantiation, the 256x256 kernel's 16-bit operand layout
+  bool glu_dw_fits(const GemmParams& p, int D, int ks) const {
+    return (res_counted & 8) && D == 512 && p.N == 2 * D && (ks == 7 || ks == 15 || ks == 31) && p.bias &&
+           !p.Cl && !p.As && p.lda % 8 == 0 && p.ldb % 8 == 0 && p.lda >= round_up(p.K, GEMM_BK) &&
+           p.ldb >= round_up(p.K, GEMM_BK) && p.Brows >= p.N && p.ld_dw % 8 == 0;
+  }
+  void launch_glu_dw(const GemmParams& p, int ks, hipStream_t s, const char* tag) {
+    if (ks == 31) launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 31>(p, s, tag, false);
+    else if (ks == 15) launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 15>(p, s, tag, false);
+    else launch_gemm256<EPI_GLU, 3, 0, 0, 1, 1, 7>(p, s, tag, false);
+  }
 };
 
 }  // namespace

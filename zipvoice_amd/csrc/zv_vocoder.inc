@@ -47,6 +47,12 @@ __global__ void zv_voc_im2col_kernel(const float* in, int layout, float div, flo
     split_store(oh, ol, row * ld + j, v);
   }
 }
+static void launch_voc_im2col(const float* in, int layout, float div, float sub, const int* lens, int B, int T,
+                              int C, int ks, const Act& out, hipStream_t s) {
+  hipLaunchKernelGGL(zv_voc_im2col_kernel, grid1d((long)B * T * C * ks), dim3(256), 0, s, in, layout, div, sub,
+                     lens, B, T, C, ks, out.h, out.l, out.ld);
+  ZV_LAUNCH_CHECK();
+}
 
 // ---- LayerNorm over C channels, one wave per row (C % 4 == 0, C <= 1024) ----
 // y = (x - mean) / sqrt(var + eps) * w + b  (biased variance, two-pass in registers)
@@ -306,9 +312,7 @@ struct zv_vocoder {
     const int C = cfg.dim, nm = cfg.n_mels, ke = cfg.embed_kernel;
     const char* tg = split ? "vocos_gemm_fp32" : "vocos_gemm_bf16";
     Act a0 = col.get(M, round_up((long)nm * ke, W_KPAD), split);
-    hipLaunchKernelGGL(zv_voc_im2col_kernel, grid1d(M * nm * ke), dim3(256), 0, s, in, layout, div,
-                       sub, lens, B, T, nm, ke, a0.h, a0.l, a0.ld);
-    ZV_LAUNCH_CHECK();
+    launch_voc_im2col(in, layout, div, sub, lens, B, T, nm, ke, a0, s);
     float* xs = x.get<float>((size_t)M * C);
     gemm<SPLIT, EPI_STD>(embed, a0, M, xs, C, Act{}, 0, nullptr, nullptr, s, tg);
     hipLaunchKernelGGL(zv_layernorm_kernel, dim3(cdiv(M, 4)), dim3(256), 0, s, xs, norm0_w, norm0_b,
