@@ -249,6 +249,14 @@ typedef struct {
   uint16_t* Ch; uint16_t* Cl; uint16_t* C2h; uint16_t* C2l; int64_t ldch;
   int launch[8];
   int num_cus;
+  /* the pre-projection form (forms 2 and 3; K = 0: off): cur1 = resid + (A . Wp^T + bp) [+ rowvec]
+   * replaces resid, x = round16(cur1) replaces the x argument (ignored); with form 2 the row vector
+   * belongs to the pre-projection, with form 3 it is added there and to C2h / C2l.  launch[3] has
+   * bit 4 (PRE) set. */
+  int K;
+  const float* A;          /* (M, K) */
+  const float* Wp;         /* (512, K) */
+  const float* bp;         /* (512) */
 } zv_ffn_check_args;
 int zv_ffn_check(zv_ffn_check_args* a);
 

@@ -535,12 +535,14 @@ int zv_linear_check(zv_linear_check_args* a) {
 int zv_ffn_check(zv_ffn_check_args* a) {
   ZV_API_BEGIN
   ZV_REQUIRE(a && a->M > 0 && a->H > 0 && a->H % (2 * FFN_HC) == 0 && a->form >= 0 && a->form <= 3 &&
-                 a->guard >= 0 && a->part_slots >= 0 && a->x && a->W1 && a->b1 && a->W2 && a->b2 &&
+                 a->guard >= 0 && a->part_slots >= 0 && (a->x || a->K > 0) && a->W1 && a->b1 && a->W2 && a->b2 &&
                  a->resid && a->C && a->ldc >= FFN_D && (!a->Ch || a->ldch >= FFN_D),
              "zv_ffn_check: bad arguments");
   const int M = a->M, H = a->H, form = a->form, G = a->guard, D = FFN_D;
   const bool norm = form == 3, byp = form == 2 || norm, rv = a->rowvec != nullptr;
-  ZV_REQUIRE((form == 1) == (rv && !norm) || norm, "zv_ffn_check: the row vector belongs to form 1 (or 3)");
+  const bool pre = a->K > 0;
+  ZV_REQUIRE(!pre || (byp && a->A && a->Wp && a->bp), "zv_ffn_check: the pre-projection belongs to forms 2 and 3");
+  ZV_REQUIRE((form == 1) == (rv && !norm) || norm || pre, "zv_ffn_check: the row vector belongs to form 1 (or 3)");
   ZV_REQUIRE((!rv || a->rows_per_group > 0) && (!byp || (a->orig && a->byp)) && (!norm || a->nb) &&
                  (form == 0 || a->Ch) && (norm || (!a->Cl && !a->C2h && !a->C2l)) &&
                  (!a->C2l || a->C2h),
@@ -559,7 +561,19 @@ int zv_ffn_check(zv_ffn_check_args* a) {
   q.H = H; q.nseg = 1;
   FfnSeg& g = q.seg[0];
   g.M = M;
-  {
+  if (pre) {
+    // the pre-projection form: Wp (512, K) packed as the engine packs conv_sa_out, W1 in the tile's
+    // register order; A in rows of lda = 32 ceil(K / 32) + 8 elements, zero past K
+    const int K = a->K;
+    const Linear Lp = store.make_linear(a->Wp, D, K, a->bp);
+    const int nkp = ffn_pre_chunks(K);
+    bf16* wpf = dev.make<bf16>((size_t)nkp * FFN_HC * D);
+    ffn_pack_pre_weights(L1, H, w1f, Lp, wpf, s);
+    q.Wpf = wpf; q.bp = Lp.b; q.nkp = nkp; q.lda = (long)nkp * FFN_HC + 8;
+    std::vector<bf16> h, l;
+    chk_act(a->A, M, K, q.lda, false, h, l);
+    g.A = dev.up(h.data(), h.size());
+  } else {
     std::vector<bf16> h, l;
     chk_act(a->x, M, D, D, false, h, l);
     g.X = dev.up(h.data(), h.size());

@@ -46,6 +46,11 @@ struct LayerW {
   // layers of width 512 with hidden widths a multiple of 64, 16-bit modes)
   bf16* ffn_w1f[3] = {nullptr, nullptr, nullptr};
   bf16* ffn_w2f[3] = {nullptr, nullptr, nullptr};
+  // the pre-projection form (ZV_FFN=3): FF2 / FF3's in_proj with its K in the accumulator's register
+  // order (a second packed copy, H * 512 each: the natural-order copy stays for the sites and row
+  // counts that keep the conv_sa_out linear), and conv_sa_out[c] in the W2 chunk format
+  bf16* ffn_w1fp[3] = {nullptr, nullptr, nullptr};
+  bf16* ffn_wpf[2] = {nullptr, nullptr};
   Linear na_in, na_out;
   Linear conv_in[2], conv_out[2];
   // bf16 mode: [conv_out[c] | sa_out[c]] concatenated along K (bias summed): one GEMM finishes
@@ -233,8 +238,10 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   // SwooshL -> out_proj -> residual without the hidden tensor in HBM) for launches of at
   // least ffn_min_rows rows; 2 (default): FF3 also carries the layer's BiasNorm + bypass in its
   // epilogue.  C2 bench 445 -> 431 ms per step with the pipelined depthwise conv
-  // (profiles/r03_ffn_ab.txt)
-  int ffn_fused = 2;
+  // (profiles/r03_ffn_ab.txt).  3 (default): FF2 and FF3 also run the conv + SelfAttention
+  // out-projection (conv_sa_out) as their first phase where the K-concatenated linear would run in
+  // front of them (layer<1>): no gemm_bf16_resid_rv launch, no fp32 stream round trip between the two
+  int ffn_fused = 3;
   // ZV_FFN_MIN_ROWS: launches under this many rows run the unfused pair, which fills the chip
   // better there (a fused block owns a CU and takes 128 rows: 10k rows = 78 blocks for 256
   // CUs).  C2 435 -> 426-432 ms (profiles/r03_ffn_policy_ab.txt); C3 (16 utterances, no
@@ -279,7 +286,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     graph_mode = envi("ZV_GRAPH", 2);
     sa_tp = envi("ZV_SA_TP", 1);
     fp8_fuse = envi("ZV_FP8_FUSE", 7);
-    ffn_fused = envi("ZV_FFN", 2);
+    ffn_fused = envi("ZV_FFN", 3);
     ffn_min_rows = envi("ZV_FFN_MIN_ROWS", 15000);
     ffn_persist = envi("ZV_FFN_PERSIST", 1);
     split_streams = envi("ZV_SPLIT_STREAMS", 3);
@@ -605,6 +612,13 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
             W.conv_sa_out[c] = make_linear_kcat(cp + "out_proj", dim,
                                                 lp + "self_attn" + std::to_string(c + 1) + ".out_proj",
                                                 heads * Z.vd, dim, cfg.precision == ZV_MIXED && mixed_sa);
+          if (ffn_fused >= 3 && W.conv_sa_out[c].hi && W.ffn_w1f[c + 1]) {
+            const int f = c + 1;                      // conv(c) is followed by FF(c + 2)
+            W.ffn_w1fp[f] = store.dalloc<bf16>((long)hs[f] * FFN_D);
+            W.ffn_wpf[c] = store.dalloc<bf16>((long)ffn_pre_chunks(W.conv_sa_out[c].K) * FFN_HC * FFN_D);
+            ffn_pack_pre_weights(W.ff_in[f], hs[f], W.ffn_w1fp[f], W.conv_sa_out[c], W.ffn_wpf[c], nullptr);
+            ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+          }
           W.dw_w[c] = store.upload_key(cp + "depthwise_conv.weight", (size_t)dim * W.ks);
           W.dw_b[c] = store.upload_key(cp + "depthwise_conv.bias", dim);
         }
@@ -817,7 +831,8 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       q.W1f = W.ffn_w1f[f]; q.b1 = W.ff_in[f].b; q.W2f = W.ffn_w2f[f]; q.b2 = W.ff_out[f].b;
       return q;
     };
-    auto ff = [&](int f, const Out& oe) {
+    std::function<void(FfnParams&, int)> ffn_pre_operands;   // (set below, where [dw | o] is known)
+    auto ff = [&](int f, const Out& oe, int pre_c = -1) {
       if constexpr (SPLIT == 1) {
         if (ffn_fused && W.ffn_w1f[f] && !(f8 && W.ff_in[f].q8) && oe.C && oe.resid &&
             !oe.act.l && !oe.residh && Mtot >= ffn_min_rows && cur_a.ld % 8 == 0) {
@@ -826,10 +841,12 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
           g.resid = oe.resid; g.C = oe.C; q.ldc = oe.ldc; g.Ch = oe.act.h; q.ldch = oe.act.ld;
           g.rowvec = oe.rowvec; q.rowvec_ld = oe.rowvec_ld; q.rows_per_group = oe.rows_per_group;
           g.orig = oe.orig; q.byp = oe.byp;
+          if (pre_c >= 0) ffn_pre_operands(q, pre_c);
           ffn_site(q, ws, s, "ffn_bf16");
           return;
         }
       }
+      ZV_REQUIRE(pre_c < 0, "the pre-projection site fell off the fused FeedForward");
       // fp8: the SwooshL output only as the fp8 out-projection's operand (decided per in/out
       // pair: a 16-bit out-projection reads the bf16 hidden copy)
       const bool f8f = f8 && W.ff_in[f].q8 && W.ff_out[f].q8;
@@ -887,6 +904,24 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     // fp16 parity mode's split SelfAttention products (mixed_sa; the weights were built for it)
     const bool sa_split = kcat && pass.io_split && W.conv_sa_out[0].K == D + 3 * H * Z.vd;
     ZV_REQUIRE(!kcat || sa_split || W.conv_sa_out[0].K == D + H * Z.vd, "conv + SelfAttention out-projection width");
+    // ZV_FFN=3: conv(c)'s K-concatenated out-projection runs as the first phase of the fused
+    // FeedForward behind it (FF2 with bypass_mid, FF3 with BiasNorm + bypass), under exactly the
+    // conditions that put that FeedForward on the fused kernel; decided on the batch's rows
+    const bool ffn_norm = SPLIT == 1 && ffn_fused >= 2 && W.ffn_w1f[2] && !f8 && D == FFN_D &&
+                          Mtot >= ffn_min_rows && cur_a.ld == src_a.ld && cur_a.ld % 8 == 0;
+    auto pre_fits = [&](int c) {
+      return kcat && ffn_fused >= 3 && D == FFN_D && W.ffn_w1fp[c + 1] && W.ffn_wpf[c] && !cur_a.l &&
+             Mtot >= ffn_min_rows && cur_a.ld % 8 == 0 && dwo.ld % 8 == 0 &&
+             dwo.ld >= (long)ffn_pre_chunks(W.conv_sa_out[c].K) * FFN_HC;
+    };
+    const bool pre_site[2] = {pre_fits(0), pre_fits(1) && ffn_norm};
+    ffn_pre_operands = [&](FfnParams& q, int c) {
+      FfnSeg& g = q.seg[0];
+      g.X = nullptr; g.A = dwo.h; q.lda = dwo.ld;
+      q.W1f = W.ffn_w1fp[c + 1]; q.Wpf = W.ffn_wpf[c]; q.bp = W.conv_sa_out[c].b;
+      q.nkp = ffn_pre_chunks(W.conv_sa_out[c].K);
+      g.rowvec = temb; q.rowvec_ld = D; q.rows_per_group = L;
+    };
     auto self_attn = [&](int a) {                     // SelfAttention (:564-570, :600-606)
       const int vd = Z.vd, HV = H * vd;
       // V^T rows per head: vd, or 16 where the value projection was built padded (sa_vpad: rows
@@ -944,7 +979,9 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
                       dq ? dw.q : nullptr, dw.qs, dw.ldq);
         if (f8 && !dq) pack8(dw, M, D, s);
       }
-      if (kcat) {                                     // cur += [dw | o] . [conv_out | sa_out]^T + temb
+      if (kcat && pre_site[c]) {
+        // (the FeedForward behind this module runs the out-projection)
+      } else if (kcat) {                              // cur += [dw | o] . [conv_out | sa_out]^T + temb
         Out e = res;
         e.rowvec = temb; e.rowvec_ld = D; e.rows_per_group = L;
         linear<SPLIT>(W.conv_sa_out[c], dw, M, e, s);
@@ -957,14 +994,12 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     {                                                 // FF2 + bypass_mid (:593-598)
       Out e = res; e.byp = W.bypass_mid;
       e.orig = src;
-      ff(1, e);
+      ff(1, e, pre_site[0] ? 0 : -1);
     }
     self_attn(1);                                     // SA2 (+ temb)
     conv(1);                                          // conv2
     // FF3 + BiasNorm + bypass in the fused FeedForward kernel's norm epilogue (the FF3 output
     // never reaches HBM; zv_ffn.inc)
-    const bool ffn_norm = SPLIT == 1 && ffn_fused >= 2 && W.ffn_w1f[2] && !f8 && D == FFN_D &&
-                          Mtot >= ffn_min_rows && cur_a.ld == src_a.ld && cur_a.ld % 8 == 0;
     if (ffn_norm) {
       FfnParams q = ffn_params(2);
       FfnSeg& g = q.seg[0];
@@ -973,6 +1008,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       q.byp = W.bypass; q.nb = W.norm_bias; q.log_scale = W.norm_log_scale;
       g.rowvec = temb; q.rowvec_ld = D; q.rows_per_group = L;
       g.C2h = has_next ? cur_a.h : nullptr; g.C2l = has_next ? cur_a.l : nullptr;
+      if (pre_site[1]) ffn_pre_operands(q, 1);
       ffn_site(q, ws, s, "ffn_norm_bf16");
     } else {                                          // FF3: only the fp32 stream feeds BiasNorm
       Out e = res;                                    // (which rewrites both copies): no bf16 copy

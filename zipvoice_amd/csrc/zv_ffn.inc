@@ -75,7 +75,8 @@ constexpr long FFN_PART_FLOATS = (long)FFN_BM * FFN_D;   // one P item's tiles (
 
 struct FfnSeg {                    // one row range and its own operand pointers
   int M, rb0;                      // rows; first row block of the range in the launch's order
-  const bf16* X;                   // (M, 512) 16-bit copy of the stream (the module input)
+  const bf16* X;                   // (M, 512) 16-bit copy of the stream (the module input; PRE: unused)
+  const bf16* A;                   // PRE: (M, Kp) 16-bit pre-projection operand, row stride lda
   const float* resid; float* C;    // fp32 stream (resid may alias C)
   bf16* Ch;                        // the stream's 16-bit copy (or null)
   const float* rowvec;             // row vector (row r adds rowvec[r / rows_per_group])
@@ -91,6 +92,12 @@ struct FfnParams {
   const bf16* W1f; const float* b1;  // in_proj, fragment-major [H/32][32 k-steps][64][8]
   const bf16* W2f; const float* b2;  // out_proj, fragment-major [H/32][16][2][64][8], K permuted
   const float* byp;
+  // PRE (the pre-projection form): cur1 = resid + (A . Wp^T + bp) [+ rowvec] is formed in the out^T
+  // tiles before the module runs, x = round16(cur1) in registers; Wpf fragment-major
+  // [nkp][16][2][64][8] with K in natural order (zv_ffn_pack_wp_kernel), zero past K.  Columns
+  // [K, 32 nkp) of A are read: the caller keeps them zero (finite at least: Wpf is zero there).
+  // W1f's K is then in the accumulator's register order (zv_ffn_pack_w1p_kernel)
+  const bf16* Wpf; const float* bp; long lda; int nkp;
   // NORM epilogue (FF3 + the layer's BiasNorm + bypass, zipformer.py:610-618, scaling.py:330-355):
   // x = resid + FF(x) is never stored; out = orig + (x * rsqrt(mean((x - nb)^2)) e^log_scale - orig)
   // * byp -> C (fp32, in place over orig) and Ch / Cl (16-bit hi / lo copy); out + rowvec ->
@@ -277,7 +284,13 @@ constexpr unsigned long long FFN_SPIN_TICKS = 200000000;
 // NORM (FF3 + BiasNorm epilogue): 0 off, 1 on (its optional outputs checked at run time)
 // TP: the transposed plain epilogue (FFN_EPI_T) is allowed; the launcher clears it for a row vector
 // whose groups are shorter than a wave (its per-row lookup would stall the prefetch stream)
-template <bool RV, bool ORIG, bool COPY, int ABL = 0, int NORM = 0, bool TP = true>
+// PRE: the pre-projection form (FfnParams: Wpf).  An item that starts a row block (whole, or a P
+// item) first streams the Wp chunks through the W2 slots onto initial accumulators resid + bp
+// [+ rowvec], then takes x = round16 of the tiles as its in-projection operand in place (the tile's
+// registers 8 pp .. 8 pp + 7 of output tile jt are k-step 2 jt + pp: W1f's K order); the epilogue
+// reads no residual.  A P item also stores x to Ch (write-through, before its flag), where its C
+// item loads it in the same register order: cut and uncut row blocks stay bitwise equal
+template <bool RV, bool ORIG, bool COPY, int ABL = 0, int NORM = 0, bool TP = true, bool PRE = false>
 __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -400,14 +413,17 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
                         v[2][0], v[2][1], v[2][2], v[2][3], v[3][0], v[3][1], v[3][2], v[3][3]};
         __builtin_amdgcn_sched_barrier(0);
       });
-    } else {
+    } else if constexpr (!PRE) {
 #pragma unroll
       for (int j = 0; j < 16; ++j) out[j] = f32x16{};
     }
     // the output tiles live in the AGPRs (left to itself the allocator gave some of them VGPRs
     // once they were written / read outside the MFMAs, and spilled)
+    // (PRE: the pre-projection below writes a starting row block's tiles)
+    if constexpr (!PRE || split_in) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) asm volatile("" : "+a"(out[j]));
+      for (int j = 0; j < 16; ++j) asm volatile("" : "+a"(out[j]));
+    }
 #if FFN_TIMING
     const unsigned long long tx0 = __builtin_amdgcn_s_memtime();
     ++tm_items;
@@ -429,17 +445,27 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
       }
     }
     bf16x8 xf[32];
-    {
+    if constexpr (!PRE) {
       const int tr = min(t0 + tl, S.M - 1);
       const bf16* xr = S.X + (long)tr * p.ldx + 8 * hh;
 #pragma unroll
       for (int s = 0; s < 32; ++s) xf[s] = *reinterpret_cast<const bf16x8*>(xr + 16 * s);
+    } else if constexpr (split_in) {
+      // PRE, C item: x as its P item stored it (Ch), in the accumulator's register order: element e of
+      // k-step s is channel 16 s + 8 (e >> 2) + 4 hh + (e & 3), two 8-B pieces
+      const int tr = min(t0 + tl, S.M - 1);
+      const bf16* xr = S.Ch + (long)tr * p.ldch + 4 * hh;
+#pragma unroll
+      for (int s = 0; s < 32; ++s) {
+        const bf16x4 lo = *reinterpret_cast<const bf16x4*>(xr + 16 * s), hi = *reinterpret_cast<const bf16x4*>(xr + 16 * s + 8);
+        xf[s] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      }
     }
     // the x loads are the last 32 vector-memory operations: everything older (the weight DMA, the
     // previous item's stores, the row vectors) has landed at vmcnt(32); each x fragment's own wait
     // is hipcc's (counted, before its first in-projection MFMA), so the prologue chain starts as the
     // first fragments arrive
-    wait_vmcnt<FFN_XOVL ? 32 : 0>();
+    wait_vmcnt<(FFN_XOVL && !PRE) ? 32 : 0>();
     if constexpr (NLDS && !split_out) {
       if (nrv) {
 #pragma unroll
@@ -451,6 +477,148 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
 #if FFN_TIMING
     tm_x += __builtin_amdgcn_s_memtime() - tx0;
 #endif
+
+    if constexpr (PRE && !split_in) {
+      // ---- the pre-projection: out^T = resid + bp [+ rowvec] + Wp . A^T, then x = round16(out^T).
+      // Every slot's readers are behind the barrier above: Wp chunk kc streams through W2 slot
+      // 2 + (kc & 1), one vmcnt(0) + barrier per chunk; the wave's rows of A, resid and Ch through
+      // buffer resources (rows past M read 0, their stores are dropped)
+      int lvp = lane;
+      asm volatile("" : "+v"(lvp));          // (lane-invariant offsets not hoisted out of the item loop)
+      const int ptl = lvp & 31, phh = lvp >> 5;
+      const int wr = max(0, min(32, S.M - t0));
+      const __amdgpu_buffer_rsrc_t rs_a =
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16*>(S.A + (long)t0 * p.lda), 0, wr * (int)p.lda * 2, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs_pr =
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(S.resid + (long)t0 * p.ldc), 0, wr * (int)p.ldc * 4, 0x00020000);
+      const int a_off = (ptl * (int)p.lda + 8 * phh) * 2, r_off = (ptl * (int)p.ldc + 4 * phh) * 4;
+      auto load_a = [&](int kc, int s) {
+        return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_a, a_off + kc * 64 + s * 32, 0, 0));
+      };
+      dma(p.Wpf, 0, 2, 0); dma(p.Wpf, 0, 2, 1);
+      bf16x8 ac[2], an[2];
+      ac[0] = load_a(0, 0); ac[1] = load_a(0, 1);
+      // the initial accumulators: register 4 q + e of tile j is output 32 j + 8 q + 4 hh + e of token tl
+      const bool hrv = S.rowvec != nullptr;
+      const int rpg = hrv ? p.rows_per_group : 1;
+      auto tile_of = [&](const f32x4 (&v)[4]) {
+        return f32x16{v[0][0], v[0][1], v[0][2], v[0][3], v[1][0], v[1][1], v[1][2], v[1][3],
+                      v[2][0], v[2][1], v[2][2], v[2][3], v[3][0], v[3][1], v[3][2], v[3][3]};
+      };
+      if (!hrv || rpg >= 32) {
+        // bp + the wave's two row groups' row vectors staged in the wave's 4 KiB of W2 slot 3 (free
+        // until chunk 1's DMA, issued behind the first chunk barrier); the residual pieces PDT tiles ahead
+        float* cvs = reinterpret_cast<float*>(smem + 3 * FFN_SLOT) + wave * 2 * FFN_D;
+        const int g0 = hrv ? min(t0, S.M - 1) / rpg : 0;
+        const int g1 = hrv ? min(g0 + 1, (S.M - 1) / rpg) : 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int f = (q * 64 + lvp) * 4, ch = f & (FFN_D - 1);
+          f32x4 v = *reinterpret_cast<const f32x4*>(p.bp + ch);
+          if (hrv) v += *reinterpret_cast<const f32x4*>(S.rowvec + (long)(f < FFN_D ? g0 : g1) * p.rowvec_ld + ch);
+          *reinterpret_cast<f32x4*>(cvs + f) = v;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+        const float* cvp = cvs + ((hrv && t0 + ptl >= (g0 + 1) * rpg) ? FFN_D : 0) + 4 * phh;
+        constexpr int PDT = 6;
+        f32x4 ri[16][4];
+        auto pf = [&](int j) {
+          if (j < 16) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              ri[j][q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_pr, r_off + (32 * j + 8 * q) * 4, 0, 0));
+          }
+        };
+#pragma unroll
+        for (int j = 0; j < PDT; ++j) pf(j);
+        static_for<16>([&](auto J_) {
+          constexpr int j = decltype(J_)::value;
+          pf(j + PDT);
+          f32x4 v[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) v[q] = ri[j][q] + *reinterpret_cast<const f32x4*>(cvp + 32 * j + 8 * q);
+          out[j] = tile_of(v);
+          asm volatile("" : "+a"(out[j]));
+          __builtin_amdgcn_sched_barrier(0);
+        });
+      } else {
+        // row groups shorter than a wave: each lane its own row's vector
+        const int grp = min(t0 + ptl, S.M - 1) / rpg;
+        const float* vrow = S.rowvec + (long)grp * p.rowvec_ld + 4 * phh;
+        const float* bpl = p.bp + 4 * phh;
+        static_for<16>([&](auto J_) {
+          constexpr int j = decltype(J_)::value;
+          f32x4 v[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f32x4 r4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_pr, r_off + (32 * j + 8 * q) * 4, 0, 0));
+            v[q] = r4 + (*reinterpret_cast<const f32x4*>(bpl + 32 * j + 8 * q) + *reinterpret_cast<const f32x4*>(vrow + 32 * j + 8 * q));
+          }
+          out[j] = tile_of(v);
+          asm volatile("" : "+a"(out[j]));
+          if constexpr ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+        });
+      }
+      auto pstep = [&](auto PAR_, int kc) {
+        constexpr int PAR = decltype(PAR_)::value;       // kc & 1: the chunk's slot
+        wait_vmcnt<0>();                     // this wave's DMA pieces and A fragments of chunk kc
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();        // ... everyone's, and everyone is done with the other slot
+        asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");
+        if (kc + 1 < p.nkp) { dma(p.Wpf, kc + 1, 3 - PAR, 0); dma(p.Wpf, kc + 1, 3 - PAR, 1); }
+        const int kn = min(kc + 1, p.nkp - 1);
+        an[0] = load_a(kn, 0); an[1] = load_a(kn, 1);
+        bf16x8 fb[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) fb[q] = w2f(PAR, q);
+        static_for<32>([&](auto I_) {
+          constexpr int i = decltype(I_)::value;
+          ffn_mma_a(out[i >> 1], fb[i & 3], ac[i & 1]);
+          if constexpr (i + 4 < 32) fb[i & 3] = w2f(PAR, i + 4);
+        });
+        // (WAR: the asm MFMAs read their operands during their passes, see the chunk step below)
+        asm volatile("" ::"v"(ac[0]), "v"(ac[1]), "v"(fb[0]), "v"(fb[1]), "v"(fb[2]), "v"(fb[3]));
+        ac[0] = an[0]; ac[1] = an[1];
+      };
+      int kc = 0;
+      for (; kc + 1 < p.nkp; kc += 2) {
+        pstep(std::integral_constant<int, 0>{}, kc);
+        pstep(std::integral_constant<int, 1>{}, kc + 1);
+      }
+      if (kc < p.nkp) pstep(std::integral_constant<int, 0>{}, kc);
+      // MFMA result -> accvgpr read: 18 wait states; then x in place
+      asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");
+#pragma unroll
+      for (int j = 0; j < 16; ++j) asm volatile("" : "+a"(out[j]));
+      static_for<32>([&](auto S_) {
+        constexpr int s = decltype(S_)::value, jt = s >> 1, pp = s & 1;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) xf[s][e] = (bf16)out[jt][8 * pp + e];
+      });
+#pragma unroll
+      for (int j = 0; j < 16; ++j) asm volatile("" : "+a"(out[j]));
+      if constexpr (split_out) {
+        // P item: x to the stream's 16-bit copy for its C item, write-through like the tiles (the flag
+        // is raised behind this wave's vmcnt(0))
+        const __amdgpu_buffer_rsrc_t rs_xh =
+            __builtin_amdgcn_make_buffer_rsrc(S.Ch + (long)t0 * p.ldch, 0, wr * (int)p.ldch * 2, 0x00020000);
+        const int h_off = (ptl * (int)p.ldch + 4 * phh) * 2;
+        static_for<32>([&](auto S_) {
+          constexpr int s = decltype(S_)::value;
+          const v4u32_t w = __builtin_bit_cast(v4u32_t, xf[s]);
+          __builtin_amdgcn_raw_buffer_store_b64(v2u32_t{w[0], w[1]}, rs_xh, h_off + 32 * s, 0, 16);
+          __builtin_amdgcn_raw_buffer_store_b64(v2u32_t{w[2], w[3]}, rs_xh, h_off + 32 * s + 16, 0, 16);
+        });
+      }
+      // x is VALU-written: its converts are done, and a wait-state run passes, before the prologue's
+      // asm MFMAs read it
+#pragma unroll
+      for (int s = 0; s < 32; ++s) asm volatile("" : "+v"(xf[s]));
+      asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");
+      // every wave is done with the Wp slots before the chunk loop's first W2 DMA: that DMA follows
+      // the prologue's barrier
+    }
 
     // bias quad q of chunk c: hidden rows 32 c + 8 q + 4 hh + 0..3 (accumulator registers 4q..4q+3)
     auto bias4 = [&](int c, int q) { return *reinterpret_cast<const f32x4*>(b1s + c * FFN_HC + 8 * q + 4 * hh); };
@@ -551,8 +719,10 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
     auto prefetch = [&](int g) {
       if (g < 32) {
         const int n = 16 * g + 8 * hh;     // g = 2 j + pp: outputs 32 j + 16 pp + 8 hh .. + 7
-        rr[g][0] = *reinterpret_cast<const f32x4*>(rrow + n);
-        rr[g][1] = *reinterpret_cast<const f32x4*>(rrow + n + 4);
+        if constexpr (!PRE) {   // (PRE: the residual is in the tiles already)
+          rr[g][0] = *reinterpret_cast<const f32x4*>(rrow + n);
+          rr[g][1] = *reinterpret_cast<const f32x4*>(rrow + n + 4);
+        }
         if constexpr (OPRE) {
           ro[g][0] = *reinterpret_cast<const f32x4*>(orow + n);
           ro[g][1] = *reinterpret_cast<const f32x4*>(orow + n + 4);
@@ -612,7 +782,7 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
     };
     auto tprefetch = [&](int k) {
       if constexpr (EPN) {
-        if (k < 128) {
+        if (k < 128 && !(PRE && k < 64)) {
           // (the row pair and the pass in the scalar offset: per-piece VGPR offsets, kept for
           // pass 2's stores, spilled)
           int so = (k & 15) * tstep;
@@ -624,7 +794,7 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
       if constexpr (EPT) {
         if (k < 64) {
           const int off = toff + (k & 15) * tstep + (k >> 4) * 512;
-          tq[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_r, off, 0, 0));
+          if constexpr (!PRE) tq[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_r, off, 0, 0));
           if constexpr (ORIG) to[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_o, off, 0, 0));
         }
       }
@@ -646,7 +816,7 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
         if constexpr ((EPT || EPN) && !split_out) {
           load_consts();
 #pragma unroll
-          for (int k = 0; k < PT; ++k) tprefetch(k);
+          for (int k = 0; k < PT; ++k) tprefetch((PRE && EPN) ? 64 + k : k);   // (PRE: the original only)
         } else {
 #pragma unroll
           for (int g = 0; g < PD; ++g) prefetch(g);
@@ -797,15 +967,19 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
         const f32x4 nbv = *reinterpret_cast<const f32x4*>(ncs + FFN_D + col);
         static_for<16>([&](auto I_) {
           constexpr int i = decltype(I_)::value, k = 16 * ps + i;
-          tprefetch(k + PT);
+          if constexpr (!PRE) tprefetch(k + PT);
           const int row = 2 * i + plr;
           const f32x4 a = *reinterpret_cast<const f32x4*>(tb + row * 128 + ((plc ^ (row & 7)) * 4));
           // x = resid + (acc + b2) into the freed accumulators: tile 4 ps + i / 4, registers 4 (i % 4) ..
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            const float x = tq[k][e] + (a[e] + bb[e]);
+            const float x = PRE ? a[e] + bb[e] : tq[k][e] + (a[e] + bb[e]);
             const float d = x - nbv[e];
-            ssr[i] += d * d;
+            // (PRE: explicit fused multiply-adds.  Left to contraction, an item kind's instantiation
+            // may sum d * d as packed multiplies and adds where another fuses them, and a cut row
+            // block's C item then differs from the whole row block in the last bit of a row's scale)
+            if constexpr (PRE) ssr[i] = __builtin_fmaf(d, d, ssr[i]);
+            else ssr[i] += d * d;
             out[4 * ps + (i >> 2)][4 * (i & 3) + e] = x;
           }
           if constexpr ((i & 3) == 3) asm volatile("" : "+a"(out[4 * ps + (i >> 2)]));
@@ -855,7 +1029,8 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float o = tq[64 + k][e];
-            y[e] = o + (out[4 * ps + (i >> 2)][4 * (i & 3) + e] * ssr[i] - o) * byv[e];
+            if constexpr (PRE) y[e] = __builtin_fmaf(__builtin_fmaf(out[4 * ps + (i >> 2)][4 * (i & 3) + e], ssr[i], -o), byv[e], o);
+            else y[e] = o + (out[4 * ps + (i >> 2)][4 * (i & 3) + e] * ssr[i] - o) * byv[e];
           }
           int fo = i * tstep, ho = i * hstep;   // (scalar offsets, per piece as above)
           asm volatile("" : "+s"(fo), "+s"(ho));
@@ -924,10 +1099,11 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
         const f32x4 n1 = *reinterpret_cast<const f32x4*>(nbc + n + 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          v[e] = rr[g][0][e] + (v[e] + b0[e]);
-          v[4 + e] = rr[g][1][e] + (v[4 + e] + b1[e]);
+          v[e] = PRE ? v[e] + b0[e] : rr[g][0][e] + (v[e] + b0[e]);
+          v[4 + e] = PRE ? v[4 + e] + b1[e] : rr[g][1][e] + (v[4 + e] + b1[e]);
           const float d0 = v[e] - n0[e], d1 = v[4 + e] - n1[e];
-          ss += d0 * d0 + d1 * d1;
+          if constexpr (PRE) ss = __builtin_fmaf(d1, d1, __builtin_fmaf(d0, d0, ss));
+          else ss += d0 * d0 + d1 * d1;
           out[j][8 * pp + e] = v[e];
           out[j][8 * pp + 4 + e] = v[4 + e];
         }
@@ -963,8 +1139,13 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
         float y[8];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          y[e] = rq[g][0][e] + (out[j][8 * pp + e] * scale - rq[g][0][e]) * c0v[e];
-          y[4 + e] = rq[g][1][e] + (out[j][8 * pp + 4 + e] * scale - rq[g][1][e]) * c1v[e];
+          if constexpr (PRE) {
+            y[e] = __builtin_fmaf(__builtin_fmaf(out[j][8 * pp + e], scale, -rq[g][0][e]), c0v[e], rq[g][0][e]);
+            y[4 + e] = __builtin_fmaf(__builtin_fmaf(out[j][8 * pp + 4 + e], scale, -rq[g][1][e]), c1v[e], rq[g][1][e]);
+          } else {
+            y[e] = rq[g][0][e] + (out[j][8 * pp + e] * scale - rq[g][0][e]) * c0v[e];
+            y[4 + e] = rq[g][1][e] + (out[j][8 * pp + 4 + e] * scale - rq[g][1][e]) * c1v[e];
+          }
         }
         const long o = (long)m * p.ldc + n, oh = (long)m * p.ldch + n;
         GLOBAL f32x4* ca = adr32(Cp, o);
@@ -1038,7 +1219,7 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
           const f32x4 a = *reinterpret_cast<const f32x4*>(tb + row * 128 + ((lc ^ (row & 7)) * 4));
           f32x4 v;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = tq[k][e] + (a[e] + bb[e]);
+          for (int e = 0; e < 4; ++e) v[e] = PRE ? a[e] + bb[e] : tq[k][e] + (a[e] + bb[e]);
           const int mrow = t0 + row;
           if constexpr (RV) {
             // (groups of >= 32 rows, the launcher's condition for TP: two per wave at most)
@@ -1051,7 +1232,8 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
           }
           if constexpr (ORIG) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = to[k][e] + (v[e] - to[k][e]) * sc4[e];
+            for (int e = 0; e < 4; ++e)
+              v[e] = PRE ? __builtin_fmaf(v[e] - to[k][e], sc4[e], to[k][e]) : to[k][e] + (v[e] - to[k][e]) * sc4[e];
           }
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32_t, v), rs_c, toff + i * tstep + ps * 512, 0, 0);
           if constexpr (COPY) {
@@ -1084,8 +1266,8 @@ __global__ __launch_bounds__(256, 1) void zv_ffn_kernel(FfnParams p) {
         const f32x4 b1 = *reinterpret_cast<const f32x4*>(p.b2 + n + 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          v[e] = rr[g][0][e] + (v[e] + b0[e]);
-          v[4 + e] = rr[g][1][e] + (v[4 + e] + b1[e]);
+          v[e] = PRE ? v[e] + b0[e] : rr[g][0][e] + (v[e] + b0[e]);
+          v[4 + e] = PRE ? v[4 + e] + b1[e] : rr[g][1][e] + (v[4 + e] + b1[e]);
         }
         if constexpr (RV) {
           const f32x4 w0 = *reinterpret_cast<const f32x4*>(vrow + n);
@@ -1172,6 +1354,40 @@ static __global__ void zv_ffn_pack_w2_kernel(const bf16* W, long ldw, int H, bf1
   const int jb = (int)(r & 15), c = (int)(r >> 4);
   out[i] = W[(long)(32 * jb + (l & 31)) * ldw + 32 * c + 16 * s + 8 * (j >> 2) + 4 * (l >> 5) + (j & 3)];
 }
+// the PRE form's packings: W1 with its K in the out^T tile's register order (x is read in place from
+// the accumulators), and the pre-projection weight Wp (512, K) in the W2 chunk format with K in natural
+// order, zero past K:
+//   W1fp[c][s][lane][j] = W1[32 c + (lane & 31)][16 s + 8 (j >> 2) + 4 (lane >> 5) + (j & 3)]
+//   Wpf[kc][jb][s][lane][j] = Wp[32 jb + (lane & 31)][32 kc + 16 s + 8 (lane >> 5) + j]
+static __global__ void zv_ffn_pack_w1p_kernel(const bf16* W, long ldw, int H, bf16* out) {
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= (long)H * FFN_D) return;
+  const int j = (int)(i & 7);
+  long r = i >> 3;
+  const int l = (int)(r & 63); r >>= 6;
+  const int s = (int)(r & 31), c = (int)(r >> 5);
+  out[i] = W[(long)(32 * c + (l & 31)) * ldw + 16 * s + 8 * (j >> 2) + 4 * (l >> 5) + (j & 3)];
+}
+static __global__ void zv_ffn_pack_wp_kernel(const bf16* W, long ldw, int K, int nkp, bf16* out) {
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= (long)nkp * FFN_HC * FFN_D) return;
+  const int j = (int)(i & 7);
+  long r = i >> 3;
+  const int l = (int)(r & 63); r >>= 6;
+  const int s = (int)(r & 1); r >>= 1;
+  const int jb = (int)(r & 15), kc = (int)(r >> 4);
+  const int k = 32 * kc + 16 * s + 8 * (l >> 5) + j;
+  out[i] = k < K ? W[(long)(32 * jb + (l & 31)) * ldw + k] : (bf16)0.f;
+}
+inline int ffn_pre_chunks(int K) { return (K + FFN_HC - 1) / FFN_HC; }
+// L1: the FeedForward's in_proj -> w1fp (H * 512); Lp: the pre-projection (512, K) -> wpf (ffn_pre_chunks(K) * 32 * 512)
+static void ffn_pack_pre_weights(const Linear& L1, int H, bf16* w1fp, const Linear& Lp, bf16* wpf, hipStream_t s) {
+  const long n = (long)H * FFN_D, np = (long)ffn_pre_chunks(Lp.K) * FFN_HC * FFN_D;
+  hipLaunchKernelGGL(zv_ffn_pack_w1p_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, L1.hi, (long)L1.Kpad, H, w1fp);
+  hipLaunchKernelGGL(zv_ffn_pack_wp_kernel, dim3(cdiv(np, 256)), dim3(256), 0, s, Lp.hi, (long)Lp.Kpad, Lp.K,
+                     ffn_pre_chunks(Lp.K), wpf);
+  ZV_LAUNCH_CHECK();
+}
 // both packings of one FeedForward (L1: in_proj (H, 512), L2: out_proj (512, H)) into w1f / w2f, H * 512 each
 static void ffn_pack_weights(const Linear& L1, const Linear& L2, int H, bf16* w1f, bf16* w2f, hipStream_t s) {
   const long n = (long)H * FFN_D;
@@ -1192,12 +1408,12 @@ inline FfnSchedule ffn_schedule(int R, int nc, int blocks_max, bool persistent) 
   return {(int)w, (int)((W + w - 1) / w)};
 }
 
-template <bool RV, bool ORIG, bool COPY, int ABL = 0, int NORM = 0, bool TP = true>
+template <bool RV, bool ORIG, bool COPY, int ABL = 0, int NORM = 0, bool TP = true, bool PRE = false>
 static void launch_ffn_t(const FfnParams& p, int blocks, hipStream_t s, const char* tag) {
   static unsigned long long attr = 0;   // per device
   const size_t lds = ffn_lds_bytes(p.H, NORM != 0);
   if (!((attr >> zv_cur_device()) & 1)) {
-    ZV_CHECK(hipFuncSetAttribute((const void*)zv_ffn_kernel<RV, ORIG, COPY, ABL, NORM, TP>,
+    ZV_CHECK(hipFuncSetAttribute((const void*)zv_ffn_kernel<RV, ORIG, COPY, ABL, NORM, TP, PRE>,
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr |= 1ull << zv_cur_device();
   }
@@ -1208,12 +1424,14 @@ static void launch_ffn_t(const FfnParams& p, int blocks, hipStream_t s, const ch
     if (NORM) extra += (double)g.M * FFN_D * ((g.Cl ? 2 : 0) + (g.C2h ? 2 : 0) + (g.C2l ? 2 : 0));
   }
   const double outs = M * FFN_D;
-  const double bytes = outs * 2 + 2.0 * FFN_D * p.H * 2 +
+  // (PRE: no x read; the pre-projection's operand, weight and FLOPs)
+  const double Kp = PRE ? (double)p.nkp * FFN_HC : 0.0;
+  const double bytes = (PRE ? (M + FFN_D) * Kp * 2 : outs * 2) + 2.0 * FFN_D * p.H * 2 +
                        (NORM ? outs * (4 + 4 + 4 + 2) + extra : outs * (8 + (COPY ? 2 : 0) + (ORIG ? 4 : 0)));
-  g_zv_last_launch = ZvLaunchRec{FFN_BM, FFN_D, 1, (int)RV | (int)ORIG << 1 | (int)COPY << 2 | (int)TP << 3, NORM,
+  g_zv_last_launch = ZvLaunchRec{FFN_BM, FFN_D, 1, (int)RV | (int)ORIG << 1 | (int)COPY << 2 | (int)TP << 3 | (int)PRE << 4, NORM,
                                  0, blocks, p.w};
-  ZvProfScope prof(tag, 4.0 * M * FFN_D * (double)p.H, bytes, s);
-  hipLaunchKernelGGL((zv_ffn_kernel<RV, ORIG, COPY, ABL, NORM, TP>), dim3(blocks), dim3(256), lds, s, p);
+  ZvProfScope prof(tag, 4.0 * M * FFN_D * (double)p.H + 2.0 * M * FFN_D * Kp, bytes, s);
+  hipLaunchKernelGGL((zv_ffn_kernel<RV, ORIG, COPY, ABL, NORM, TP, PRE>), dim3(blocks), dim3(256), lds, s, p);
   ZV_LAUNCH_CHECK();
 }
 
@@ -1224,14 +1442,20 @@ static void launch_ffn(FfnParams p, hipStream_t s, const char* tag, int blocks_m
   ZV_REQUIRE(p.H > 0 && p.H % (2 * FFN_HC) == 0 && ffn_lds_bytes(p.H, p.nb != nullptr) <= 160 * 1024,
              "fused FeedForward: hidden width a multiple of 64 (LDS: at most 8160, 2496 with the BiasNorm epilogue)");
   ZV_REQUIRE(p.nseg >= 1 && p.nseg <= FFN_MAXSEG, "fused FeedForward: 1..4 row ranges");
-  ZV_REQUIRE(p.W1f && p.W2f && p.b1 && p.b2 && p.ldx % 8 == 0 && p.ldx >= FFN_D && p.ldc % 4 == 0 &&
+  ZV_REQUIRE(p.W1f && p.W2f && p.b1 && p.b2 && (p.Wpf || (p.ldx % 8 == 0 && p.ldx >= FFN_D)) && p.ldc % 4 == 0 &&
                  p.ldc >= FFN_D && (p.ldch == 0 || (p.ldch % 8 == 0 && p.ldch >= FFN_D)),
              "fused FeedForward operands (16-B aligned rows of at least 512)");
   const bool rv = p.seg[0].rowvec != nullptr, og = p.seg[0].orig != nullptr, cp = p.seg[0].Ch != nullptr;
+  const bool pre = p.Wpf != nullptr;
+  // the pre-projection form: A's columns [K, 32 nkp) are read (the caller keeps them zero), so its
+  // rows hold at least 32 nkp elements
+  ZV_REQUIRE(!pre || (p.bp && p.nkp >= 1 && p.lda >= (long)p.nkp * FFN_HC && p.lda % 8 == 0 && cp && og),
+             "fused FeedForward pre-projection operands (lda >= Kp, 16-B aligned rows, the bypass or BiasNorm site)");
   int R = 0;
   for (int i = 0; i < p.nseg; ++i) {
     FfnSeg& g = p.seg[i];
-    ZV_REQUIRE(g.M > 0 && g.X && g.resid && g.C && (g.Ch != nullptr) == cp && (g.rowvec != nullptr) == rv &&
+    ZV_REQUIRE(!pre || g.A, "fused FeedForward pre-projection operand");
+    ZV_REQUIRE(g.M > 0 && (g.X || pre) && g.resid && g.C && (g.Ch != nullptr) == cp && (g.rowvec != nullptr) == rv &&
                    (g.orig != nullptr) == og && (!g.Ch || p.ldch > 0),
                "fused FeedForward row range operands");
     g.rb0 = R;
@@ -1260,11 +1484,20 @@ static void launch_ffn(FfnParams p, hipStream_t s, const char* tag, int blocks_m
     ZV_REQUIRE(p.byp, "fused FeedForward + BiasNorm bypass");
     p.norm_scale = expf(p.log_scale);
     // (the transposed epilogue takes the row vector's rows from LDS: groups of >= 32 rows)
-    if (p.seg[0].rowvec && p.rows_per_group < 32) launch_ffn_t<false, false, true, 0, 1, false>(p, sc.blocks, s, tag);
-    else launch_ffn_t<false, false, true, 0, 1>(p, sc.blocks, s, tag);
+    const bool tp = !(p.seg[0].rowvec && p.rows_per_group < 32);
+    if (pre) {
+      if (tp) launch_ffn_t<false, false, true, 0, 1, true, true>(p, sc.blocks, s, tag);
+      else launch_ffn_t<false, false, true, 0, 1, false, true>(p, sc.blocks, s, tag);
+    } else if (tp) launch_ffn_t<false, false, true, 0, 1>(p, sc.blocks, s, tag);
+    else launch_ffn_t<false, false, true, 0, 1, false>(p, sc.blocks, s, tag);
     return;
   }
   if constexpr (ABL != 0) { launch_ffn_t<false, false, true, ABL>(p, sc.blocks, s, tag); return; }
+  if (pre) {   // the bypass site: the row vector, if any, belongs to the pre-projection
+    ZV_REQUIRE(og && cp, "fused FeedForward pre-projection: the bypass site");
+    launch_ffn_t<false, true, true, 0, 0, true, true>(p, sc.blocks, s, tag);
+    return;
+  }
   if (!rv && !og && cp) launch_ffn_t<false, false, true>(p, sc.blocks, s, tag);
   else if (!rv && !og && !cp) launch_ffn_t<false, false, false>(p, sc.blocks, s, tag);
   else if (rv && !og && cp) {

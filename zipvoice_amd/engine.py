@@ -77,7 +77,8 @@ class ZvFfnCheckArgs(ctypes.Structure):
         ("C", ctypes.c_void_p), ("ldc", ctypes.c_int64),
         ("Ch", ctypes.c_void_p), ("Cl", ctypes.c_void_p), ("C2h", ctypes.c_void_p), ("C2l", ctypes.c_void_p),
         ("ldch", ctypes.c_int64),
-        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int),
+        ("K", ctypes.c_int), ("A", ctypes.c_void_p), ("Wp", ctypes.c_void_p), ("bp", ctypes.c_void_p)]
 
 
 class ZvDwconvCheckArgs(ctypes.Structure):
