@@ -369,6 +369,66 @@ typedef struct {
 } zv_bigvgan_check_args;
 int zv_bigvgan_check(zv_bigvgan_check_args* a);
 
+/* The kernels around the decoder, one launch at a time through the launch functions zv_engine calls
+ * (test infrastructure: pins csrc/zv_elem.inc's solve-boundary kernels against float64 in
+ * tests/test_gpu_solve_ref.py; builds no engine, needs no weights; synchronous).  Every output is
+ * canary-filled by the caller and has `guard` guard rows at both ends (flat outputs: guard elements);
+ * what the kernel leaves alone comes back as it was.
+ *   ZV_SV_BUILD_INPUT   x (B * T, Fx), tc (B * T, Ft), sc (B * T, Fs), copies 1 / 2, zero_speech ->
+ *                       oh / ol (guard + copies * B * T + guard, ld), ld >= Fx + Ft + Fs; ol NULL: no lo
+ *                       half.  Rows [0, B T) of two copies are the unconditional ones.  launch[1]: 1 the
+ *                       quad kernel (Fx, Ft, Fs, ld multiples of 4), 0 the scalar one
+ *   ZV_SV_EULER         x (n), v (n, or 2 n with cfg = 1: unconditional then conditional), g, dt; grows (B)
+ *                       or NULL with gmul and per_row (n = B * per_row) -> out (guard + n + guard), updated
+ *                       in place over x
+ *   ZV_SV_CFG_COMBINE   v (2 n), g / grows, gmul, per_row -> out (guard + n + guard)
+ *   ZV_SV_MASK_COPY     mask (n) -> mout (guard + copies * n + guard) bytes
+ *   ZV_SV_FILL          value -> out (guard + n + guard)
+ *   ZV_SV_TEMB          x = t (M), W = freqs (N / 2) -> out (guard + M + guard, N): cos | sin | 0 (odd N)
+ *   ZV_SV_SMALL_LINEAR  x (M, ldin), W (N, ldw), bias (N) or NULL, add (M, N) or NULL, pre 0 / 1 (SwooshR
+ *                       on the input) -> out (guard + M + guard, ld); inplace 1: add is placed in out and
+ *                       read from there.  form -1: the engine's policy (the row-staged kernel where
+ *                       K <= 8192), 0 / 1: the row-staged / the per-output kernel; launch[1] says which
+ *   ZV_SV_POSP          W (M * N, K): M layers' linear_pos weights (N = heads * pos_head_dim, K = pos_dim
+ *                       <= 64), sequence length T -> out (guard + M * (2 T - 1) + guard, N)
+ *   ZV_SV_EMBED         tok (n) int64 in [0, N), W = table (N, C) -> oh / ol (guard + n + guard, ld)
+ *   ZV_SV_SPK_ADD       x (n, C), spk (n) in {-1, 0, 1}, W = table (2, C) -> out (guard + n + guard, C), in
+ *                       place over x
+ *   ZV_SV_TEXT_COND     x = embed (B, S, C), lens = tok_lens, lens2 = feat_lens (0 < tok_lens < S,
+ *                       feat_lens >= 0: checked here on the host) -> out (guard + B * T + guard, C)
+ *   ZV_SV_SPEECH_COND   x = prompt (B, S = Tp, C), lens = prompt_lens -> out (guard + B * T + guard, C)
+ * launch: {kind, kernel form, grid blocks, block threads, 0...}. */
+enum zv_solve_kind { ZV_SV_BUILD_INPUT = 0, ZV_SV_EULER = 1, ZV_SV_CFG_COMBINE = 2, ZV_SV_MASK_COPY = 3,
+                     ZV_SV_FILL = 4, ZV_SV_TEMB = 5, ZV_SV_SMALL_LINEAR = 6, ZV_SV_POSP = 7, ZV_SV_EMBED = 8,
+                     ZV_SV_SPK_ADD = 9, ZV_SV_TEXT_COND = 10, ZV_SV_SPEECH_COND = 11 };
+typedef struct {
+  int kind, guard, form;
+  int B, T, S, C;
+  int Fx, Ft, Fs, copies, zero_speech, cfg;
+  int M, N, K, pre, inplace;
+  float g, dt, gmul, value;
+  int64_t n, per_row, ld, ldin, ldw;
+  const float* x; const float* tc; const float* sc; const float* v; const float* grows;
+  const float* W; const float* bias; const float* add;
+  const int32_t* lens; const int32_t* lens2; const int64_t* tok; const int8_t* spk; const uint8_t* mask;
+  float* out; uint16_t* oh; uint16_t* ol; uint8_t* mout;
+  int launch[8];
+  int num_cus;
+} zv_solve_check_args;
+int zv_solve_check(zv_solve_check_args* a);
+
+/* The solve's host decisions (host only, no GPU; test infrastructure, tests/test_solve_plan.py).
+ * zv_time_steps: the Euler grid zv_euler_sample integrates over, out[0 .. num_step] =
+ * t_shift u / (1 + (t_shift - 1) u), u = torch.linspace(t_start, t_end, num_step + 1) in float32.
+ * zv_cfg_plan: DiffusionModel.forward's branches (solver.py:71-98) for one velocity call at time t:
+ * copies 2 when the rows are doubled (guidance_scale != 0, or per-row scales (has_rows) of which
+ * some are nonzero (rows_nonzero); never in distill), zero_speech 1 when the unconditional copy's
+ * speech condition is zeroed (t > 0.5), else the scale doubled: g = 2 guidance_scale, gmul = 2 (the
+ * factor on per-row scales). */
+int zv_time_steps(float t_start, float t_end, int num_step, float t_shift, float* out);
+int zv_cfg_plan(float t, float guidance_scale, int has_rows, int rows_nonzero, int distill, int* copies,
+                int* zero_speech, float* g, float* gmul);
+
 /* Attention plan (host only, no GPU; test infrastructure): the LDS bytes of the fused
  * attention consumers a layer of sequence length L would launch — SelfAttention (sa_plo < 0:
  * the plain kernel, 0 / 1: the Toeplitz kernel without / with the table's lo half),
@@ -435,7 +495,12 @@ int zv_text_encode(zv_handle h, const int64_t* tokens, const uint8_t* pad,
                    const int8_t* spk, int B, int S, float* out, void* stream);
 
 /* Frame-rate text condition: out[b, f] = embed[b, min(f / (T_b / S_b), S_b)].
- *  tok_lens, feat_lens: [B] int32 device; out: [B, T, feat_dim]. */
+ *  tok_lens, feat_lens: [B] int32 device; out: [B, T, feat_dim].
+ *  Preconditions: embed is [B, S, feat_dim] (the engine's own feat_dim: the call takes no width
+ *  and cannot check the embedding's), with the pad slot, so 0 < tok_lens[b] < S (the kernel divides
+ *  by tok_lens[b] and reads token tok_lens[b] for the frames past the last whole duration), and
+ *  feat_lens[b] >= 0.  The lengths are device values and are not checked (that would take a
+ *  device round trip); B, T > 0 and S > 1 are. */
 int zv_text_condition(zv_handle h, const float* embed, int B, int S, const int32_t* tok_lens,
                       const int32_t* feat_lens, int T, float* out, void* stream);
 

@@ -1,8 +1,9 @@
 """Float64 references for the engine's linear and fused FeedForward kernels (csrc/zv_gemm.inc,
 zv_gemm256.inc, zv_ffn.inc), the ConvolutionModule's depthwise conv (zv_elem.inc's four kernels and
 the fused GLU + conv launch) and the kernels at the stack boundaries (with their case lists, which the CPU and the GPU tests share),
-and the BigVGAN kernels with the implicit-conv GEMM (the last section; its case lists are in
-tests/bigvgan_cases.py); a helper, not a test.  numpy only.
+the BigVGAN kernels with the implicit-conv GEMM (its case lists are in tests/bigvgan_cases.py), and
+the kernels around the decoder (the last section, "solve boundary"; case lists in tests/solve_cases.py);
+a helper, not a test.  numpy only.
 
 Number formats: the 16-bit operand format of a library is "bf16" (8 significant bits) or "f16"
 (IEEE half, 11); round16 is round-to-nearest-even from float64, split16 the engine's hi / lo pair.
@@ -991,3 +992,276 @@ def bv_step_ref(c, split, fmt):
     z2, t2 = bv_act_ref(h1, lens, 1, B, Lmax, Lp, c["alpha2"], c["ibeta2"], c["f"], tol_x=th1)
     return bv_conv_ref(z2, c["w2"], c["bias2"], 1, lens, 1, B, Lmax, Lp, split, fmt, resid=c["x"],
                        tol_a=bv_operand_tol(z2, t2, split, fmt))
+
+
+# --------------------------------------------------------------------------- solve boundary
+# (csrc/zv_elem.inc's kernels around the decoder, one launch at a time through zv_solve_check;
+# tests/test_gpu_solve_ref.py, case lists in tests/solve_cases.py.)  Every reference is written from the
+# model's definition (solver.py, zipvoice.py, zipformer.py as oracle/zipvoice_np.py restates them), in
+# float64; bug= selects a deliberate mistake for the visibility checks of tests/test_kernel_ref.py
+# (host only).
+ONE_PLUS = 1.0 + 2.0 ** -20            # absorbs the second-order terms of a first-order rounding bound
+
+
+def build_input_ref(x, tc, sc, B, T, copies, zero_speech, bug=None):
+    """DiffusionModel.forward's batch (solver.py:83-98) fed to forward_fm_decoder's cat (zipvoice.py:163):
+    rows [0, B T) the unconditional copy (text zeroed; speech zeroed iff zero_speech), rows [B T, 2 B T)
+    the conditional one; one copy: the conditional one.  x (B T, Fx), tc (B T, Ft), sc (B T, Fs) ->
+    (copies B T, Fx + Ft + Fs).
+    bug: "swap" the copies swapped; "text_kept" text not zeroed in the unconditional copy;
+    "speech_flip" zero_speech inverted; "boundary" the first segment one column longer (column Fx
+    continues x's flat array); "no_lo" is the caller's (the lo half left zero)."""
+    cond = np.concatenate([x, tc, sc], axis=1)
+    if bug == "boundary":
+        flat = np.concatenate([x.reshape(-1), [0.0]])
+        cond[:, x.shape[1]] = flat[np.arange(1, x.shape[0] + 1) * x.shape[1]]
+    if copies == 1:
+        return cond
+    zs = bool(zero_speech) != (bug == "speech_flip")
+    unc = np.concatenate([x, tc if bug == "text_kept" else np.zeros_like(tc), np.zeros_like(sc) if zs else sc], axis=1)
+    if bug == "boundary":
+        unc[:, x.shape[1]] = cond[:, x.shape[1]]
+    return np.concatenate([cond, unc] if bug == "swap" else [unc, cond], axis=0)
+
+
+def euler_ref(x, v, cfg, g, dt, grows=None, gmul=1.0, per_row=None, exact=False, bug=None):
+    """One Euler step with the guidance combine (solver.py:100-110, :239): vv = (1 + g) v_cond - g v_uncond
+    (v = [uncond | cond], 2 n values; cfg 0: vv = v), x + vv dt; g per row b = i // per_row as grows[b] gmul
+    where grows is given.  x None: the combine alone.  Returns (value, tol).
+    exact: every fp32 step is asserted exact (dyadic g, gmul, dt; small-integer x, v), tol 0.
+    general: one fp32 rounding (relative 2^-24) per operation, weighted by the float64 magnitude of that
+    operation's result, propagated to the output (contraction into FMA only removes roundings):
+      gi = grows gmul          -> |gi| (|vc| + |vu|)        1 + gi -> |1 + gi| |vc|
+      (1 + gi) vc, gi vu, their difference -> |(1 + gi) vc| + |gi vu| + |vv|
+      vv dt -> |vv dt| (and everything above times |dt|)    x + vv dt -> |x + vv dt|
+    bug: "swap" v_cond and v_uncond swapped; "gmul" ignored; "prev_row" the first element of row k >= 1
+    takes row k - 1's scale; "dt_sign"."""
+    chk = (lambda a, w: assert_fp32_exact(a, w)) if exact else (lambda a, w: a)
+    n = v.shape[0] // 2 if cfg else v.shape[0]
+    if cfg:
+        vu, vc = (v[n:], v[:n]) if bug == "swap" else (v[:n], v[n:])
+        if grows is not None:
+            row = np.arange(n) // per_row
+            if bug == "prev_row":
+                row = np.where((np.arange(n) % per_row == 0) & (row > 0), row - 1, row)
+            gi = chk(np.asarray(grows, np.float64)[row] * (1.0 if bug == "gmul" else gmul), "grows gmul")
+        else:
+            gi = np.full(n, float(g))
+        a, b = chk(chk(1.0 + gi, "1 + g") * vc, "(1 + g) vc"), chk(gi * vu, "g vu")
+        vv = chk(a - b, "vv")
+        tol_vv = U32 * (np.abs(gi) * (np.abs(vc) + np.abs(vu)) + np.abs(1.0 + gi) * np.abs(vc) + np.abs(a) + np.abs(b) + np.abs(vv))
+    else:
+        vv, tol_vv = v, np.zeros(n)
+    if x is None:
+        return vv, (np.zeros(n) if exact else ONE_PLUS * tol_vv)
+    dtt = -dt if bug == "dt_sign" else dt
+    step = chk(vv * dtt, "vv dt")
+    out = chk(x + step, "x + vv dt")
+    tol = abs(dt) * tol_vv + U32 * (np.abs(step) + np.abs(out))
+    return out, (np.zeros(n) if exact else ONE_PLUS * tol)
+
+
+# the kernels' libm forms (cosf, sinf, atanf, logf, log1pf, expf) in fp32 numpy against float64, over the
+# arguments the tests use (tests/test_kernel_ref.py recomputes each): |error| of cos / sin for |arg| <= 60
+# (absolute: |value| <= 1), and of SwooshR in the logaddexp form the small linear applies
+ERR_SINCOS = 1.2 * U32
+
+
+def swoosh_r_lae_f32(x):
+    """zv_common.h swoosh_r_lae: max(y, 0) + log1p(exp(-|y|)) - 0.08 x - 0.313261687, y = x - 1, in fp32."""
+    x = np.asarray(x, _F)
+    y = x - _F(1)
+    return np.maximum(y, _F(0)) + np.log1p(np.exp(-np.abs(y))) - _F(0.08) * x - _F(0.313261687)
+
+
+def err_swoosh_r_lae(x):
+    return 1.7 * U32 * (np.abs(x) + 2.0)
+
+
+def temb_freqs(dim, n=None):
+    """timestep_embedding's frequencies as the engine computes them on the host (fp32):
+    exp(-ln(10000) k / half), k < n (n = half: what the kernel is given)."""
+    half = dim // 2
+    k = np.arange(half if n is None else n, dtype=np.float32)
+    return np.exp(np.float32(-np.log(10000.0)) * k / np.float32(half)).astype(np.float32).astype(np.float64)
+
+
+def temb_ref(t, freqs, dim, bug=None):
+    """timestep_embedding (zipformer.py:47-69): [cos(t f_k) | sin(t f_k) | 0 for an odd dim], of the fp32
+    product t f_k (exact to form in float64) -> (value (M, dim), tol).  tol = TRANS_FACTOR * ERR_SINCOS.
+    bug: "halves" sin first; "freq_index" the sine half reads freqs[k] instead of freqs[k - half] (freqs
+    must then hold 2 half entries)."""
+    half = dim // 2
+    t = np.asarray(t, np.float64)[:, None]
+    arg = (t.astype(np.float32) * freqs[None, :half].astype(np.float32)).astype(np.float64)
+    arg_s = arg
+    if bug == "freq_index":
+        arg_s = (t.astype(np.float32) * freqs[None, half:2 * half].astype(np.float32)).astype(np.float64)
+    out = np.zeros((t.shape[0], dim))
+    c, s = np.cos(arg), np.sin(arg_s)
+    out[:, :half], out[:, half:2 * half] = (s, c) if bug == "halves" else (c, s)
+    return out, np.full(out.shape, TRANS_FACTOR * ERR_SINCOS)
+
+
+def small_linear_ref(x, W, b, add, pre, exact=False, bug=None):
+    """The time / guidance MLPs' linear (zipformer.py:267-278, :726-729): out = act(x) W^T + b + add, act
+    the identity or SwooshR (pre 1).  x (M, K), W (N, K), b (N) or None, add (M, N) or None -> (value, tol).
+    exact (pre 0): dyadic operands, every partial sum in any order an fp32 value (assert_exact_dot), as are
+    the bias and add steps; tol 0.
+    general: the kernels sum lane-strided partial sums of ceil(K / 64) FMAs, then a 6-level tree, then the
+    bias and add: at most ceil(K / 64) + 6 + 2 roundings on any path, each relative 2^-24 of a partial
+    result no larger than S = sum_k |act(x_k) w_k| + |b| + |add|; pre 1 adds sum_k |w_k| tol_act(x_k), tol_act =
+    TRANS_FACTOR * err_swoosh_r_lae.
+    bug: "no_add", "no_bias"; "tail": every output of the last partial block of 32 takes row N - 1's
+    weight and bias."""
+    M, K = x.shape
+    N = W.shape[0]
+    a = swoosh_r(x) if pre else x
+    Wk, bk = W, b
+    if bug == "tail" and N % 32:
+        Wk = W.copy()
+        Wk[N - N % 32:] = W[N - 1]
+        if b is not None:
+            bk = b.copy()
+            bk[N - N % 32:] = b[N - 1]
+    acc = assert_exact_dot(a, Wk) if exact else a @ Wk.T
+    S = np.abs(a) @ np.abs(Wk).T
+    chk = (lambda v, w: assert_fp32_exact(v, w)) if exact else (lambda v, w: v)
+    if b is not None and bug != "no_bias":
+        acc, S = chk(acc + bk, "+ bias"), S + np.abs(bk)
+    if add is not None and bug != "no_add":
+        acc, S = chk(acc + add, "+ add"), S + np.abs(add)
+    if exact:
+        assert not pre
+        return acc, np.zeros_like(acc)
+    tol = (-(-K // 64) + 8) * U32 * S * ONE_PLUS
+    if pre:
+        tol = tol + (TRANS_FACTOR * err_swoosh_r_lae(x)) @ np.abs(Wk).T
+    return acc, tol
+
+
+def posp_angle(L, D):
+    """extend_pe's angle per row (zipformer.py:983-1032) in float64: row n encodes the offset x = n - (L - 1);
+    x_c = c sgn(x) (ln(|x| + c) - ln c), c = sqrt(D); xa = atan(x_c / (D / 2 pi)).  -> (x, xa), (2 L - 1,)."""
+    x = np.arange(-(L - 1), L, dtype=np.float64)
+    c = np.sqrt(float(D))
+    xc = c * np.sign(x) * (np.log(np.abs(x) + c) - np.log(c))
+    return x, np.arctan(xc / (D / (2.0 * np.pi)))
+
+
+def posp_angle_f32(L, D):
+    """The same chain as zv_posp_kernel writes it, in fp32 numpy."""
+    x = np.arange(-(L - 1), L, dtype=np.float32)
+    c = np.sqrt(_F(D))
+    xc = c * np.sign(x) * (np.log(np.abs(x) + c) - np.log(c))
+    return np.arctan(xc / _F(D / (2.0 * np.pi)))
+
+
+def err_posp_angle(x, D):
+    """|error| of the fp32 angle chain: the two logarithms' roundings (each 2^-24 ln(|x| + c)) scaled by c
+    and the length scale, through atan's slope, plus the roundings of x_c, the quotient and atan itself
+    (relative to |xa| <= pi / 2); measured constant, recomputed by tests/test_kernel_ref.py."""
+    c, ls = np.sqrt(float(D)), D / (2.0 * np.pi)
+    xc = c * (np.log(np.abs(x) + c) - np.log(c))
+    return 1.5 * U32 * (c * 2.0 * np.log(np.abs(x) + c) / ls / (1.0 + (xc / ls) ** 2) + np.pi / 2)
+
+
+def posp_table(L, D, bug=None):
+    """CompactRelPositionalEncoding.extend_pe in float64 -> (pe (2 L - 1, D), tol_pe): pe[2 k] =
+    cos(xa (k + 1)), pe[2 k + 1] = sin(xa (k + 1)), pe[D - 1] = 1.
+    tol_pe: a = xa (k + 1) carries (k + 1) TRANS_FACTOR err_posp_angle plus the product's rounding; cos / sin
+    have slope <= 1 and their own TRANS_FACTOR ERR_SINCOS; the constant column is exact.
+    bug: "offset" x = n - L; "mirror" rows reversed; "interleave" cos / sin swapped; "no_one" pe[D - 1]
+    left as the sine; "one_at_D-2"."""
+    x, xa = posp_angle(L, D)
+    if bug == "offset":
+        _, xa2 = posp_angle(L + 1, D)
+        xa = xa2[:2 * L - 1]                       # offsets -L .. L - 2
+    k1 = np.arange(1, D // 2 + 1, dtype=np.float64)
+    ang = xa[:, None] * k1[None]
+    pe, tol = np.zeros((2 * L - 1, D)), np.zeros((2 * L - 1, D))
+    pe[:, 0::2], pe[:, 1::2] = (np.sin(ang), np.cos(ang)) if bug == "interleave" else (np.cos(ang), np.sin(ang))
+    ta = k1[None] * TRANS_FACTOR * err_posp_angle(x, D)[:, None] + U32 * np.abs(ang) + TRANS_FACTOR * ERR_SINCOS
+    tol[:, 0::2] = tol[:, 1::2] = ta
+    if bug == "one_at_D-2":
+        pe[:, D - 2] = 1.0
+    elif bug != "no_one":
+        pe[:, D - 1], tol[:, D - 1] = 1.0, 0.0
+    if bug == "mirror":
+        pe = pe[::-1].copy()
+    return pe, tol
+
+
+def posp_ref(W, L, nl, HPD, D, bug=None):
+    """linear_pos (no bias, zipformer.py:1239) of every layer of a stack on the table: out[l, n, c] =
+    sum_k pe[n, k] W[l HPD + c, k] -> (value (nl (2 L - 1), HPD), tol).  tol = sum_k |W_k| tol_pe_k +
+    (D + 1) 2^-24 sum_k |pe_k W_k| (an FMA chain of D terms).
+    bug: posp_table's, and "prev_layer": layer l >= 1 reads layer l - 1's weight."""
+    pe, tp = posp_table(L, D, None if bug == "prev_layer" else bug)
+    W3 = W.reshape(nl, HPD, D)
+    if bug == "prev_layer":
+        W3 = W3[[0] + list(range(nl - 1))]
+    out = np.einsum("nk,lck->lnc", pe, W3).reshape(nl * (2 * L - 1), HPD)
+    tol = np.einsum("nk,lck->lnc", tp, np.abs(W3)) + (D + 1) * U32 * ONE_PLUS * np.einsum("nk,lck->lnc", np.abs(pe), np.abs(W3))
+    return out, tol.reshape(out.shape)
+
+
+def embed_ref(tok, table):
+    """nn.Embedding (zipvoice.py:205)."""
+    return table[np.asarray(tok, np.int64)]
+
+
+def spk_add_ref(emb, spk, table):
+    """ZipVoiceDialog's speaker-turn embeddings (zipvoice_dialog.py:153-158): + table[0] where the code is
+    0, + table[1] where it is 1, nothing at -1 (padding).  Asserted exact in fp32."""
+    spk = np.asarray(spk)
+    return assert_fp32_exact(emb + (spk == 0)[:, None] * table[0] + (spk == 1)[:, None] * table[1], "emb + spk")
+
+
+def tokens_index(feat_lens, tok_lens, T, bug=None):
+    """prepare_avg_tokens_durations + get_tokens_index (common.py:246-295): every token of utterance b lasts
+    d = feat_lens[b] // tok_lens[b] frames, placed cumulatively; the frames left over take the next index,
+    tok_lens[b], the pad slot.  (bug None equals oracle.zipvoice_np.get_tokens_index: tests/test_kernel_ref.py.)
+    bug: "no_clamp" the left-over frames go on counting tokens every d frames; "clamp_low" they take
+    tok_lens[b] - 1; "d_from_T" d = T // tok_lens[b]; "d0_token0" d = 0 sends every frame to token 0."""
+    idx = np.zeros((len(feat_lens), T), np.int64)
+    for b, (fl, S) in enumerate(zip(feat_lens, tok_lens)):
+        d = (T if bug == "d_from_T" else int(fl)) // int(S)
+        durs = [d] * int(S)
+        cur = 0
+        for i, dd in enumerate(durs):
+            idx[b, cur:min(cur + dd, T)] = i
+            cur = min(cur + dd, T)
+        rest = int(S) - 1 if bug == "clamp_low" else int(S)
+        if bug == "d0_token0" and d == 0:
+            rest = 0
+        idx[b, cur:] = rest
+        if bug == "no_clamp" and d > 0:
+            idx[b, cur:] = np.arange(cur, T) // d
+    return idx
+
+
+def text_cond_ref(emb, tok_lens, feat_lens, T, bug=None):
+    """forward_text_condition (zipvoice.py:234-250): emb (B, S, C) gathered per frame -> (B T, C).
+    A mistaken index past the embedding reads on into the next utterance's rows, as flat memory would."""
+    B, S, C = emb.shape
+    idx = tokens_index(feat_lens, tok_lens, T, bug)
+    flat = np.concatenate([emb.reshape(B * S, C), np.full((T, C), -7.0)])
+    rows = (np.arange(B)[:, None] * S + idx).reshape(-1)
+    return flat[np.minimum(rows, flat.shape[0] - 1)]
+
+
+def speech_cond_ref(pf, plen, T, bug=None):
+    """ZipVoice.sample's speech condition (zipvoice.py:441-451): the prompt features (B, Tp, F) padded with
+    zeros to T frames (or cut), zero from prompt_len on -> (B T, F).
+    bug: "le" frame prompt_len kept; "no_tp" the t < Tp term missing (frames past the prompt read on in
+    flat memory)."""
+    B, Tp, F = pf.shape
+    flat = np.concatenate([pf.reshape(B * Tp, F), np.full((T + 1, F), -7.0)])
+    out = np.zeros((B, T, F))
+    for b in range(B):
+        for t in range(T):
+            keep = (t <= plen[b]) if bug == "le" else (t < plen[b])
+            if keep and (t < Tp or bug in ("no_tp", "le")):
+                out[b, t] = flat[b * Tp + t] if (t < Tp or bug == "no_tp") else 0.0
+    return out.reshape(B * T, F)

@@ -472,3 +472,152 @@ def test_bv_step_reference_composes():
     want = (bvo.conv1d(t, c["w2"], c["bias2"], 1, 1) + x).T
     assert np.abs(ref[:n] - want).max() < 1e-3 and (np.abs(ref[:n] - want) <= 50 * tol[:n] + 1e-4).all()
     assert valid.sum() == sum(c["lens"]) and (tol[valid] > 0).all()
+
+
+# --------------------------------------------------------------------------- solve-boundary references
+# (tests/test_gpu_solve_ref.py; inputs and case lists in tests/solve_cases.py)
+import solve_cases as sc  # noqa: E402
+from oracle import zipvoice_np as zvo  # noqa: E402
+
+
+def _differs(true, bugged, tol, what):
+    """A mutant differs from the true reference by more than the tolerance (exact class: at all) on the
+    GPU test's own inputs."""
+    d = np.abs(np.asarray(true, np.float64) - np.asarray(bugged, np.float64))
+    assert (d > np.asarray(tol) * np.ones_like(d)).any(), f"{what}: the mistake is invisible"
+
+
+def test_solve_fp32_formula_errors():
+    """The measured constants of the solve-boundary tolerances: cos / sin up to 60 rad, SwooshR in the
+    logaddexp form over the small linear's inputs, the positional angle chain over every test's L and D."""
+    a = np.linspace(-60.0, 60.0, 400001).astype(np.float32)
+    e = max(np.abs(np.cos(a).astype(np.float64) - np.cos(a.astype(np.float64))).max(),
+            np.abs(np.sin(a).astype(np.float64) - np.sin(a.astype(np.float64))).max())
+    print(f"cos / sin: {e / kr.U32:.2f} * 2^-24")
+    assert e <= kr.ERR_SINCOS
+    x = np.concatenate([np.linspace(-40.0, 40.0, 200001), 2.0 * np.random.default_rng(0).standard_normal(100000)])
+    x = x.astype(np.float32).astype(np.float64)
+    r = (np.abs(kr.swoosh_r_lae_f32(x).astype(np.float64) - kr.swoosh_r(x)) / kr.err_swoosh_r_lae(x)).max()
+    print(f"SwooshR (logaddexp form): {1.7 * r:.2f} * 2^-24 * (|x| + 2)")
+    assert r <= 1.0
+    worst = 0.0
+    for L, D in sorted({(c[0], c[3]) for c in sc.POSP}):
+        xs, xa = kr.posp_angle(L, D)
+        worst = max(worst, (np.abs(kr.posp_angle_f32(L, D).astype(np.float64) - xa) / kr.err_posp_angle(xs, D)).max())
+    print(f"posP angle: {1.5 * worst:.2f} * err_posp_angle's unit")
+    assert worst <= 1.0
+
+
+def test_solve_refs_match_the_oracle():
+    """The references against oracle/zipvoice_np.py's restatement of the model (fp32) and its index rule."""
+    for T, tl, fl, S in sc.TEXT_COND:
+        assert np.array_equal(kr.tokens_index(fl, tl, T), zvo.get_tokens_index(np.asarray(fl), np.asarray(tl), T))
+    for L, D in ((1, 2), (5, 48), (65, 64)):
+        assert np.abs(kr.posp_table(L, D)[0] - zvo.rel_pos_table(L, D)).max() < 1e-5
+    for dim in sc.TEMB_DIMS:
+        t = np.array([0.0, 0.5, 1.0, 3.0])
+        ref, _ = kr.temb_ref(t, kr.temb_freqs(dim), dim)
+        assert np.abs(ref - zvo.timestep_embedding(t.astype(np.float32), dim)).max() < 1e-6
+    # the doubled batch as the oracle's velocity() builds it
+    x, tc, s = sc.build_inputs(10, 10, 5)
+    B, T = sc.BUILD_B, 5
+    for zs in (0, 1):
+        want = np.concatenate([np.concatenate([x, np.zeros_like(tc), np.zeros_like(s) if zs else s], 1),
+                               np.concatenate([x, tc, s], 1)], 0)
+        assert np.array_equal(kr.build_input_ref(x, tc, s, B, T, 2, zs), want)
+
+
+@pytest.mark.parametrize("fmt", ["bf16", "f16"])
+def test_solve_build_input_mutants_visible(fmt):
+    for Fx, Ft, ld in sc.BUILD_SHAPES:
+        for T in sc.BUILD_T:
+            x, tc, s = sc.build_inputs(Fx, Ft, T)
+            for zs in (0, 1):
+                ref = kr.build_input_ref(x, tc, s, sc.BUILD_B, T, 2, zs)
+                hi, lo = kr.split16(ref, fmt)
+                for bug in ("swap", "text_kept", "speech_flip", "boundary"):
+                    _differs(hi, kr.split16(kr.build_input_ref(x, tc, s, sc.BUILD_B, T, 2, zs, bug=bug), fmt)[0], 0.0,
+                             f"build {bug} ({Fx}, {Ft}) T={T} zs={zs}")
+                _differs(lo, np.zeros_like(lo), 0.0, "build: the lo half dropped")
+            ref1 = kr.build_input_ref(x, tc, s, sc.BUILD_B, T, 1, 0)
+            _differs(ref1, kr.build_input_ref(x, tc, s, sc.BUILD_B, T, 1, 0, bug="boundary"), 0.0, "build boundary, one copy")
+
+
+@pytest.mark.parametrize("klass", ["exact", "general"])
+@pytest.mark.parametrize("T", sc.EULER_T)
+def test_solve_euler_mutants_visible(T, klass):
+    per_row = T * sc.EULER_FX
+    x, v, g, dt = sc.euler_inputs(T, klass)
+    ex = klass == "exact"
+    for mode, grows, gmul in sc.EULER_MODES:
+        cfg = int(mode != "nocfg")
+        vk = v if cfg else v[:x.shape[0]]
+        for xin in (x, None) if cfg else (x,):
+            ref, tol = kr.euler_ref(xin, vk, cfg, g, dt, grows, gmul, per_row, exact=ex)
+            bugs = (["dt_sign"] if xin is not None else []) + (["swap"] if cfg else [])
+            bugs += ["prev_row"] if grows is not None else []
+            bugs += ["gmul"] if grows is not None and gmul != 1.0 else []
+            for bug in bugs:
+                _differs(ref, kr.euler_ref(xin, vk, cfg, g, dt, grows, gmul, per_row, bug=bug)[0], tol, f"euler {mode} {bug}")
+
+
+def test_solve_temb_mutants_visible():
+    for dim in sc.TEMB_DIMS:
+        for M in (1, 3):
+            for which in ("t", "g"):
+                t = sc.temb_t(M, which)
+                if not t.any():
+                    continue
+                ref, tol = kr.temb_ref(t, kr.temb_freqs(dim), dim)
+                _differs(ref, kr.temb_ref(t, kr.temb_freqs(dim), dim, bug="halves")[0], tol, f"temb halves dim={dim}")
+                if dim >= 6:
+                    _differs(ref, kr.temb_ref(t, kr.temb_freqs(dim, 2 * (dim // 2)), dim, bug="freq_index")[0], tol,
+                             f"temb freq_index dim={dim}")
+
+
+@pytest.mark.parametrize("M,N,K,pre,bias,add", sc.SMALL_LINEAR)
+def test_solve_small_linear_mutants_visible(M, N, K, pre, bias, add):
+    for klass in (("exact", "general") if not pre else ("general",)):
+        x, W, b, a = sc.small_linear_inputs(M, N, K, pre, bias, add, klass)
+        ref, tol = kr.small_linear_ref(x, W, b, a, pre, exact=klass == "exact")
+        bugs = (["no_bias"] if bias else []) + (["no_add"] if add else []) + (["tail"] if N % 32 > 1 else [])
+        for bug in bugs:
+            _differs(ref, kr.small_linear_ref(x, W, b, a, pre, bug=bug)[0], tol, f"small linear {bug} {klass}")
+        # a condition on the reference: the tolerance stays far below the outputs' scale
+        if klass == "general":
+            assert np.median(tol) <= 1e-3 * max(np.abs(ref).mean(), 1e-3) * (8 if K > 4096 else 1)
+
+
+@pytest.mark.parametrize("L,nl,HPD,D", sc.POSP)
+def test_solve_posp_mutants_visible(L, nl, HPD, D):
+    for klass, shifts in (("onehot", sc.posp_shifts(nl, HPD, D)), ("general", (0,))):
+        seen = set()
+        for sh in shifts:
+            W = sc.posp_weights(L, nl, HPD, D, klass, sh)
+            ref, tol = kr.posp_ref(W, L, nl, HPD, D)
+            bugs = ["offset", "interleave", "no_one", "one_at_D-2"] + (["mirror"] if L > 1 and D > 2 else [])   # D = 2: cos alone, even in x
+            bugs += ["prev_layer"] if nl > 1 and (klass == "general" or HPD % D) else []
+            for bug in bugs:
+                d = np.abs(ref - kr.posp_ref(W, L, nl, HPD, D, bug=bug)[0])
+                if (d > tol).any():
+                    seen.add(bug)
+            want = set(bugs)
+        assert seen == want, f"posP {klass} L={L} D={D}: invisible {want - seen}"
+
+
+def test_solve_text_side_mutants_visible():
+    for C in sc.TEXT_C:
+        vis = set()
+        for T, tl, fl, S in sc.TEXT_COND:
+            emb = sc.table(len(tl), S, C)
+            ref = kr.text_cond_ref(emb, tl, fl, T)
+            for bug in ("no_clamp", "clamp_low", "d_from_T", "d0_token0"):
+                if (ref != kr.text_cond_ref(emb, tl, fl, T, bug=bug)).any():
+                    vis.add(bug)
+        assert vis == {"no_clamp", "clamp_low", "d_from_T", "d0_token0"}, vis
+        for T, Tp, plen in sc.SPEECH_COND:
+            pf = sc.table(len(plen), Tp, C) + 1.0
+            ref = kr.speech_cond_ref(pf, plen, T)
+            _differs(ref, kr.speech_cond_ref(pf, plen, T, bug="le"), 0.0, "speech t <= plen")
+            if T > Tp:
+                _differs(ref, kr.speech_cond_ref(pf, plen, T, bug="no_tp"), 0.0, "speech t < Tp missing")

@@ -1,6 +1,7 @@
 // Test-infrastructure and microbenchmark entry points of the C ABI: zv_bench_gemm, zv_gemm_selftest,
 // zv_attn_plan, zv_attn2_check, zv_mx8_quantize, zv_mx8_gemm_check, zv_linear_check, zv_ffn_check,
-// zv_dwconv_check, zv_stackedge_check, zv_bigvgan_check.
+// zv_dwconv_check, zv_stackedge_check, zv_bigvgan_check, zv_solve_check (and the host-only zv_time_steps,
+// zv_cfg_plan).
 // None of them builds an engine: each runs one launch (or a timed loop of one launch) of a kernel the
 // engine, the vocoder or BigVGAN dispatch also instantiates, on operands it makes itself, through the
 // launch function they launch it through (the form choice, the grid and the argument order exist
@@ -762,6 +763,183 @@ int zv_stackedge_check(zv_stackedge_check_args* a) {
   const int rec[8] = {kind, ran.form, ran.blocks, ran.threads, 0, 0, 0, 0};
   memcpy(a->launch, rec, sizeof(rec));
   a->num_cus = zv_num_cus();
+  ZV_API_END
+}
+
+// ---------------------------------------------------------------------------
+// zv_solve_check: the kernels around the decoder (operand build, Euler / CFG, mask copy, fill, timestep
+// embedding, the small fp32 linear, the positional projection, the text-side lookups) through the
+// launch functions zv_engine calls (zv_elem.inc), on host arrays with canary-guarded outputs; and the
+// solve's two host decisions, zv_time_steps and zv_cfg_plan (no GPU).
+// ---------------------------------------------------------------------------
+int zv_solve_check(zv_solve_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && a->kind >= ZV_SV_BUILD_INPUT && a->kind <= ZV_SV_SPEECH_COND && a->guard >= 0,
+             "zv_solve_check: bad arguments");
+  const int kind = a->kind;
+  const size_t G = (size_t)a->guard;
+  ChkDev dev;
+  hipStream_t s = nullptr;
+  EdgeLaunch ran{};
+  // a canary-guarded output of `rows` rows of stride ld (guard rows at both ends), as the caller filled it
+  auto up32 = [&](size_t rows, size_t ld) { return dev.up(a->out, (rows + 2 * G) * ld); };
+  auto down32 = [&](float* d, size_t rows, size_t ld) { dev.down(a->out, d, (rows + 2 * G) * ld); };
+  auto sync = [&] { ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize())); };
+  if (kind == ZV_SV_BUILD_INPUT) {
+    const int B = a->B, T = a->T, Fx = a->Fx, Ft = a->Ft, Fs = a->Fs, Fin = Fx + Ft + Fs;
+    ZV_REQUIRE(B > 0 && T > 0 && Fx > 0 && Ft > 0 && Fs > 0 && (a->copies == 1 || a->copies == 2) && a->ld >= Fin &&
+                   a->x && a->tc && a->sc && a->oh,
+               "zv_solve_check: BUILD_INPUT needs x, tc, sc, oh, copies 1 / 2, ld >= Fx + Ft + Fs");
+    const size_t bt = (size_t)B * T, rows = (size_t)a->copies * bt, n16 = (rows + 2 * G) * a->ld;
+    const float* x = dev.up(a->x, bt * Fx);
+    const float* tc = dev.up(a->tc, bt * Ft);
+    const float* sc = dev.up(a->sc, bt * Fs);
+    uint16_t* oh = dev.up(a->oh, n16);
+    uint16_t* ol = a->ol ? dev.up(a->ol, n16) : nullptr;
+    ran = launch_build_input(x, tc, sc, reinterpret_cast<bf16*>(oh) + G * a->ld,
+                             ol ? reinterpret_cast<bf16*>(ol) + G * a->ld : nullptr, a->ld, B, T, Fx, Ft, Fs,
+                             a->copies, a->zero_speech, s);
+    sync();
+    dev.down(a->oh, oh, n16);
+    if (ol) dev.down(a->ol, ol, n16);
+  } else if (kind == ZV_SV_EULER || kind == ZV_SV_CFG_COMBINE) {
+    const bool euler = kind == ZV_SV_EULER;
+    const int cfg = euler ? a->cfg : 1;
+    const long n = a->n;
+    ZV_REQUIRE(n > 0 && a->v && a->out && (cfg == 0 || cfg == 1) && (!euler || a->x), "zv_solve_check: EULER / CFG_COMBINE need v and out (EULER: x)");
+    ZV_REQUIRE(!a->grows || (a->B > 0 && a->per_row > 0 && (long)a->B * a->per_row == n),
+               "zv_solve_check: per-row scales need n = B * per_row");
+    const float* v = dev.up(a->v, (size_t)(cfg ? 2 * n : n));
+    const float* gr = a->grows ? dev.up(a->grows, (size_t)a->B) : nullptr;
+    std::vector<float> ho(a->out, a->out + (size_t)n + 2 * G);
+    if (euler) memcpy(&ho[G], a->x, (size_t)n * sizeof(float));   // in place over x, as the engine's solve
+    float* o = dev.up(ho.data(), ho.size());
+    ran = euler ? launch_euler_update(o + G, v, n, cfg, a->g, a->dt, gr, a->gmul, a->per_row > 0 ? a->per_row : n, s)
+                : launch_cfg_combine(o + G, v, n, a->g, gr, a->gmul, a->per_row > 0 ? a->per_row : n, s);
+    sync();
+    dev.down(a->out, o, (size_t)n + 2 * G);
+  } else if (kind == ZV_SV_MASK_COPY) {
+    ZV_REQUIRE(a->n > 0 && a->copies >= 1 && a->mask && a->mout, "zv_solve_check: MASK_COPY needs the mask and mout");
+    const uint8_t* in = dev.up(a->mask, (size_t)a->n);
+    uint8_t* o = dev.up(a->mout, (size_t)a->n * a->copies + 2 * G);
+    ran = launch_copy_u8(in, o + G, a->n, a->copies, s);
+    sync();
+    dev.down(a->mout, o, (size_t)a->n * a->copies + 2 * G);
+  } else if (kind == ZV_SV_FILL) {
+    ZV_REQUIRE(a->n > 0 && a->n < (1L << 30) && a->out, "zv_solve_check: FILL needs out");
+    float* o = up32((size_t)a->n, 1);
+    ran = launch_fill(o + G, a->value, (int)a->n, s);
+    sync();
+    down32(o, (size_t)a->n, 1);
+  } else if (kind == ZV_SV_TEMB) {
+    const int M = a->M, dim = a->N;
+    ZV_REQUIRE(M > 0 && dim > 1 && a->x && a->W && a->out, "zv_solve_check: TEMB needs t (x), freqs (W), out");
+    const float* t = dev.up(a->x, (size_t)M);
+    const float* fr = dev.up(a->W, (size_t)(dim / 2));
+    float* o = up32((size_t)M, (size_t)dim);
+    ran = launch_timestep_embed(t, fr, o + G * dim, M, dim, s);
+    sync();
+    down32(o, (size_t)M, (size_t)dim);
+  } else if (kind == ZV_SV_SMALL_LINEAR) {
+    const int M = a->M, N = a->N, K = a->K;
+    ZV_REQUIRE(M > 0 && N > 0 && K > 0 && a->ldin >= K && a->ldw >= K && a->ld >= N && a->x && a->W && a->out &&
+                   (a->pre == 0 || a->pre == 1) && a->form >= -1 && a->form <= 1 && (!a->inplace || a->add),
+               "zv_solve_check: SMALL_LINEAR needs x (M, ldin), W (N, ldw), out, pre 0 / 1, form -1 / 0 / 1");
+    const float* in = dev.up(a->x, (size_t)M * a->ldin);
+    const float* W = dev.up(a->W, (size_t)N * a->ldw);
+    const float* b = a->bias ? dev.up(a->bias, (size_t)N) : nullptr;
+    std::vector<float> ho(a->out, a->out + ((size_t)M + 2 * G) * a->ld);
+    std::vector<float> hadd;
+    if (a->add) hadd = chk_pad(a->add, M, N, a->ld);
+    if (a->inplace)                                          // add == out, as the engine's e0 += guid(e1)
+      for (int m = 0; m < M; ++m) memcpy(&ho[(G + m) * a->ld], a->add + (size_t)m * N, (size_t)N * sizeof(float));
+    float* o = dev.up(ho.data(), ho.size());
+    float* oi = o + G * a->ld;
+    const float* add = a->inplace ? oi : (a->add ? dev.up(hadd.data(), hadd.size()) : nullptr);
+    ran = launch_small_linear(in, (int)a->ldin, W, (int)a->ldw, b, add, oi, (int)a->ld, M, N, K, a->pre, a->form, s);
+    sync();
+    down32(o, (size_t)M, (size_t)a->ld);
+  } else if (kind == ZV_SV_POSP) {
+    const int L = a->T, nl = a->M, HPD = a->N, D = a->K;
+    ZV_REQUIRE(L > 0 && nl > 0 && HPD > 0 && D > 0 && a->W && a->out, "zv_solve_check: POSP needs W (nl * HPD, D) and out");
+    const size_t rows = (size_t)nl * (2 * (size_t)L - 1);
+    const float* W = dev.up(a->W, (size_t)nl * HPD * D);
+    float* o = up32(rows, (size_t)HPD);
+    ran = launch_posp(W, o + G * HPD, L, nl, HPD, D, s);
+    sync();
+    down32(o, rows, (size_t)HPD);
+  } else if (kind == ZV_SV_EMBED) {
+    const int C = a->C, V = a->N;
+    const long n = a->n;
+    ZV_REQUIRE(n > 0 && C > 0 && V > 0 && a->ld >= C && a->tok && a->W && a->oh, "zv_solve_check: EMBED needs tok (n), W (N, C), oh");
+    for (long i = 0; i < n; ++i) ZV_REQUIRE(a->tok[i] >= 0 && a->tok[i] < V, "zv_solve_check: token outside the table");
+    const int64_t* tok = dev.up(a->tok, (size_t)n);
+    const float* tab = dev.up(a->W, (size_t)V * C);
+    const size_t n16 = ((size_t)n + 2 * G) * a->ld;
+    uint16_t* oh = dev.up(a->oh, n16);
+    uint16_t* ol = a->ol ? dev.up(a->ol, n16) : nullptr;
+    ran = launch_embed(tok, tab, reinterpret_cast<bf16*>(oh) + G * a->ld, ol ? reinterpret_cast<bf16*>(ol) + G * a->ld : nullptr,
+                       a->ld, n, C, s);
+    sync();
+    dev.down(a->oh, oh, n16);
+    if (ol) dev.down(a->ol, ol, n16);
+  } else if (kind == ZV_SV_SPK_ADD) {
+    const int C = a->C;
+    const long n = a->n;
+    ZV_REQUIRE(n > 0 && C > 0 && a->x && a->spk && a->W && a->out, "zv_solve_check: SPK_ADD needs x (n, C), spk (n), W (2, C), out");
+    for (long i = 0; i < n; ++i) ZV_REQUIRE(a->spk[i] >= -1 && a->spk[i] <= 1, "zv_solve_check: speaker code outside {-1, 0, 1}");
+    const int8_t* spk = dev.up(a->spk, (size_t)n);
+    const float* tab = dev.up(a->W, (size_t)2 * C);
+    std::vector<float> ho(a->out, a->out + ((size_t)n + 2 * G) * C);
+    memcpy(&ho[G * C], a->x, (size_t)n * C * sizeof(float));    // in place, as text_encode's output
+    float* o = dev.up(ho.data(), ho.size());
+    ran = launch_spk_add(o + G * C, spk, tab, n, C, s);
+    sync();
+    down32(o, (size_t)n, (size_t)C);
+  } else if (kind == ZV_SV_TEXT_COND) {
+    const int B = a->B, T = a->T, S = a->S, C = a->C;
+    ZV_REQUIRE(B > 0 && T > 0 && S > 1 && C > 0 && a->x && a->lens && a->lens2 && a->out,
+               "zv_solve_check: TEXT_COND needs x (B, S, C), lens (tokens), lens2 (frames), out");
+    for (int b = 0; b < B; ++b)
+      ZV_REQUIRE(a->lens[b] > 0 && a->lens[b] < S && a->lens2[b] >= 0, "zv_solve_check: 0 < tok_lens < S, feat_lens >= 0");
+    const float* emb = dev.up(a->x, (size_t)B * S * C);
+    const int* tl = dev.up(a->lens, (size_t)B);
+    const int* fl = dev.up(a->lens2, (size_t)B);
+    float* o = up32((size_t)B * T, (size_t)C);
+    ran = launch_text_cond(emb, S, C, tl, fl, o + G * C, B, T, s);
+    sync();
+    down32(o, (size_t)B * T, (size_t)C);
+  } else {   // ZV_SV_SPEECH_COND
+    const int B = a->B, T = a->T, Tp = a->S, F = a->C;
+    ZV_REQUIRE(B > 0 && T > 0 && Tp > 0 && F > 0 && a->x && a->lens && a->out,
+               "zv_solve_check: SPEECH_COND needs x (B, S = Tp, C), lens (prompt lengths), out");
+    const float* pf = dev.up(a->x, (size_t)B * Tp * F);
+    const int* pl = dev.up(a->lens, (size_t)B);
+    float* o = up32((size_t)B * T, (size_t)F);
+    ran = launch_speech_cond(pf, Tp, pl, o + G * F, B, T, F, s);
+    sync();
+    down32(o, (size_t)B * T, (size_t)F);
+  }
+  const int rec[8] = {kind, ran.form, ran.blocks, ran.threads, 0, 0, 0, 0};
+  memcpy(a->launch, rec, sizeof(rec));
+  a->num_cus = zv_num_cus();
+  ZV_API_END
+}
+
+int zv_time_steps(float t_start, float t_end, int num_step, float t_shift, float* out) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(num_step >= 0 && out, "zv_time_steps: num_step >= 0 and out (num_step + 1 floats)");
+  const std::vector<float> ts = solve_time_steps(t_start, t_end, num_step, t_shift);
+  memcpy(out, ts.data(), ts.size() * sizeof(float));
+  ZV_API_END
+}
+
+int zv_cfg_plan(float t, float guidance_scale, int has_rows, int rows_nonzero, int distill, int* copies,
+                int* zero_speech, float* g, float* gmul) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(copies && zero_speech && g && gmul, "zv_cfg_plan: null output");
+  const CfgPlan p = cfg_plan(t, guidance_scale, has_rows != 0, rows_nonzero != 0, distill != 0);
+  *copies = p.copies; *zero_speech = p.zero_speech; *g = p.g; *gmul = p.gmul;
   ZV_API_END
 }
 

@@ -6,6 +6,9 @@
 #include "zv_gemm.inc"
 
 // ---- decoder input: xt = cat[x, text_c, speech_c] with CFG batch doubling --
+// (this kernel, its quad form, the Euler / CFG, fill, timestep, posP and small-linear kernels below and
+// the mask copy and text-side kernels at the end of the file are pinned against float64 through their
+// launch functions: zv_solve_check, tests/test_gpu_solve_ref.py)
 // DiffusionModel.forward (solver.py:83-98) + forward_fm_decoder (zipvoice.py:163).
 // rows [0,B) = uncond (text zeroed; speech zeroed iff zero_speech_uncond),
 // rows [B,2B) = cond.  Without CFG (ncopies = 1) row b = cond.  Written as the
@@ -919,4 +922,150 @@ __global__ void zv_speech_cond_kernel(const float* pf, int Tp, const int* plen, 
     const int b = (int)(bt / T);
     out[idx] = (t < plen[b] && t < Tp) ? pf[((long)b * Tp + t) * F + f] : 0.f;
   }
+}
+
+// ---- the solve-boundary launches (zv_engine, zv_text_condition / zv_speech_condition and ---------
+// zv_solve_check): what turns (x, text, speech, t, g) into the decoder's operand and velocities back
+// into x.  Pinned against float64 one kernel at a time (zv_solve_check, tests/test_gpu_solve_ref.py:
+// segment and copy boundaries, row boundaries of the per-row guidance, the grid-stride second trip,
+// every column of the positional table, token / prompt boundaries); the host decisions below them
+// (cfg_plan, solve_time_steps) in tests/test_solve_plan.py.  Each returns what it launched, as the
+// stack-boundary launches above.
+
+// form 1: four features per thread (every segment and the row stride a multiple of 4); 0: one
+static EdgeLaunch launch_build_input(const float* x, const float* tc, const float* sc, bf16* oh, bf16* ol, long ld,
+                                     int B, int T, int Fx, int Ft, int Fs, int copies, int zero_speech,
+                                     hipStream_t s) {
+  const long rows = (long)copies * B * T;
+  const int Fin = Fx + Ft + Fs;
+  const bool quad = Fx % 4 == 0 && Ft % 4 == 0 && Fs % 4 == 0 && ld % 4 == 0;
+  const dim3 grid = quad ? grid1d(rows * Fin / 4) : grid1d(rows * Fin);
+  if (quad)
+    hipLaunchKernelGGL(zv_build_input4_kernel, grid, dim3(256), 0, s, x, tc, sc, oh, ol, ld, B, T, Fx, Ft, Fs,
+                       copies, zero_speech);
+  else
+    hipLaunchKernelGGL(zv_build_input_kernel, grid, dim3(256), 0, s, x, tc, sc, oh, ol, ld, B, T, Fx, Ft, Fs,
+                       copies, zero_speech);
+  ZV_LAUNCH_CHECK();
+  return {quad ? 1 : 0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_euler_update(float* x, const float* v, long n, int cfg, float g, float dt,
+                                      const float* grows, float gmul, long per_row, hipStream_t s) {
+  const dim3 grid = grid1d(n);
+  hipLaunchKernelGGL(zv_euler_update_kernel, grid, dim3(256), 0, s, x, v, n, cfg, g, dt, grows, gmul, per_row);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_cfg_combine(float* out, const float* v, long n, float g, const float* grows, float gmul,
+                                     long per_row, hipStream_t s) {
+  const dim3 grid = grid1d(n);
+  hipLaunchKernelGGL(zv_cfg_combine_kernel, grid, dim3(256), 0, s, out, v, n, g, grows, gmul, per_row);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_copy_u8(const uint8_t* in, uint8_t* out, long n, int copies, hipStream_t s) {
+  const dim3 grid = grid1d(n * copies);
+  hipLaunchKernelGGL(zv_copy_u8_kernel, grid, dim3(256), 0, s, in, out, n, copies);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_fill(float* p, float v, int n, hipStream_t s) {
+  const dim3 grid(cdiv(n, 256));
+  hipLaunchKernelGGL(zv_fill_kernel, grid, dim3(256), 0, s, p, v, n);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_timestep_embed(const float* t, const float* freqs, float* out, int M, int dim,
+                                        hipStream_t s) {
+  const dim3 grid = grid1d(M * dim);
+  hipLaunchKernelGGL(zv_timestep_embed_kernel, grid, dim3(256), 0, s, t, freqs, out, M, dim);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_posp(const float* W, float* out, int L, int nl, int HPD, int D, hipStream_t s) {
+  ZV_REQUIRE(D > 0 && D <= POSP_MAXD, "positional dimension above POSP_MAXD");
+  const dim3 grid((unsigned)cdiv((long)nl * (2L * L - 1) * HPD, 256L));
+  hipLaunchKernelGGL(zv_posp_kernel, grid, dim3(256), 0, s, W, out, L, nl, HPD, D);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+// form 0: one block per (row, 32 outputs) with the row's activation staged in LDS; 1: one wave per
+// output, only where the row does not fit LDS.  form < 0: this policy; 0 / 1 force a kernel (tests)
+constexpr int SL_ROWS_MAXK = 8192;
+static EdgeLaunch launch_small_linear(const float* in, int ldin, const float* W, int ldw, const float* b,
+                                      const float* add, float* out, int ldout, int M, int N, int K, int pre,
+                                      int form, hipStream_t s) {
+  const bool fits = M > 0 && K <= SL_ROWS_MAXK;
+  ZV_REQUIRE(form != 0 || fits, "small linear: the row-staged kernel needs M > 0 and K <= 8192");
+  const bool rows = form < 0 ? fits : form == 0;
+  const dim3 grid = rows ? dim3((unsigned)M, (unsigned)cdiv(N, SL_NB)) : dim3((unsigned)cdiv((long)M * N, 4L));
+  if (rows)
+    hipLaunchKernelGGL(zv_small_linear_rows_kernel, grid, dim3(256), (size_t)K * sizeof(float), s, in, ldin, W,
+                       ldw, b, add, out, ldout, M, N, K, pre);
+  else
+    hipLaunchKernelGGL(zv_small_linear_kernel, grid, dim3(256), 0, s, in, ldin, W, ldw, b, add, out, ldout, M,
+                       N, K, pre);
+  ZV_LAUNCH_CHECK();
+  return {rows ? 0 : 1, (int)(grid.x * grid.y), 256};
+}
+static EdgeLaunch launch_embed(const int64_t* tok, const float* table, bf16* oh, bf16* ol, long ld, long n, int C,
+                               hipStream_t s) {
+  const dim3 grid = grid1d(n * C);
+  hipLaunchKernelGGL(zv_embed_kernel, grid, dim3(256), 0, s, tok, table, oh, ol, ld, n, C);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_spk_add(float* emb, const int8_t* spk, const float* table, long n, int C, hipStream_t s) {
+  const dim3 grid = grid1d(n * C);
+  hipLaunchKernelGGL(zv_spk_add_kernel, grid, dim3(256), 0, s, emb, spk, table, n, C);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+// emb (B, S, C) with the pad slot: 0 < tok_lens[b] < S (device values, not checked here)
+static EdgeLaunch launch_text_cond(const float* emb, int S, int C, const int* tok_lens, const int* feat_lens,
+                                   float* out, int B, int T, hipStream_t s) {
+  ZV_REQUIRE(B > 0 && T > 0 && S > 1 && C > 0, "text condition: B, T, C > 0 and S > 1 (a token and the pad slot)");
+  const dim3 grid = grid1d((long)B * T * C);
+  hipLaunchKernelGGL(zv_text_cond_kernel, grid, dim3(256), 0, s, emb, S, C, tok_lens, feat_lens, out, B, T);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_speech_cond(const float* pf, int Tp, const int* plen, float* out, int B, int T, int F,
+                                     hipStream_t s) {
+  ZV_REQUIRE(B > 0 && T > 0 && Tp > 0 && F > 0, "speech condition: B, T, Tp, F > 0");
+  const dim3 grid = grid1d((long)B * T * F);
+  hipLaunchKernelGGL(zv_speech_cond_kernel, grid, dim3(256), 0, s, pf, Tp, plen, out, B, T, F);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+
+// ---- the solve's host decisions (zv_engine::velocity / euler_sample, zv_cfg_plan, zv_time_steps) ----
+// DiffusionModel.forward's branches (solver.py:71-98): whether the rows are doubled (conditional +
+// unconditional copies), whether the unconditional copy's speech is zeroed (t > 0.5), else the scale
+// doubled: g for the scalar form, gmul for per-row scales.  has_rows: per-row scales are given and
+// rows_nonzero says whether any is nonzero ((guidance_scale == 0.0).all() selects the unguided
+// branch).  Distill: never doubled, the scale feeds the guidance embedding as it is.
+struct CfgPlan { int copies, zero_speech; float g, gmul; };
+static CfgPlan cfg_plan(float t, float gscale, bool has_rows, bool rows_nonzero, bool distill) {
+  const bool on = !distill && (has_rows ? rows_nonzero : gscale != 0.0f);
+  CfgPlan p{on ? 2 : 1, 0, gscale, 1.0f};
+  if (on) {
+    if (t > 0.5f) p.zero_speech = 1;
+    else { p.g = gscale * 2.0f; p.gmul = 2.0f; }
+  }
+  return p;
+}
+// torch.linspace float32 (forward half / backward half) + shift, solver.py:256-281
+static std::vector<float> solve_time_steps(float t_start, float t_end, int num_step, float t_shift) {
+  const int steps = num_step + 1;
+  std::vector<float> u(steps);
+  if (steps == 1) u[0] = t_start;
+  else {
+    const float step = (t_end - t_start) / (float)(steps - 1);
+    const int half = steps / 2;
+    for (int i = 0; i < steps; ++i)
+      u[i] = (i < half) ? t_start + step * (float)i : t_end - step * (float)(steps - i - 1);
+  }
+  for (int i = 0; i < steps; ++i) u[i] = t_shift * u[i] / (1.0f + (t_shift - 1.0f) * u[i]);
+  return u;
 }

@@ -702,18 +702,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   // ---------------------------------------------------------------- launch helpers
   void small_linear(const Linear& L, const float* in, int ldin, int M, float* out, int ldout,
                     int pre, const float* add, hipStream_t s) {
-    // one block per (row, 32 outputs) with the row's activation staged in LDS; the per-output
-    // kernel only where the row does not fit LDS
-    if (M > 0 && L.K <= 8192) {
-      hipLaunchKernelGGL(zv_small_linear_rows_kernel, dim3((unsigned)M, (unsigned)cdiv(L.N, SL_NB)), dim3(256),
-                         (size_t)L.K * sizeof(float), s,
-                         in, ldin, L.w32, L.K, L.b, add, out, ldout, M, L.N, L.K, pre);
-    } else {
-      const long n = (long)M * L.N;
-      hipLaunchKernelGGL(zv_small_linear_kernel, dim3((unsigned)cdiv(n, 4L)), dim3(256), 0, s, in, ldin, L.w32,
-                         L.K, L.b, add, out, ldout, M, L.N, L.K, pre);
-    }
-    ZV_LAUNCH_CHECK();
+    launch_small_linear(in, ldin, L.w32, L.K, L.b, add, out, ldout, M, L.N, L.K, pre, -1, s);
   }
 
   bool fp8_mode() const { return cfg.precision == ZV_FP8; }
@@ -1051,11 +1040,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       reuse = pass.posp_reuse && k.L == L && k.nl == nl && k.w == S.pos_w_all && k.buf == posP;
       k = Workspace::PosPKey{L, nl, S.pos_w_all, posP};
     }
-    if (!reuse) {
-      hipLaunchKernelGGL(zv_posp_kernel, dim3((unsigned)cdiv((long)nl * R * HPD, 256L)), dim3(256), 0, s, S.pos_w_all, posP,
-                         L, nl, HPD, Z.pos_dim);
-      ZV_LAUNCH_CHECK();
-    }
+    if (!reuse) launch_posp(S.pos_w_all, posP, L, nl, HPD, Z.pos_dim, s);
     for (size_t li = 0; li < S.layers.size(); ++li)
       layer<SPLIT>(pass, Z, S.layers[li], ws, src, src_a, cur, cur_a, B, L, pad,
                    posP + li * (size_t)R * HPD, temb, li + 1 < S.layers.size(), s, li > 0);
@@ -1085,13 +1070,9 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       const int E = Z.temb_dim;
       float* e0 = ws.temb0.get<float>((size_t)N * 2 * E);
       float* e1 = ws.temb1.get<float>((size_t)N * 2 * E);
-      hipLaunchKernelGGL(zv_timestep_embed_kernel, grid1d(N * E), dim3(256), 0, s, t, temb_freqs,
-                         e0, N, E);
-      ZV_LAUNCH_CHECK();
+      launch_timestep_embed(t, temb_freqs, e0, N, E, s);
       if (Z.has_guid) {
-        hipLaunchKernelGGL(zv_timestep_embed_kernel, grid1d(N * E), dim3(256), 0, s, g,
-                           temb_freqs, e1, N, E);
-        ZV_LAUNCH_CHECK();
+        launch_timestep_embed(g, temb_freqs, e1, N, E, s);
         small_linear(Z.guid, e1, E, N, e0, E, 0, e0, s);   // e0 += guidance_scale_embed(e1)
       }
       small_linear(Z.te0, e0, E, N, e1, 2 * E, 0, nullptr, s);
@@ -1135,13 +1116,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     const bool split = cfg.precision == ZV_FP32 || cfg.precision == ZV_MIXED;   // split input projection
     const long N = (long)copies * B;
     Act xin = ws.xin.get(N * T, round_up(Fin, 64), split);
-    if (Fx % 4 == 0 && Ft % 4 == 0 && xin.ld % 4 == 0)
-      hipLaunchKernelGGL(zv_build_input4_kernel, grid1d(N * T * Fin / 4), dim3(256), 0, s, x, tc, sc,
-                         xin.h, xin.l, xin.ld, B, T, Fx, Ft, Fx, copies, zero_speech);
-    else
-      hipLaunchKernelGGL(zv_build_input_kernel, grid1d(N * T * Fin), dim3(256), 0, s, x, tc, sc,
-                         xin.h, xin.l, xin.ld, B, T, Fx, Ft, Fx, copies, zero_speech);
-    ZV_LAUNCH_CHECK();
+    launch_build_input(x, tc, sc, xin.h, xin.l, xin.ld, B, T, Fx, Ft, Fx, copies, zero_speech, s);
     return xin;
   }
 
@@ -1154,7 +1129,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   // whether a guided call doubles its rows (conditional + unconditional copies), and whether a
   // decoder call of N rows of T frames runs its row blocks on their own streams
   bool cfg_doubles(float g, const float* grows, bool cfg_rows) const {
-    return !distill() && (grows ? cfg_rows : g != 0.0f);
+    return cfg_plan(0.f, g, grows != nullptr, cfg_rows, distill()).copies == 2;
   }
   bool splits_rows(long N, int T) const { return split_streams >= 2 && N >= 2 && N * T >= split_min_rows; }
 
@@ -1224,35 +1199,27 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
                 bool euler, float dt, bool posp_reuse, hipStream_t s) {
     const int Fx = stereo() ? 2 * cfg.feat_dim : cfg.feat_dim;
     const int Fin = 2 * Fx + cfg.feat_dim;
-    const bool cfg_on = cfg_doubles(gscale, grows, cfg_rows);
-    const int copies = cfg_on ? 2 : 1;
+    const CfgPlan plan = cfg_plan(t, gscale, grows != nullptr, cfg_rows, distill());
+    const bool cfg_on = plan.copies == 2;
+    const int copies = plan.copies, zero_speech = plan.zero_speech;
     const int N = copies * B;
-    float g = gscale, gmul = 1.0f;
-    int zero_speech = 0;
-    if (cfg_on) {
-      if (t > 0.5f) zero_speech = 1;
-      else { g = gscale * 2.0f; gmul = 2.0f; }
-    }
+    const float g = plan.g, gmul = plan.gmul;
     Act xin = build_xin(ws_dec, x, tc, sc, B, T, Fx, copies, zero_speech, s);
     const uint8_t* padN = pad;
     if (pad && copies == 2) {
       uint8_t* p2 = ws_dec.mask2.get<uint8_t>((size_t)N * T);
-      hipLaunchKernelGGL(zv_copy_u8_kernel, grid1d((long)N * T), dim3(256), 0, s, pad, p2,
-                         (long)B * T, 2);
-      ZV_LAUNCH_CHECK();
+      launch_copy_u8(pad, p2, (long)B * T, 2, s);
       padN = p2;
     }
     float* tv = ws_dec.tvec.get<float>(N);
-    hipLaunchKernelGGL(zv_fill_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, tv, t, N);
-    ZV_LAUNCH_CHECK();
+    launch_fill(tv, t, N, s);
     const float* gv = nullptr;
     if (distill()) {
       if (grows) {
         gv = grows;   // the guidance embedding takes the per-row scales as they are
       } else {
         float* g1 = ws_dec.gvec.get<float>(N);
-        hipLaunchKernelGGL(zv_fill_kernel, dim3(cdiv(N, 256)), dim3(256), 0, s, g1, gscale, N);
-        ZV_LAUNCH_CHECK();
+        launch_fill(g1, gscale, N, s);
         gv = g1;
       }
     }
@@ -1261,13 +1228,9 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     decoder(xin, Fin, N, T, padN, tv, gv, v, posp_reuse, s);
     const float* gr = cfg_on ? grows : nullptr;
     if (euler) {
-      hipLaunchKernelGGL(zv_euler_update_kernel, grid1d(n), dim3(256), 0, s, const_cast<float*>(x),
-                         v, n, copies == 2 ? 1 : 0, g, dt, gr, gmul, (long)T * Fx);
-      ZV_LAUNCH_CHECK();
+      launch_euler_update(const_cast<float*>(x), v, n, copies == 2 ? 1 : 0, g, dt, gr, gmul, (long)T * Fx, s);
     } else if (copies == 2) {
-      hipLaunchKernelGGL(zv_cfg_combine_kernel, grid1d(n), dim3(256), 0, s, vout, v, n, g, gr,
-                         gmul, (long)T * Fx);
-      ZV_LAUNCH_CHECK();
+      launch_cfg_combine(vout, v, n, g, gr, gmul, (long)T * Fx, s);
     }
   }
 
@@ -1285,7 +1248,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   void euler_sample(float* x, const float* tc, const float* sc, const uint8_t* pad, int B, int T,
                     int num_step, float g, const float* grows, bool cfg_rows, float t0, float t1,
                     float shift, hipStream_t s) {
-    const std::vector<float> ts = time_steps(t0, t1, num_step, shift);
+    const std::vector<float> ts = solve_time_steps(t0, t1, num_step, shift);
     bool graph = graph_mode != 0 && !g_zv_prof.on;
     if (graph && graph_mode == 2)     // no graph where the decoder splits its (CFG-doubled) rows
       graph = !splits_rows((cfg_doubles(g, grows, cfg_rows) ? 2L : 1L) * B, T);
@@ -1353,38 +1316,17 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     ZV_CHECK(hipStreamWaitEvent(s, gev_out, 0));
   }
 
-  static std::vector<float> time_steps(float t_start, float t_end, int num_step, float t_shift) {
-    // torch.linspace float32 (forward half / backward half) + shift, solver.py:256-281
-    const int steps = num_step + 1;
-    std::vector<float> u(steps);
-    if (steps == 1) u[0] = t_start;
-    else {
-      const float step = (t_end - t_start) / (float)(steps - 1);
-      const int half = steps / 2;
-      for (int i = 0; i < steps; ++i)
-        u[i] = (i < half) ? t_start + step * (float)i : t_end - step * (float)(steps - i - 1);
-    }
-    for (int i = 0; i < steps; ++i) u[i] = t_shift * u[i] / (1.0f + (t_shift - 1.0f) * u[i]);
-    return u;
-  }
-
   void text_encode(const int64_t* tok, const uint8_t* pad, const int8_t* spk, int B, int S,
                    float* out, hipStream_t s) {
     const long n = (long)B * S;
     const int E = cfg.text_embed_dim;
     const bool split = cfg.precision == ZV_FP32 || cfg.precision == ZV_MIXED;   // mixed: the text encoder is split too
     Act emb = ws_txt.emb.get(n, round_up(E, 64), split);
-    hipLaunchKernelGGL(zv_embed_kernel, grid1d(n * E), dim3(256), 0, s, tok, embed_table, emb.h,
-                       emb.l, emb.ld, n, E);
-    ZV_LAUNCH_CHECK();
+    launch_embed(tok, embed_table, emb.h, emb.l, emb.ld, n, E, s);
     const Pass pass;
     if (split) zipformer<3>(pass, txt, ws_txt, emb, 0, B, S, pad, nullptr, nullptr, out, s);
     else zipformer<1>(pass, txt, ws_txt, emb, 0, B, S, pad, nullptr, nullptr, out, s);
-    if (spk && spk_table) {
-      hipLaunchKernelGGL(zv_spk_add_kernel, grid1d(n * cfg.feat_dim), dim3(256), 0, s, out, spk,
-                         spk_table, n, cfg.feat_dim);
-      ZV_LAUNCH_CHECK();
-    }
+    if (spk && spk_table) launch_spk_add(out, spk, spk_table, n, cfg.feat_dim, s);
   }
 };
 
@@ -1647,10 +1589,8 @@ int zv_text_condition(zv_handle h, const float* embed, int B, int S, const int32
                       const int32_t* feat_lens, int T, float* out, void* stream) {
   ZV_API_BEGIN
   check_ready(h);
-  const int C = h->cfg.feat_dim;
-  hipLaunchKernelGGL(zv_text_cond_kernel, grid1d((long)B * T * C), dim3(256), 0,
-                     (hipStream_t)stream, embed, S, C, tok_lens, feat_lens, out, B, T);
-  ZV_LAUNCH_CHECK();
+  ZV_REQUIRE(embed && tok_lens && feat_lens && out, "zv_text_condition: null argument");
+  launch_text_cond(embed, S, h->cfg.feat_dim, tok_lens, feat_lens, out, B, T, (hipStream_t)stream);
   ZV_API_END
 }
 
@@ -1658,9 +1598,8 @@ int zv_speech_condition(zv_handle h, const float* prompt, int B, int Tp, int F,
                         const int32_t* prompt_lens, int T, float* out, void* stream) {
   ZV_API_BEGIN
   check_ready(h);
-  hipLaunchKernelGGL(zv_speech_cond_kernel, grid1d((long)B * T * F), dim3(256), 0,
-                     (hipStream_t)stream, prompt, Tp, prompt_lens, out, B, T, F);
-  ZV_LAUNCH_CHECK();
+  ZV_REQUIRE(prompt && prompt_lens && out, "zv_speech_condition: null argument");
+  launch_speech_cond(prompt, Tp, prompt_lens, out, B, T, F, (hipStream_t)stream);
   ZV_API_END
 }
 

@@ -114,6 +114,17 @@ class ZvBigvganCheckArgs(ctypes.Structure):
         ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
 
 
+class ZvSolveCheckArgs(ctypes.Structure):
+    """zv_solve_check_args (test infrastructure; tests/test_gpu_solve_ref.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kind", "guard", "form", "B", "T", "S", "C", "Fx", "Ft", "Fs", "copies",
+                                            "zero_speech", "cfg", "M", "N", "K", "pre", "inplace")] + [
+        (n, ctypes.c_float) for n in ("g", "dt", "gmul", "value")] + [
+        (n, ctypes.c_int64) for n in ("n", "per_row", "ld", "ldin", "ldw")] + [
+        (n, ctypes.c_void_p) for n in ("x", "tc", "sc", "v", "grows", "W", "bias", "add", "lens", "lens2", "tok",
+                                       "spk", "mask", "out", "oh", "ol", "mout")] + [
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+
+
 # symbol name -> (restype, argtypes); must match include/zipvoice_hip.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -135,6 +146,9 @@ SIGNATURES = {
     "zv_dwconv_check": (_I, [ctypes.POINTER(ZvDwconvCheckArgs)]),
     "zv_stackedge_check": (_I, [ctypes.POINTER(ZvStackedgeCheckArgs)]),
     "zv_bigvgan_check": (_I, [ctypes.POINTER(ZvBigvganCheckArgs)]),
+    "zv_solve_check": (_I, [ctypes.POINTER(ZvSolveCheckArgs)]),
+    "zv_time_steps": (_I, [_F, _F, _I, _F, _P]),
+    "zv_cfg_plan": (_I, [_F, _F, _I, _I, _I, _P, _P, _P, _P]),
     "zv_profile_report": (_I, [ctypes.c_char_p, _I]),
     "zv_host_block_count": (ctypes.c_int64, []),
     "zv_attn_fallbacks": (_I, [_P, _I, _P]),
