@@ -716,6 +716,71 @@ int zv_wavjoin_apply_docs(zv_wavjoin_handle h, const float* wav, int64_t wav_ld,
                           int32_t* spans, void* stream);
 int64_t zv_wavjoin_device_bytes(zv_wavjoin_handle h);
 
+/* ------------------------------------------------------------------------
+ * Seeded noise: standard normals that are a pure function of (seed, stream, element
+ * index), drawn on the device (zipvoice_amd/noise.py seeded_normal; the seeds / seed
+ * arguments of sample, generate_sentence, generate_batch, generate_long and
+ * generate_long_batch).  NO reference counterpart beyond --seed
+ * (zipvoice/bin/infer_zipvoice.py:240, fix_random_seed): the reference speaks one sentence
+ * per call, so there one global seed fixes a request's audio; here a request's noise must
+ * not depend on the batch it is drawn in, so the behaviour is defined here
+ * (tests/noise_ref.py restates it in numpy).
+ *
+ * The noise function.  For a row with unsigned 64-bit seed and 32-bit stream, element
+ * index e (64-bit; e = f * F + c when the row is a (T, F) feature plane):
+ *   block j = e / 4, lane i = e % 4;
+ *   (x0, x1, x2, x3) = Philox4x32-10(counter = (j & 0xffffffff, j >> 32, stream, 0),
+ *                                    key = (seed & 0xffffffff, seed >> 32)),
+ *     with the standard constants: multipliers 0xD2511F53 (on counter word 0) and
+ *     0xCD9E8D57 (on counter word 2), key increments 0x9E3779B9 and 0xBB67AE85, ten rounds;
+ *   u(x) = fl32(fl32(x) * 2^-32 + 2^-33), which lies in (0, 1]; a u that rounds to 1.0 is
+ *     allowed and gives a radius of 0;
+ *   r(u) = sqrt(-2 ln u);
+ *   z0 = r(u(x0)) * sin(2 pi u(x1)), z1 = r(u(x0)) * cos(2 pi u(x1)),
+ *   z2 = r(u(x2)) * sin(2 pi u(x3)), z3 = r(u(x2)) * cos(2 pi u(x3));
+ *   element e is z_i.
+ * The uint32 words are specified bit-exactly (the Random123 known answers hold).  The
+ * normals are specified to a tolerance, because log, sin and cos differ between math
+ * libraries: |z - z_ref| <= 16 * 2^-24 * (1 + r) against a float64 evaluation of the rules
+ * above on the fp32 u.  What the device computes is bitwise the same for the same
+ * (seed, stream, e): it does not depend on B, the row stride, pointer alignment, launch
+ * geometry, or on which operand build (bf16 / fp16) of the library is loaded.  A row's first
+ * len * F elements therefore do not depend on the batch's frame count.
+ * ---------------------------------------------------------------------- */
+/* seeds: [B] device int64, the bit pattern is the unsigned 64-bit seed; streams: [B] device
+ * int32 (the bit pattern is the unsigned 32-bit stream), or NULL for all zero; n elements
+ * per row, ld >= n the row stride in floats.  Writes out[b * ld + e] for b < B, e < n and
+ * nothing else: columns [n, ld) are not touched.  Stateless (no handle, no allocation) and
+ * without a host-blocking runtime call; one launch on `stream`.  Rejected: B <= 0 or
+ * B > 65535, n < 0 or n > 2^40, ld < n, null seeds / out with n > 0.  n == 0 succeeds and
+ * launches nothing. */
+int zv_noise_normal(const int64_t* seeds, const int32_t* streams, int B, int64_t n, int64_t ld,
+                    float* out, void* stream);
+
+/* The two layers of the noise function on their own (test infrastructure;
+ * tests/test_noise_spec.py, tests/test_gpu_noise.py).  Host pointers throughout; where 0
+ * runs the library's host functions (no GPU needed), where 1 the same source as device
+ * functions in a one-off kernel, copied back.
+ * ZV_NOISE_BITS: bits[4 * count] receives Philox4x32-10(counter + k, key) for
+ *   k = 0 .. count - 1, where k is added to the 64-bit number formed by counter[0] (low)
+ *   and counter[1] (high), so the carry from word 0 into word 1 can be reached; counter[2]
+ *   and counter[3] stay.
+ * ZV_NOISE_NORMALS: words[4 * count] caller-chosen uint32 go in as `count` quadruples
+ *   (x0, x1, x2, x3); normals[4 * count] receives their (z0, z1, z2, z3).
+ * count is in [0, 2^26]; 0 succeeds and does nothing. */
+enum { ZV_NOISE_BITS = 0, ZV_NOISE_NORMALS = 1 };
+typedef struct {
+  int mode;                 /* ZV_NOISE_BITS / ZV_NOISE_NORMALS */
+  int where;                /* 0 host, 1 device */
+  uint32_t counter[4];      /* BITS: the start counter */
+  uint32_t key[2];          /* BITS: the key */
+  int64_t count;            /* BITS: blocks; NORMALS: word quadruples */
+  const uint32_t* words;    /* NORMALS in */
+  uint32_t* bits;           /* BITS out */
+  float* normals;           /* NORMALS out */
+} zv_noise_check_args;
+int zv_noise_check(zv_noise_check_args* a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1385,6 +1385,7 @@ static auto api_create(F make) -> decltype(make()) {
 }
 
 #include "zv_checks.inc"
+#include "zv_noise.inc"
 
 extern "C" {
 

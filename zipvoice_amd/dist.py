@@ -89,7 +89,13 @@ def generate_batch_dp(items: Sequence, compute: Callable[[Sequence], Tuple[torch
     every rank.  Multi-channel output (ZipVoice-Dialog-Stereo: one wav per channel,
     ``infer_zipvoice_dialog.py:483-490``) comes as wav (b, n, C) channel-last with lens in
     samples per channel and is gathered as (B, n_max, C).  Returns (wav, lens, (lo, hi)) with
-    (lo, hi) this rank's shard."""
+    (lo, hi) this rank's shard.
+
+    Seeded noise needs nothing here: a request's seed travels inside its item, and
+    ``compute`` hands the shard's seeds to ``generate_batch(seeds=...)`` /
+    ``model.sample(seeds=...)``, whose noise is a function of (seed, stream, element) alone.
+    The output is then independent of the world size; with torch.randn noise every rank
+    draws for its own shard, so it is not."""
     world, rank = _world_rank(group)
     if costs is None:
         costs = [1.0] * len(items)

@@ -125,6 +125,14 @@ class ZvSolveCheckArgs(ctypes.Structure):
         ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
 
 
+class ZvNoiseCheckArgs(ctypes.Structure):
+    """zv_noise_check_args (test infrastructure; tests/test_noise_spec.py, tests/test_gpu_noise.py)."""
+    _fields_ = [("mode", ctypes.c_int), ("where", ctypes.c_int),
+                ("counter", ctypes.c_uint32 * 4), ("key", ctypes.c_uint32 * 2),
+                ("count", ctypes.c_int64),
+                ("words", ctypes.c_void_p), ("bits", ctypes.c_void_p), ("normals", ctypes.c_void_p)]
+
+
 # symbol name -> (restype, argtypes); must match include/zipvoice_hip.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -195,6 +203,9 @@ SIGNATURES = {
     "zv_wavjoin_apply_docs": (_I, [_P, _P, ctypes.c_int64, _P, _P, _I, _I, _P, _I, _P,
                                    ctypes.c_int64, ctypes.c_int64, _P, _P, _P]),
     "zv_wavjoin_device_bytes": (ctypes.c_int64, [_P]),
+    # seeded noise (zipvoice_amd/noise.py)
+    "zv_noise_normal": (_I, [_P, _P, _I, ctypes.c_int64, ctypes.c_int64, _P, _P]),
+    "zv_noise_check": (_I, [ctypes.POINTER(ZvNoiseCheckArgs)]),
 }
 
 _libs: Dict[str, ctypes.CDLL] = {}

@@ -16,10 +16,12 @@ their rate.  ``prepare_prompt`` assembles the dialog / stereo prompts the way
 from __future__ import annotations
 
 import datetime as dt
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+from .noise import check_keys
 
 
 def get_feature_extractor(feature_type: str, num_channels: int = 1):
@@ -110,10 +112,13 @@ def generate_sentence(tokens: List[int], prompt_tokens: List[int], prompt_wav, m
                       feature_extractor, num_step: int = 16, guidance_scale: float = 1.0,
                       speed: float = 1.0, t_shift: float = 0.5, target_rms: float = 0.1,
                       feat_scale: float = 0.1, feat_bias: float = 0.0,
-                      sampling_rate: int = 24000, prompt_sampling_rate: int = 24000
-                      ) -> Tuple[torch.Tensor, Dict[str, float]]:
+                      sampling_rate: int = 24000, prompt_sampling_rate: int = 24000,
+                      seed: Optional[int] = None) -> Tuple[torch.Tensor, Dict[str, float]]:
     """One sentence (infer_zipvoice.py:276-403).  Returns (wav (1, N) on the
-    device, metrics with the reference's keys)."""
+    device, metrics with the reference's keys).  ``seed`` (an int in [0, 2^64); the
+    reference's ``--seed``, :240) keys the initial noise to this request
+    (``noise.seeded_normal``, stream 0): the same seed in a ``generate_batch`` row starts from
+    the same noise.  Without it the noise comes from torch.randn, as before."""
     dev = model.device
     w = torch.as_tensor(np.asarray(prompt_wav) if not torch.is_tensor(prompt_wav) else prompt_wav,
                         dtype=torch.float32)
@@ -130,7 +135,8 @@ def generate_sentence(tokens: List[int], prompt_tokens: List[int], prompt_wav, m
     pred, pred_lens, _, _ = model.sample(
         tokens=[tokens], prompt_tokens=[prompt_tokens], prompt_features=prompt_features,
         prompt_features_lens=prompt_features_lens, speed=speed, t_shift=t_shift,
-        duration="predict", num_step=num_step, guidance_scale=guidance_scale)
+        duration="predict", num_step=num_step, guidance_scale=guidance_scale,
+        seeds=None if seed is None else [seed])
     torch.cuda.synchronize(dev)
     start_vocoder_t = dt.datetime.now()
     wav = vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale, feat_bias=feat_bias,
@@ -189,13 +195,18 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
                    feature_extractor, num_step: int = 16, guidance_scale: float = 1.0,
                    speed: float = 1.0, t_shift: float = 0.5, target_rms: float = 0.1,
                    feat_scale: float = 0.1, feat_bias: float = 0.0, x0=None,
-                   remove_long_sil: bool = False, joiner=None
+                   remove_long_sil: bool = False, joiner=None,
+                   seeds: Optional[Sequence[int]] = None
                    ) -> Tuple[List[torch.Tensor], Dict[str, float]]:
     """Batched serving form: items = [(tokens, prompt_tokens, prompt_wav), ...] with 24 kHz
     prompts, or (tokens, prompt_tokens, prompt_wav, prompt_sampling_rate); prompts at
     other rates are resampled on the device, one batched call per distinct rate.
     Each output equals what ``generate_sentence`` would produce for that item with
     the same initial noise (per-utterance lengths and masks throughout).
+
+    ``seeds`` (one int in [0, 2^64) per item; not together with ``x0``) keys every item's
+    initial noise to the item (``noise.seeded_normal``, stream 0): item i then starts from the
+    noise ``generate_sentence(seed=seeds[i])`` starts from, whatever it is batched with.
 
     ``remove_long_sil`` (upstream ZipVoice's ``--remove-long-sil``; mono and one-channel
     Dialog models, stereo is out of scope): every decoded row goes through
@@ -205,6 +216,10 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
     the trimmed lengths."""
     dev = model.device
     B = len(items)
+    if seeds is not None:
+        if x0 is not None:
+            raise ValueError("give x0 or seeds, not both")
+        seeds, _ = check_keys(seeds, None, B)
     feats, nfr, rms, _ = _prepare_prompts(items, feature_extractor, target_rms, dev)
     prompt_features = (feats + feat_bias) * feat_scale
     if remove_long_sil:
@@ -218,7 +233,7 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
         tokens=[it[0] for it in items], prompt_tokens=[it[1] for it in items],
         prompt_features=prompt_features, prompt_features_lens=nfr, speed=speed,
         t_shift=t_shift, duration="predict", num_step=num_step, guidance_scale=guidance_scale,
-        x0=x0)
+        x0=x0, seeds=seeds)
     out = vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale, feat_bias=feat_bias,
                                   clamp=True)
     if remove_long_sil:

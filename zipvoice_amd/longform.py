@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import engine as _eng
+from .noise import check_keys
 
 
 # ------------------------------------------------------------------------------ chunker
@@ -272,8 +273,13 @@ def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model
                   return_chunks: bool = False, num_step: int = 16, guidance_scale: float = 1.0,
                   speed: float = 1.0, t_shift: float = 0.5, target_rms: float = 0.1,
                   feat_scale: float = 0.1, feat_bias: float = 0.0, sampling_rate: int = 24000,
-                  prompt_sampling_rate: int = 24000):
+                  prompt_sampling_rate: int = 24000, seed: Optional[int] = None):
     """A text of any length with one prompt (mono and one-channel Dialog models).
+
+    ``seed`` (an int in [0, 2^64); not together with ``x0``) keys the noise to the request:
+    chunk k of the text, in text order, draws with ``noise.seeded_normal`` from
+    (seed, stream = k), whatever group it falls into, so ``generate_long_batch`` with the
+    same seed for this request starts every chunk from the same noise.
 
     The prompt is prepared once, as ``infer.generate_sentence`` does; ``chunk_budget`` and
     ``chunk_tokens`` cut the text into K chunks that each fit ``max_seconds`` together with
@@ -285,6 +291,10 @@ def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model
     num_chunks, num_batches); with ``return_chunks`` also the list of per-chunk waveforms
     (untrimmed, before the gain) and the joiner's spans."""
     from .infer import _prompt_rms_normalise, _resampler
+    if seed is not None:
+        if x0 is not None:
+            raise ValueError("give x0 or seed, not both")
+        seed = check_keys([seed])[0][0]
     dev = model.device
     w = torch.as_tensor(np.asarray(prompt_wav) if not torch.is_tensor(prompt_wav) else prompt_wav,
                         dtype=torch.float32)
@@ -317,7 +327,10 @@ def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model
             prompt_features=prompt_features.expand(nb, -1, -1).contiguous(),
             prompt_features_lens=torch.full((nb,), P, dtype=torch.int64, device=dev),
             speed=speed, t_shift=t_shift, duration="predict", num_step=num_step,
-            guidance_scale=guidance_scale, x0=None if x0 is None else x0[gi])
+            guidance_scale=guidance_scale, x0=None if x0 is None else x0[gi],
+            seeds=None if seed is None else [seed] * nb,
+            seed_streams=None if seed is None else list(range(gi * int(batch_size),
+                                                              gi * int(batch_size) + nb)))
         wavs.append(vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale,
                                             feat_bias=feat_bias, clamp=True))
         lens.append(pred_lens)
@@ -409,10 +422,17 @@ def generate_long_batch(requests: Sequence[tuple], model, vocoder, feature_extra
                         joiner: Optional[WavJoiner] = None, x0=None, return_chunks: bool = False,
                         sort_by_length: bool = True, num_step: int = 16,
                         guidance_scale: float = 1.0, speed: float = 1.0, t_shift: float = 0.5,
-                        target_rms: float = 0.1, feat_scale: float = 0.1, feat_bias: float = 0.0):
+                        target_rms: float = 0.1, feat_scale: float = 0.1, feat_bias: float = 0.0,
+                        seeds: Optional[Sequence[int]] = None):
     """Several texts of any length, each with its own prompt, with their chunks pooled into
     shared ``model.sample`` batches (mono and one-channel Dialog models; stereo is out of
     scope).
+
+    ``seeds`` (one int in [0, 2^64) per request; not together with ``x0``) keys the noise to
+    the requests: chunk k of request d, in text order and before any sorting or grouping,
+    draws with ``noise.seeded_normal`` from (seeds[d], stream = k), as
+    ``generate_long(seed=seeds[d])`` draws it, so a request's noise does not depend on the
+    other requests' texts.
 
     requests = [(tokens, prompt_tokens, prompt_wav), ...] with prompts at the model's rate, or
     (tokens, prompt_tokens, prompt_wav, prompt_sampling_rate).  The prompts are prepared as
@@ -431,6 +451,10 @@ def generate_long_batch(requests: Sequence[tuple], model, vocoder, feature_extra
     R = len(requests)
     if R == 0:
         raise ValueError("no requests to synthesise")
+    if seeds is not None:
+        if x0 is not None:
+            raise ValueError("give x0 or seeds, not both")
+        seeds, _ = check_keys(seeds, None, R)
     sampling_rate = feature_extractor.config.sampling_rate
     feats, nfr, rms, nsamp = _prepare_prompts(requests, feature_extractor, target_rms, dev)
     prompt_features = (feats + feat_bias) * feat_scale
@@ -444,6 +468,8 @@ def generate_long_batch(requests: Sequence[tuple], model, vocoder, feature_extra
     hop = vocoder.cfg.hop_length
     K = len(plan.chunks)
     P = [int(v) for v in nfr.tolist()]
+    # chunk i is chunk i - first[doc_of[i]] of its request (join order is text by text)
+    first = [sum(plan.doc_sizes[:d]) for d in range(R)]
 
     torch.cuda.synchronize(dev)
     t0 = dt.datetime.now()
@@ -457,7 +483,9 @@ def generate_long_batch(requests: Sequence[tuple], model, vocoder, feature_extra
             .contiguous(),
             prompt_features_lens=nfr.index_select(0, di), speed=speed, t_shift=t_shift,
             duration="predict", num_step=num_step, guidance_scale=guidance_scale,
-            x0=None if x0 is None else x0[gi])
+            x0=None if x0 is None else x0[gi],
+            seeds=None if seeds is None else [seeds[d] for d in docs],
+            seed_streams=None if seeds is None else [i - first[plan.doc_of[i]] for i in grp])
         wavs.append(vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale,
                                             feat_bias=feat_bias, clamp=True))
         lens.append(pred_lens)

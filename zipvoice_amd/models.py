@@ -17,7 +17,7 @@ Usage (mirrors ``infer_zipvoice.py:549-577``)::
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -25,6 +25,7 @@ import torch
 from .common import make_pad_mask, pad_labels, predict_features_lens, speaker_turn_indices
 from .config import ModelConfig
 from .engine import HipEngine
+from .noise import check_keys, seeded_normal
 from .solver import DistillEulerSolver, EulerSolver
 from .weights import check_state_dict, load_checkpoint_state_dict, synthetic_state_dict
 
@@ -191,10 +192,21 @@ class ZipVoice:
                prompt_features: torch.Tensor, prompt_features_lens: torch.Tensor,
                features_lens: Optional[torch.Tensor] = None, speed: float = 1.0,
                t_shift: float = 1.0, duration: str = "predict", num_step: int = 5,
-               guidance_scale: float = 0.5, x0: Optional[torch.Tensor] = None):
+               guidance_scale: float = 0.5, x0: Optional[torch.Tensor] = None,
+               seeds: Optional[Sequence[int]] = None,
+               seed_streams: Optional[Sequence[int]] = None):
         """zipvoice.py:388-486.  ``x0`` (extra, optional) supplies the initial noise
-        explicitly; otherwise it is drawn with torch.randn on the device as the
-        reference does (:453-458)."""
+        explicitly; ``seeds`` (extra, optional; one int in [0, 2^64) per row, with
+        ``seed_streams`` one int in [0, 2^32) per row, default 0) draws row b with
+        ``noise.seeded_normal`` from (seeds[b], seed_streams[b]), so a row's noise does not
+        depend on what it is batched with; otherwise the noise is drawn with torch.randn on
+        the device as the reference does (:453-458)."""
+        if seeds is not None and x0 is not None:
+            raise ValueError("give x0 or seeds, not both")
+        if seed_streams is not None and seeds is None:
+            raise ValueError("seed_streams needs seeds")
+        if seeds is not None:
+            seeds, seed_streams = check_keys(seeds, seed_streams, len(tokens))
         eng = self._need_engine()
         assert duration in ["real", "predict"]
         prompt_features_lens = prompt_features_lens.to(self.device)
@@ -210,7 +222,9 @@ class ZipVoice:
         batch_size, num_frames, _ = text_condition.shape
         speech_condition = eng.speech_condition(prompt_features, prompt_features_lens, num_frames)
         F = prompt_features.size(-1)
-        if x0 is None:
+        if seeds is not None:
+            x0 = seeded_normal(seeds, (num_frames, F), seed_streams, device=self.device)
+        elif x0 is None:
             x0 = torch.randn(batch_size, num_frames, F, device=self.device)
         elif tuple(x0.shape) != (batch_size, num_frames, F):
             raise ValueError(f"x0 must have shape {(batch_size, num_frames, F)}, got "

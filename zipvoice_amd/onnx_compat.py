@@ -22,6 +22,7 @@ from typing import List
 
 import torch
 
+from .noise import check_keys, seeded_normal
 from .solver import get_time_steps
 
 
@@ -64,10 +65,17 @@ class OnnxModel:
 
 def sample(model: OnnxModel, tokens: List[List[int]], prompt_tokens: List[List[int]],
            prompt_features: torch.Tensor, speed: float = 1.0, t_shift: float = 0.5,
-           guidance_scale: float = 1.0, num_step: int = 16, x0: torch.Tensor = None
-           ) -> torch.Tensor:
-    """infer_zipvoice_onnx.sample (:317-381) on the adapter (``x0`` optional)."""
+           guidance_scale: float = 1.0, num_step: int = 16, x0: torch.Tensor = None,
+           seeds=None) -> torch.Tensor:
+    """infer_zipvoice_onnx.sample (:317-381) on the adapter (``x0`` optional; ``seeds``, one
+    int in [0, 2^64) for the one row and not together with ``x0``, draws the noise
+    ``model.sample(seeds=...)`` draws, on the device, and moves it to the host where this loop
+    keeps ``x``)."""
     assert len(tokens) == len(prompt_tokens) == 1
+    if seeds is not None:
+        if x0 is not None:
+            raise ValueError("give x0 or seeds, not both")
+        seeds, _ = check_keys(seeds, None, 1)
     tokens_t = torch.tensor(tokens, dtype=torch.int64)
     prompt_tokens_t = torch.tensor(prompt_tokens, dtype=torch.int64)
     prompt_features_len = torch.tensor(prompt_features.size(1), dtype=torch.int64)
@@ -75,7 +83,10 @@ def sample(model: OnnxModel, tokens: List[List[int]], prompt_tokens: List[List[i
                                             torch.tensor(speed, dtype=torch.float32))
     batch_size, num_frames, _ = text_condition.shape
     timesteps = get_time_steps(t_start=0.0, t_end=1.0, num_step=num_step, t_shift=t_shift)
-    x = torch.randn(batch_size, num_frames, model.feat_dim) if x0 is None else x0.cpu()
+    if seeds is not None:
+        x = seeded_normal(seeds, (num_frames, model.feat_dim), device=model.model.device).cpu()
+    else:
+        x = torch.randn(batch_size, num_frames, model.feat_dim) if x0 is None else x0.cpu()
     speech_condition = torch.nn.functional.pad(
         prompt_features.cpu(), (0, 0, 0, num_frames - prompt_features.shape[1]))
     g = torch.tensor(guidance_scale, dtype=torch.float32)
