@@ -21,6 +21,7 @@
  *   zv_velocity        DiffusionModel.forward / DistillDiffusionModel.forward
  *                      (zipvoice/models/modules/solver.py:40-165)
  *   zv_euler_sample    EulerSolver.sample (zipvoice/models/modules/solver.py:182-240)
+ *   zv_euler_sample_sched  EulerSolver.sample run per row with that row's own scalars (defined below)
  *   zv_text_encode     ZipVoice.forward_text_embed (zipvoice/models/zipvoice.py:187-212,
  *                      ZipVoiceDialog override zipvoice/models/zipvoice_dialog.py:127-159)
  *   zv_text_condition  ZipVoice.forward_text_condition (zipvoice/models/zipvoice.py:214-251)
@@ -429,6 +430,66 @@ int zv_time_steps(float t_start, float t_end, int num_step, float t_shift, float
 int zv_cfg_plan(float t, float guidance_scale, int has_rows, int rows_nonzero, int distill, int* copies,
                 int* zero_speech, float* g, float* gmul);
 
+/* The scheduled solve's host plan (host only, no GPU; what zv_euler_sample_sched itself runs;
+ * tests/test_sched_plan.py).  Row b of a schedule integrates its own grid ts_b = zv_time_steps(t_start,
+ * t_end, num_step, t_shift) with its own guidance scale, as EulerSolver.sample (solver.py:182-240)
+ * would on that row alone.  The solve runs steps = max_b num_step steps; row b is active at step k iff
+ * k < num_step_b, and a step's active list keeps the input order.  Not distilled: an active row has an
+ * unconditional copy iff its scale is nonzero (solver.py:71 per row), with zv_cfg_plan's branch at the
+ * row's own t (t > 0.5: the copy's speech zeroed and the scale g, else the speech kept and the scale
+ * 2 g).  The step's decoder batch is the `copies` unconditional copies, in active order, then the
+ * `active` conditional rows, in active order (every row active and guided: [uncond B | cond B]).
+ * Distilled: no copies; the row's scale feeds the guidance embedding (act_scale).
+ * zv_sched_plan fills `steps` and `total_rows` (the sum over the steps of copies + active: the decoder
+ * rows of the whole solve) and, for step `step` in [0, steps), `active`, `copies` and every array that
+ * is not NULL: dec_* take copies + active (at most 2 B) entries, act_* take active (at most B).
+ * Rejected: B < 1 (or above 32767), num_step < 1, a non-finite field, t_shift <= 0, step outside
+ * [0, steps). */
+typedef struct { int32_t num_step; float t_start, t_end, t_shift, guidance_scale; } zv_row_sched;
+typedef struct {
+  int32_t steps;             /* K */
+  int32_t active, copies;    /* A, U of the step */
+  int64_t total_rows;
+  int32_t* dec_src;          /* per decoder row: its input row */
+  uint8_t* dec_zero_text;    /* ... 1: text condition zeroed (an unconditional copy) */
+  uint8_t* dec_zero_speech;  /* ... 1: speech condition zeroed */
+  float* dec_t;              /* ... its time */
+  int32_t* act_row;          /* per active row: its input row */
+  float* act_dt;             /* ... ts[k + 1] - ts[k] in float32 */
+  float* act_scale;          /* ... the scale of the update (g or 2 g; 0 without a copy); distill: g */
+  int32_t* act_cond;         /* ... the decoder row of its conditional velocity */
+  int32_t* act_uncond;       /* ... of its unconditional velocity, or -1 */
+} zv_sched_plan_out;
+int zv_sched_plan(const zv_row_sched* rows, int B, int distill, int step, zv_sched_plan_out* out);
+
+/* The scheduled solve's three kernels, one launch at a time through the launch functions zv_engine
+ * calls (test infrastructure: tests/test_gpu_sched_ref.py; builds no engine; synchronous).  Outputs are
+ * canary-filled by the caller with `guard` guard rows (flat outputs: elements) at both ends, as
+ * zv_solve_check's.  Every index is checked on the host before the launch.
+ *   ZV_SC_BUILD_INPUT  x (B * T, Fx), tc (B * T, Ft), sc (B * T, Fs); src / zero_text / zero_speech (N):
+ *                      decoder row j = cat[x, tc, sc] of input row src[j], text / speech zeroed by its
+ *                      flags -> oh / ol (guard + N * T + guard, ld); ol NULL: no lo half.  launch[1]: 1
+ *                      the quad kernel (Fx, Ft, Fs, ld multiples of 4), 0 the scalar one
+ *   ZV_SC_MASK_GATHER  mask (B * T), src (N) -> mout (guard + N * T + guard) bytes
+ *   ZV_SC_EULER        x (B * per_row), v (N * per_row); row / dt / scale / cond / uncond (A, rows
+ *                      distinct): x[row] += ((1 + g) v[cond] - g v[uncond]) dt, or v[cond] dt where
+ *                      uncond < 0 -> out (guard + B * per_row + guard), in place over x
+ * launch: {kind, kernel form, grid.x, block threads, grid.y, 0...}. */
+enum zv_sched_kind { ZV_SC_BUILD_INPUT = 0, ZV_SC_MASK_GATHER = 1, ZV_SC_EULER = 2 };
+typedef struct {
+  int kind, guard;
+  int B, T, N, A;
+  int Fx, Ft, Fs;
+  int64_t ld, per_row;
+  const int32_t* src; const uint8_t* zero_text; const uint8_t* zero_speech;
+  const float* x; const float* tc; const float* sc; const uint8_t* mask; const float* v;
+  const int32_t* row; const float* dt; const float* scale; const int32_t* cond; const int32_t* uncond;
+  float* out; uint16_t* oh; uint16_t* ol; uint8_t* mout;
+  int launch[8];
+  int num_cus;
+} zv_sched_check_args;
+int zv_sched_check(zv_sched_check_args* a);
+
 /* Attention plan (host only, no GPU; test infrastructure): the LDS bytes of the fused
  * attention consumers a layer of sequence length L would launch — SelfAttention (sa_plo < 0:
  * the plain kernel, 0 / 1: the Toeplitz kernel without / with the table's lo half),
@@ -486,6 +547,22 @@ int zv_euler_sample_rows(zv_handle h, float* x, const float* text_c, const float
                          const uint8_t* pad, int B, int T, int num_step,
                          const float* guidance_rows, float t_start, float t_end,
                          float t_shift, void* stream);
+
+/* Scheduled solve: one call integrates B rows, each over its own Euler grid with its own guidance
+ * scale (rows: HOST array of B zv_row_sched, read before the call returns).  Row b ends as
+ * EulerSolver.sample (solver.py:182-240) would leave it when run on that row alone with that row's
+ * scalars; the reference has no batched counterpart (its solver takes one num_step / t_shift per
+ * call).  In place over x like zv_euler_sample; a row is neither read into the decoder nor written
+ * once its steps are done, and a row with scale 0 has no unconditional copy, so the decoder runs
+ * zv_sched_plan's total_rows rows instead of 2 B max(num_step).  The padded length T is the
+ * batch's for every step.  Plain launches on `stream` (no graph); the step tables go up once per
+ * solve from pinned staging owned by the engine, and a warm call makes no host-blocking runtime call
+ * and no device-to-host read (the all-zero-scale question is answered from the host schedule).
+ * zv_sched_stats: out[0] the decoder rows launched, out[1] the steps run by the handle's last
+ * scheduled solve. */
+int zv_euler_sample_sched(zv_handle h, float* x, const float* text_c, const float* speech_c,
+                          const uint8_t* pad, int B, int T, const zv_row_sched* rows, void* stream);
+int zv_sched_stats(zv_handle h, int64_t* out);
 
 /* Text encoder (+ dialog speaker-turn embeddings).
  *  tokens: [B, S] int64 (already padded with pad_id, one extra pad per row);

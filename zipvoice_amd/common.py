@@ -36,9 +36,10 @@ def speaker_turn_indices(tokens_padded: torch.Tensor, spk_a_id: int, spk_b_id: i
 
 
 def predict_features_lens(prompt_features_lens: torch.Tensor, prompt_tokens_lens: torch.Tensor,
-                          tokens_lens: torch.Tensor, speed: float) -> torch.Tensor:
+                          tokens_lens: torch.Tensor, speed) -> torch.Tensor:
     """zipvoice.py:323-325: P + ceil(P / S_p * S_t / speed), in float32 as torch does
-    for int64 / int64 true division."""
+    for int64 / int64 true division.  speed: a float, or a (B,) float32 tensor of per-row
+    speeds (the same float32 arithmetic, row by row)."""
     r = prompt_features_lens.to(torch.float32) / prompt_tokens_lens.to(torch.float32)
     r = r * tokens_lens.to(torch.float32) / speed
     return prompt_features_lens + torch.ceil(r).to(torch.int64)

@@ -943,6 +943,117 @@ int zv_cfg_plan(float t, float guidance_scale, int has_rows, int rows_nonzero, i
   ZV_API_END
 }
 
+// the scheduled solve's host plan (sched_plan, zv_elem.inc: the function zv_engine::euler_sample_sched runs)
+int zv_sched_plan(const zv_row_sched* rows, int B, int distill, int step, zv_sched_plan_out* out) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(out != nullptr, "zv_sched_plan: null output");
+  const SchedPlan p = sched_plan(reinterpret_cast<const SchedRow*>(rows), B, distill != 0);
+  ZV_REQUIRE(step >= 0 && step < p.K, "zv_sched_plan: step outside [0, max num_step)");
+  const SchedStep& st = p.steps[step];
+  out->steps = p.K;
+  out->total_rows = p.total_rows;
+  out->active = st.A;
+  out->copies = st.U;
+  for (int j = 0; j < st.U + st.A; ++j) {
+    if (out->dec_src) out->dec_src[j] = st.src[j];
+    if (out->dec_zero_text) out->dec_zero_text[j] = st.zt[j];
+    if (out->dec_zero_speech) out->dec_zero_speech[j] = st.zs[j];
+    if (out->dec_t) out->dec_t[j] = st.t[j];
+  }
+  for (int i = 0; i < st.A; ++i) {
+    if (out->act_row) out->act_row[i] = st.upd[i].row;
+    if (out->act_dt) out->act_dt[i] = st.upd[i].dt;
+    if (out->act_scale) out->act_scale[i] = distill ? st.gdec[i] : (st.upd[i].vu < 0 ? 0.0f : st.upd[i].g);
+    if (out->act_cond) out->act_cond[i] = st.upd[i].vc;
+    if (out->act_uncond) out->act_uncond[i] = st.upd[i].vu;
+  }
+  ZV_API_END
+}
+
+// ---------------------------------------------------------------------------
+// zv_sched_check: the scheduled solve's kernels (operand build through the row map, mask gather, the
+// scattered Euler update) through the launch functions zv_engine::euler_sample_sched calls, on host
+// arrays with canary-guarded outputs.  Every index is checked here before a launch.
+// ---------------------------------------------------------------------------
+int zv_sched_check(zv_sched_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && a->kind >= ZV_SC_BUILD_INPUT && a->kind <= ZV_SC_EULER && a->guard >= 0, "zv_sched_check: bad arguments");
+  const int kind = a->kind, B = a->B, T = a->T, N = a->N;
+  const size_t G = (size_t)a->guard;
+  ZV_REQUIRE(B > 0 && B <= 32767, "zv_sched_check: B must be in [1, 32767]");
+  ChkDev dev;
+  hipStream_t s = nullptr;
+  EdgeLaunch ran{};
+  int gy = 0;
+  auto sync = [&] { ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize())); };
+  auto row_map = [&](bool flags) {
+    ZV_REQUIRE(N > 0 && N <= 65535 && a->src && (!flags || (a->zero_text && a->zero_speech)),
+               "zv_sched_check: src (and the zero flags) of N decoder rows");
+    std::vector<int> m(N);
+    for (int j = 0; j < N; ++j) {
+      ZV_REQUIRE(a->src[j] >= 0 && a->src[j] < B, "zv_sched_check: a source row outside [0, B)");
+      m[j] = sched_map_entry(a->src[j], flags && a->zero_text[j] != 0, flags && a->zero_speech[j] != 0);
+    }
+    return dev.up(m.data(), (size_t)N);
+  };
+  if (kind == ZV_SC_BUILD_INPUT) {
+    const int Fx = a->Fx, Ft = a->Ft, Fs = a->Fs, Fin = Fx + Ft + Fs;
+    ZV_REQUIRE(T > 0 && Fx > 0 && Ft > 0 && Fs > 0 && a->ld >= Fin && a->x && a->tc && a->sc && a->oh,
+               "zv_sched_check: BUILD_INPUT needs x, tc, sc, oh, ld >= Fx + Ft + Fs");
+    const int* map = row_map(true);
+    const size_t bt = (size_t)B * T, n16 = ((size_t)N * T + 2 * G) * a->ld;
+    const float* x = dev.up(a->x, bt * Fx);
+    const float* tc = dev.up(a->tc, bt * Ft);
+    const float* sc = dev.up(a->sc, bt * Fs);
+    uint16_t* oh = dev.up(a->oh, n16);
+    uint16_t* ol = a->ol ? dev.up(a->ol, n16) : nullptr;
+    ran = launch_build_input_map(x, tc, sc, reinterpret_cast<bf16*>(oh) + G * a->ld,
+                                 ol ? reinterpret_cast<bf16*>(ol) + G * a->ld : nullptr, a->ld, map, N, T, Fx, Ft, Fs, s);
+    gy = N;
+    sync();
+    dev.down(a->oh, oh, n16);
+    if (ol) dev.down(a->ol, ol, n16);
+  } else if (kind == ZV_SC_MASK_GATHER) {
+    ZV_REQUIRE(T > 0 && a->mask && a->mout, "zv_sched_check: MASK_GATHER needs the mask and mout");
+    const int* map = row_map(false);
+    const uint8_t* in = dev.up(a->mask, (size_t)B * T);
+    uint8_t* o = dev.up(a->mout, (size_t)N * T + 2 * G);
+    ran = launch_gather_u8(in, o + G, map, N, T, s);
+    gy = N;
+    sync();
+    dev.down(a->mout, o, (size_t)N * T + 2 * G);
+  } else {
+    const int A = a->A;
+    const long per_row = a->per_row;
+    ZV_REQUIRE(N > 0 && A > 0 && A <= B && per_row > 0 && a->x && a->v && a->out && a->row && a->dt && a->scale &&
+                   a->cond && a->uncond,
+               "zv_sched_check: EULER needs x, v, out and row / dt / scale / cond / uncond of A <= B active rows");
+    std::vector<SchedUpd> upd(A);
+    std::vector<char> seen(B, 0);
+    for (int i = 0; i < A; ++i) {
+      ZV_REQUIRE(a->row[i] >= 0 && a->row[i] < B && !seen[a->row[i]], "zv_sched_check: active rows distinct and inside [0, B)");
+      ZV_REQUIRE(a->cond[i] >= 0 && a->cond[i] < N && a->uncond[i] >= -1 && a->uncond[i] < N,
+                 "zv_sched_check: a velocity row outside [0, N)");
+      seen[a->row[i]] = 1;
+      upd[i] = SchedUpd{a->row[i], a->dt[i], a->scale[i], a->cond[i], a->uncond[i]};
+    }
+    const size_t n = (size_t)B * per_row;
+    const float* v = dev.up(a->v, (size_t)N * per_row);
+    const SchedUpd* du = dev.up(upd.data(), (size_t)A);
+    std::vector<float> ho(a->out, a->out + n + 2 * G);
+    memcpy(&ho[G], a->x, n * sizeof(float));              // in place over x, as the engine's solve
+    float* o = dev.up(ho.data(), ho.size());
+    ran = launch_euler_update_sched(o + G, v, du, A, per_row, s);
+    gy = A;
+    sync();
+    dev.down(a->out, o, n + 2 * G);
+  }
+  const int rec[8] = {kind, ran.form, ran.blocks, ran.threads, gy, 0, 0, 0};
+  memcpy(a->launch, rec, sizeof(rec));
+  a->num_cus = zv_num_cus();
+  ZV_API_END
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------

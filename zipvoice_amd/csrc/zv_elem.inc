@@ -2,6 +2,8 @@
 // All are HBM-bound (bytes per element >> flops): vectorised 16-B accesses
 // where the row width allows, one wave per row for row reductions.
 #pragma once
+#include <cmath>
+
 #include "zv_common.h"
 #include "zv_gemm.inc"
 
@@ -64,6 +66,11 @@ __global__ __launch_bounds__(256) void zv_build_input4_kernel(
 // x = x + v * dt                                      (no cfg)
 // g per row when grows is given (guidance_scale of shape (batch, 1, 1), solver.py:61-62):
 // g_b = grows[b] * gmul (gmul = 2 where t <= 0.5 doubles the scale, solver.py:95)
+// (the arithmetic as device functions: this kernel and the scheduled one below inline the same
+// expressions, so the compiler contracts both into the same FMAs)
+__device__ __forceinline__ float euler_combine(float vc, float vu, float g) { return (1.0f + g) * vc - g * vu; }
+__device__ __forceinline__ float euler_step(float x, float vv, float dt) { return x + vv * dt; }
+
 __global__ void zv_euler_update_kernel(float* x, const float* v, long n, int cfg, float g,
                                        float dt, const float* grows, float gmul, long per_row) {
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n;
@@ -71,12 +78,87 @@ __global__ void zv_euler_update_kernel(float* x, const float* v, long n, int cfg
     float vv;
     if (cfg) {
       const float gi = grows ? grows[i / per_row] * gmul : g;
-      vv = (1.0f + gi) * v[n + i] - gi * v[i];
+      vv = euler_combine(v[n + i], v[i], gi);
     } else {
       vv = v[i];
     }
-    x[i] = x[i] + vv * dt;
+    x[i] = euler_step(x[i], vv, dt);
   }
+}
+
+// ---- the scheduled solve's kernels (zv_engine::euler_sample_sched) ----------
+// One call integrates rows with their own step counts, grids and guidance scales: a step's decoder
+// batch holds only the rows that still have steps left, the needed unconditional copies first.  The
+// host plans every step (sched_plan below) and uploads the tables once per solve; these kernels do
+// zv_build_input_kernel's / zv_copy_u8_kernel's / zv_euler_update_kernel's job through them.  One
+// decoder (or active) row per blockIdx.y: its table entry is a wave-uniform load, once per block.
+// A row map entry: (source input row << 2) | zero_speech << 1 | zero_text.
+__host__ __device__ static inline int sched_map_entry(int src, bool zero_text, bool zero_speech) {
+  return (src << 2) | (zero_speech ? 2 : 0) | (zero_text ? 1 : 0);
+}
+// An active row's update: x[row] += vv dt with vv = (1 + g) v[vc] - g v[vu], or v[vc] where vu < 0.
+struct SchedUpd { int row; float dt, g; int vc, vu; };
+
+// decoder row j = cat[x, text_c, speech_c] of input row map[j] >> 2, text / speech zeroed by its flags
+__global__ __launch_bounds__(256) void zv_build_input_map_kernel(
+    const float* x, const float* tc, const float* sc, bf16* oh, bf16* ol, long ld, const int* map, int T,
+    int Fx, int Ft, int Fs) {
+  const int Fin = Fx + Ft + Fs;
+  const int e = map[blockIdx.y];
+  const long src = (long)(e >> 2) * T, dst = (long)blockIdx.y * T;
+  const bool zt = e & 1, zs = e & 2;
+  const int total = T * Fin;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int t = i / Fin, f = i - t * Fin;
+    float v;
+    if (f < Fx) v = x[(src + t) * Fx + f];
+    else if (f < Fx + Ft) v = zt ? 0.f : tc[(src + t) * Ft + (f - Fx)];
+    else v = zs ? 0.f : sc[(src + t) * Fs + (f - Fx - Ft)];
+    split_store(oh, ol, (dst + t) * ld + f, v);
+  }
+}
+// the quad form (Fx, Ft, Fs and ld multiples of 4), as zv_build_input4_kernel
+__global__ __launch_bounds__(256) void zv_build_input_map4_kernel(
+    const float* x, const float* tc, const float* sc, bf16* oh, bf16* ol, long ld, const int* map, int T,
+    int Fx, int Ft, int Fs) {
+  const int q = (Fx + Ft + Fs) >> 2;              // quads per frame
+  const int e = map[blockIdx.y];
+  const long src = (long)(e >> 2) * T, dst = (long)blockIdx.y * T;
+  const bool zt = e & 1, zs = e & 2;
+  const int total = T * q;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int t = i / q, f = (i - t * q) << 2;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (f < Fx) v = *reinterpret_cast<const f32x4*>(x + (src + t) * Fx + f);
+    else if (f < Fx + Ft) { if (!zt) v = *reinterpret_cast<const f32x4*>(tc + (src + t) * Ft + (f - Fx)); }
+    else if (!zs) v = *reinterpret_cast<const f32x4*>(sc + (src + t) * Fs + (f - Fx - Ft));
+    float vv[4] = {v[0], v[1], v[2], v[3]};
+    store_split4(oh, ol, (dst + t) * ld + f, vv);
+  }
+}
+// the padding mask of the decoder rows: out[j] = in[map[j] >> 2], T bytes each
+__global__ __launch_bounds__(256) void zv_gather_u8_kernel(const uint8_t* in, uint8_t* out, const int* map, int T) {
+  const long src = (long)(map[blockIdx.y] >> 2) * T, dst = (long)blockIdx.y * T;
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < T; t += gridDim.x * blockDim.x) out[dst + t] = in[src + t];
+}
+// the Euler step of the active rows, scattered into x at their input rows (v: the decoder batch's
+// velocities, per_row values each); rows outside the list are not touched
+__global__ __launch_bounds__(256) void zv_euler_update_sched_kernel(float* x, const float* v, const SchedUpd* upd,
+                                                                    long per_row) {
+  const SchedUpd u = upd[blockIdx.y];
+  float* xr = x + (long)u.row * per_row;
+  const float* vc = v + (long)u.vc * per_row;
+  const float* vu = v + (long)(u.vu < 0 ? 0 : u.vu) * per_row;
+  const bool cfg = u.vu >= 0;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < per_row; i += (long)gridDim.x * blockDim.x) {
+    const float vv = cfg ? euler_combine(vc[i], vu[i], u.g) : vc[i];
+    xr[i] = euler_step(xr[i], vv, u.dt);
+  }
+}
+// completion mark of a staged upload: a host-mapped word takes the upload's sequence number
+__global__ void zv_mark_kernel(unsigned* word, unsigned seq) {
+  *reinterpret_cast<volatile unsigned*>(word) = seq;
+  __threadfence_system();
 }
 
 // CFG combine only (forward_fm_decoder-level API): out = (1+g) vc - g vu
@@ -969,6 +1051,44 @@ static EdgeLaunch launch_copy_u8(const uint8_t* in, uint8_t* out, long n, int co
   ZV_LAUNCH_CHECK();
   return {0, (int)grid.x, 256};
 }
+// the scheduled solve's launches: grid (blocks over one row's elements, rows); a row's blocks are
+// capped at SCHED_ROW_BLOCKS (the kernels stride), the rows fill the chip
+constexpr int SCHED_ROW_BLOCKS = 1024;
+static dim3 sched_grid(long per_row, int rows) {
+  ZV_REQUIRE(rows > 0 && rows <= 65535, "scheduled solve: 1 to 65535 decoder rows per step");
+  return dim3((unsigned)std::min<long>(std::max<long>(cdiv(per_row, 256), 1), SCHED_ROW_BLOCKS), (unsigned)rows);
+}
+// map (device, N entries, sched_map_entry): decoder rows [0, N) of T frames.  form as launch_build_input
+static EdgeLaunch launch_build_input_map(const float* x, const float* tc, const float* sc, bf16* oh, bf16* ol,
+                                         long ld, const int* map, int N, int T, int Fx, int Ft, int Fs,
+                                         hipStream_t s) {
+  const int Fin = Fx + Ft + Fs;
+  ZV_REQUIRE(T > 0 && (long)T * Fin < (1L << 30), "scheduled solve: frames times input width must stay under 2^30");
+  const bool quad = Fx % 4 == 0 && Ft % 4 == 0 && Fs % 4 == 0 && ld % 4 == 0;
+  const dim3 grid = sched_grid(quad ? (long)T * Fin / 4 : (long)T * Fin, N);
+  if (quad)
+    hipLaunchKernelGGL(zv_build_input_map4_kernel, grid, dim3(256), 0, s, x, tc, sc, oh, ol, ld, map, T, Fx, Ft, Fs);
+  else
+    hipLaunchKernelGGL(zv_build_input_map_kernel, grid, dim3(256), 0, s, x, tc, sc, oh, ol, ld, map, T, Fx, Ft, Fs);
+  ZV_LAUNCH_CHECK();
+  return {quad ? 1 : 0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_gather_u8(const uint8_t* in, uint8_t* out, const int* map, int N, int T, hipStream_t s) {
+  ZV_REQUIRE(T > 0 && T < (1 << 30), "scheduled solve: 1 to 2^30 - 1 frames");
+  const dim3 grid = sched_grid(T, N);
+  hipLaunchKernelGGL(zv_gather_u8_kernel, grid, dim3(256), 0, s, in, out, map, T);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+// upd (device, A entries): the active rows of one step
+static EdgeLaunch launch_euler_update_sched(float* x, const float* v, const SchedUpd* upd, int A, long per_row,
+                                            hipStream_t s) {
+  ZV_REQUIRE(per_row > 0, "scheduled solve: empty rows");
+  const dim3 grid = sched_grid(per_row, A);
+  hipLaunchKernelGGL(zv_euler_update_sched_kernel, grid, dim3(256), 0, s, x, v, upd, per_row);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
 static EdgeLaunch launch_fill(float* p, float v, int n, hipStream_t s) {
   const dim3 grid(cdiv(n, 256));
   hipLaunchKernelGGL(zv_fill_kernel, grid, dim3(256), 0, s, p, v, n);
@@ -1068,4 +1188,75 @@ static std::vector<float> solve_time_steps(float t_start, float t_end, int num_s
   }
   for (int i = 0; i < steps; ++i) u[i] = t_shift * u[i] / (1.0f + (t_shift - 1.0f) * u[i]);
   return u;
+}
+
+// ---- the scheduled solve's host plan (zv_engine::euler_sample_sched, zv_sched_plan) ----
+// Row b integrates its own grid solve_time_steps(t_start, t_end, num_step, t_shift) with its own scale,
+// as EulerSolver.sample would on that row alone (solver.py:182-240).  Step k of the solve takes the rows
+// with k < num_step, in input order (nothing is sorted or permuted); its decoder batch is the
+// unconditional copies of the guided ones (g != 0; none in distill), in active order, then the
+// conditional rows, in active order.  cfg_plan per row at the row's own t decides whether the copy's
+// speech is zeroed (t > 0.5) or the scale doubled.
+struct SchedRow { int num_step; float t_start, t_end, t_shift, g; };   // zv_row_sched's layout
+struct SchedStep {
+  int A = 0, U = 0;
+  std::vector<int> src;                      // [U + A] source input row of each decoder row
+  std::vector<unsigned char> zt, zs;         // [U + A] text / speech zeroed
+  std::vector<float> t;                      // [U + A]
+  std::vector<SchedUpd> upd;                 // [A]: input row, dt, effective scale, decoder rows of v_cond / v_uncond
+  std::vector<float> gdec;                   // [A]: the row's own scale (distill: the guidance embedding's input)
+};
+struct SchedPlan {
+  int K = 0;
+  long total_rows = 0;
+  std::vector<std::vector<float>> ts;        // per input row: its grid
+  std::vector<SchedStep> steps;
+};
+static SchedPlan sched_plan(const SchedRow* rows, int B, bool distill) {
+  ZV_REQUIRE(rows != nullptr, "scheduled solve: null schedule");
+  ZV_REQUIRE(B >= 1 && B <= 32767, "scheduled solve: B must be in [1, 32767]");
+  SchedPlan p;
+  p.ts.resize(B);
+  for (int b = 0; b < B; ++b) {
+    const SchedRow& r = rows[b];
+    const std::string at = "scheduled solve: row " + std::to_string(b) + ": ";
+    ZV_REQUIRE(r.num_step >= 1, at + "num_step must be at least 1");
+    ZV_REQUIRE(r.num_step <= 65536, at + "num_step above 65536");
+    ZV_REQUIRE(std::isfinite(r.t_start) && std::isfinite(r.t_end) && std::isfinite(r.t_shift) && std::isfinite(r.g),
+               at + "t_start, t_end, t_shift and guidance_scale must be finite");
+    ZV_REQUIRE(r.t_shift > 0.0f, at + "t_shift must be positive");
+    p.ts[b] = solve_time_steps(r.t_start, r.t_end, r.num_step, r.t_shift);
+    p.K = std::max(p.K, r.num_step);
+  }
+  p.steps.resize(p.K);
+  for (int k = 0; k < p.K; ++k) {
+    SchedStep& st = p.steps[k];
+    std::vector<int> act;
+    std::vector<CfgPlan> plan;
+    for (int b = 0; b < B; ++b)
+      if (k < rows[b].num_step) {
+        act.push_back(b);
+        plan.push_back(cfg_plan(p.ts[b][k], rows[b].g, false, false, distill));
+        if (plan.back().copies == 2) ++st.U;
+      }
+    st.A = (int)act.size();
+    const int N = st.U + st.A;
+    st.src.resize(N); st.zt.resize(N); st.zs.resize(N); st.t.resize(N);
+    st.upd.resize(st.A); st.gdec.resize(st.A);
+    int u = 0;
+    for (int i = 0; i < st.A; ++i) {
+      const int b = act[i], jc = st.U + i;
+      const float t = p.ts[b][k];
+      st.src[jc] = b; st.zt[jc] = 0; st.zs[jc] = 0; st.t[jc] = t;
+      int ju = -1;
+      if (plan[i].copies == 2) {
+        ju = u++;
+        st.src[ju] = b; st.zt[ju] = 1; st.zs[ju] = (unsigned char)plan[i].zero_speech; st.t[ju] = t;
+      }
+      st.upd[i] = SchedUpd{b, p.ts[b][k + 1] - t, plan[i].g, jc, ju};
+      st.gdec[i] = rows[b].g;
+    }
+    p.total_rows += N;
+  }
+  return p;
 }

@@ -396,6 +396,9 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     drop_graphs();
     // the stream set outlives the engine: drain what this engine queued on it, then return it
     release_stream_set(streams);
+    // the scheduled solve's staging: a queued upload on the caller's stream may still read a slot
+    if (!sched_slots.empty()) (void)ZV_BLOCKING(hipDeviceSynchronize());
+    for (SchedSlot& sl : sched_slots) (void)ZV_BLOCKING(hipHostFree(sl.base));
     if (gev_in) (void)ZV_BLOCKING(hipEventDestroy(gev_in));
     if (gev_out) (void)ZV_BLOCKING(hipEventDestroy(gev_out));
     for (int i = 0; i < MAX_SPLIT - 1; ++i)
@@ -1316,6 +1319,99 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     ZV_CHECK(hipStreamWaitEvent(s, gev_out, 0));
   }
 
+  // ---------------------------------------------------------------- scheduled solve
+  // zv_euler_sample_sched body: rows with their own grids and scales in one solve (sched_plan,
+  // zv_elem.inc).  The host plans every step and uploads one table per solve: per step the row map
+  // [N], the decoder's t [N], the updates [A] and the guidance embedding's scales [A] (distill), so a
+  // step's t / g vectors are slices of it (no fill launch).  Plain launches on the caller's stream.
+  //
+  // Staging: the table is written into a pinned slot and copied with hipMemcpyAsync; a one-thread
+  // kernel queued behind the copy then writes the upload's sequence number into the slot's
+  // host-mapped word.  A slot is taken again only when that word shows its last upload done (one
+  // volatile host read: no runtime call, so a warm solve stays at zero host-blocking calls), a
+  // fresh slot is allocated otherwise: solves queued back to back each keep their own table until
+  // the GPU has read it.
+  struct SchedSlot {
+    unsigned* base = nullptr;   // pinned + mapped: word 0 the completion mark, the table from byte 64
+    unsigned* mark_dev = nullptr;
+    size_t cap = 0;             // table bytes
+    unsigned issued = 0;
+    bool idle() const { return *reinterpret_cast<volatile unsigned*>(base) == issued; }
+  };
+  std::vector<SchedSlot> sched_slots;
+  DBuf sched_tab;
+  int64_t sched_rows_run = 0, sched_steps_run = 0;
+  SchedSlot& sched_slot(size_t bytes) {
+    for (SchedSlot& sl : sched_slots)
+      if (sl.cap >= bytes && sl.idle()) return sl;
+    SchedSlot sl;
+    sl.cap = (size_t)round_up((long)std::max<size_t>(bytes, 64 * 1024), 4096);
+    ZV_CHECK(ZV_BLOCKING(hipHostMalloc((void**)&sl.base, sl.cap + 64, hipHostMallocMapped | hipHostMallocPortable)));
+    sl.base[0] = 0;
+    ZV_CHECK(ZV_BLOCKING(hipHostGetDevicePointer((void**)&sl.mark_dev, (void*)sl.base, 0)));
+    sched_slots.push_back(sl);
+    return sched_slots.back();
+  }
+
+  void euler_sample_sched(float* x, const float* tc, const float* sc, const uint8_t* pad, int B, int T,
+                          const SchedRow* rows, hipStream_t s) {
+    const SchedPlan plan = sched_plan(rows, B, distill());
+    const int Fx = stereo() ? 2 * cfg.feat_dim : cfg.feat_dim;
+    const int Ft = cfg.feat_dim, Fin = 2 * Fx + Ft;
+    const bool split = cfg.precision == ZV_FP32 || cfg.precision == ZV_MIXED;   // as build_xin
+    // the table: 4-byte words, step after step
+    struct Off { size_t map, t, upd, g; };
+    std::vector<Off> off(plan.K);
+    size_t words = 0;
+    for (int k = 0; k < plan.K; ++k) {
+      const SchedStep& st = plan.steps[k];
+      const size_t N = (size_t)st.U + st.A;
+      off[k] = Off{words, words + N, words + 2 * N, words + 2 * N + 5 * (size_t)st.A};
+      words += 2 * N + 6 * (size_t)st.A;
+    }
+    static_assert(sizeof(SchedUpd) == 20, "SchedUpd is five 4-byte words");
+    SchedSlot& sl = sched_slot(words * 4);
+    unsigned* tab = sl.base + 16;
+    for (int k = 0; k < plan.K; ++k) {
+      const SchedStep& st = plan.steps[k];
+      const int N = st.U + st.A;
+      int* m = reinterpret_cast<int*>(tab + off[k].map);
+      for (int j = 0; j < N; ++j) m[j] = sched_map_entry(st.src[j], st.zt[j] != 0, st.zs[j] != 0);
+      memcpy(tab + off[k].t, st.t.data(), (size_t)N * 4);
+      memcpy(tab + off[k].upd, st.upd.data(), (size_t)st.A * sizeof(SchedUpd));
+      memcpy(tab + off[k].g, st.gdec.data(), (size_t)st.A * 4);
+    }
+    // (sized for 64 KiB at least: schedules of a few KB never move it)
+    unsigned* dtab = sched_tab.get<unsigned>(std::max<size_t>(words, 16 * 1024));
+    ZV_CHECK(hipMemcpyAsync(dtab, tab, words * 4, hipMemcpyHostToDevice, s));
+    sl.issued += 1;
+    hipLaunchKernelGGL(zv_mark_kernel, dim3(1), dim3(1), 0, s, sl.mark_dev, sl.issued);
+    ZV_LAUNCH_CHECK();
+    sched_rows_run = 0;
+    sched_steps_run = 0;
+    for (int k = 0; k < plan.K; ++k) {
+      const SchedStep& st = plan.steps[k];
+      const int N = st.U + st.A;
+      const int* map = reinterpret_cast<const int*>(dtab + off[k].map);
+      Act xin = ws_dec.xin.get((long)N * T, round_up(Fin, 64), split);
+      launch_build_input_map(x, tc, sc, xin.h, xin.l, xin.ld, map, N, T, Fx, Ft, Fx, s);
+      const uint8_t* padN = pad;
+      if (pad && !(st.U == 0 && st.A == B)) {     // (no copy and every row active: the batch is the input)
+        uint8_t* p2 = ws_dec.mask2.get<uint8_t>((size_t)N * T);
+        launch_gather_u8(pad, p2, map, N, T, s);
+        padN = p2;
+      }
+      float* v = ws_dec.vout.get<float>((size_t)N * T * Fx);
+      const float* tv = reinterpret_cast<const float*>(dtab + off[k].t);
+      // distill: the conditional rows are the whole batch (U = 0), so the active-order scales are its g
+      const float* gv = distill() ? reinterpret_cast<const float*>(dtab + off[k].g) : nullptr;
+      decoder(xin, Fin, N, T, padN, tv, gv, v, k > 0, s);
+      launch_euler_update_sched(x, v, reinterpret_cast<const SchedUpd*>(dtab + off[k].upd), st.A, (long)T * Fx, s);
+      sched_rows_run += N;
+      sched_steps_run += 1;
+    }
+  }
+
   void text_encode(const int64_t* tok, const uint8_t* pad, const int8_t* spk, int B, int S,
                    float* out, hipStream_t s) {
     const long n = (long)B * S;
@@ -1500,7 +1596,7 @@ int64_t zv_device_bytes(zv_handle h) {
   if (!h) return 0;
   return (int64_t)(h->store.weight_bytes + h->ws_dec.bytes() + h->ws_split[0].bytes() + h->ws_split[1].bytes() +
                    h->ws_split[2].bytes() + h->ws_txt.bytes() + h->gx.bytes +
-                   h->gtc.bytes + h->gsc.bytes + h->gpad.bytes + h->ggrows.bytes);
+                   h->gtc.bytes + h->gsc.bytes + h->gpad.bytes + h->ggrows.bytes + h->sched_tab.bytes);
 }
 
 int zv_fm_decoder(zv_handle h, const float* t, const float* guidance, const float* xt,
@@ -1574,6 +1670,27 @@ int zv_euler_sample_rows(zv_handle h, float* x, const float* text_c, const float
   const bool on = any_nonzero_rows(guidance_rows, B, s);
   h->euler_sample(x, text_c, speech_c, pad, B, T, num_step, 0.f, guidance_rows, on, t_start,
                   t_end, t_shift, s);
+  ZV_API_END
+}
+
+static_assert(sizeof(zv_row_sched) == sizeof(SchedRow), "SchedRow mirrors zv_row_sched");
+
+int zv_euler_sample_sched(zv_handle h, float* x, const float* text_c, const float* speech_c,
+                          const uint8_t* pad, int B, int T, const zv_row_sched* rows, void* stream) {
+  ZV_API_BEGIN
+  check_ready(h);
+  ZV_REQUIRE(B > 0 && T > 0, "empty batch");
+  ZV_REQUIRE(x && text_c && speech_c && rows, "zv_euler_sample_sched: null argument");
+  h->euler_sample_sched(x, text_c, speech_c, pad, B, T, reinterpret_cast<const SchedRow*>(rows),
+                        (hipStream_t)stream);
+  ZV_API_END
+}
+
+int zv_sched_stats(zv_handle h, int64_t* out) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(h != nullptr && out != nullptr, "zv_sched_stats: null argument");
+  out[0] = h->sched_rows_run;
+  out[1] = h->sched_steps_run;
   ZV_API_END
 }
 

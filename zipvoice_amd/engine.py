@@ -125,6 +125,44 @@ class ZvSolveCheckArgs(ctypes.Structure):
         ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
 
 
+class ZvRowSched(ctypes.Structure):
+    """zv_row_sched: one row of a scheduled solve (zv_euler_sample_sched, zv_sched_plan)."""
+    _fields_ = [("num_step", ctypes.c_int32), ("t_start", ctypes.c_float), ("t_end", ctypes.c_float),
+                ("t_shift", ctypes.c_float), ("guidance_scale", ctypes.c_float)]
+
+
+class ZvSchedPlanOut(ctypes.Structure):
+    """zv_sched_plan_out (tests/test_sched_plan.py)."""
+    _fields_ = [("steps", ctypes.c_int32), ("active", ctypes.c_int32), ("copies", ctypes.c_int32),
+                ("total_rows", ctypes.c_int64)] + [
+        (n, ctypes.c_void_p) for n in ("dec_src", "dec_zero_text", "dec_zero_speech", "dec_t", "act_row", "act_dt",
+                                       "act_scale", "act_cond", "act_uncond")]
+
+
+class ZvSchedCheckArgs(ctypes.Structure):
+    """zv_sched_check_args (test infrastructure; tests/test_gpu_sched_ref.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kind", "guard", "B", "T", "N", "A", "Fx", "Ft", "Fs")] + [
+        ("ld", ctypes.c_int64), ("per_row", ctypes.c_int64)] + [
+        (n, ctypes.c_void_p) for n in ("src", "zero_text", "zero_speech", "x", "tc", "sc", "mask", "v", "row", "dt",
+                                       "scale", "cond", "uncond", "out", "oh", "ol", "mout")] + [
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+
+
+def row_schedule_array(schedule):
+    """A sequence of rows with num_step / t_start / t_end / t_shift / guidance_scale attributes (or
+    5-tuples in that order) as a ctypes array of zv_row_sched."""
+    arr = (ZvRowSched * len(schedule))()
+    for i, r in enumerate(schedule):
+        if isinstance(r, (tuple, list)):
+            n, t0, t1, sh, g = r
+        else:
+            n, t0, t1, sh, g = r.num_step, r.t_start, r.t_end, r.t_shift, r.guidance_scale
+        if int(n) != n:
+            raise ValueError(f"schedule row {i}: num_step must be an integer, got {n!r}")
+        arr[i] = ZvRowSched(int(n), float(t0), float(t1), float(sh), float(g))
+    return arr
+
+
 class ZvNoiseCheckArgs(ctypes.Structure):
     """zv_noise_check_args (test infrastructure; tests/test_noise_spec.py, tests/test_gpu_noise.py)."""
     _fields_ = [("mode", ctypes.c_int), ("where", ctypes.c_int),
@@ -169,6 +207,10 @@ SIGNATURES = {
     "zv_euler_sample": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _P]),
     "zv_velocity_rows": (_I, [_P, _F, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "zv_euler_sample_rows": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _F, _F, _F, _P]),
+    "zv_euler_sample_sched": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    "zv_sched_stats": (_I, [_P, _P]),
+    "zv_sched_plan": (_I, [_P, _I, _I, _I, ctypes.POINTER(ZvSchedPlanOut)]),
+    "zv_sched_check": (_I, [ctypes.POINTER(ZvSchedCheckArgs)]),
     "zv_text_encode": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "zv_text_condition": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P]),
     "zv_speech_condition": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
@@ -453,6 +495,32 @@ class HipEngine:
                                             float(t_start), float(t_end), float(t_shift),
                                             _stream()))
         return x
+
+    def euler_sample_sched(self, x0, text_c, speech_c, padding_mask, schedule) -> torch.Tensor:
+        """One solve over rows with their own step counts, grids and guidance scales
+        (zv_euler_sample_sched): ``schedule`` holds one row per batch row (solver.RowSchedule, or
+        (num_step, t_start, t_end, t_shift, guidance_scale) tuples).  Queued on the current stream;
+        the schedule is read on the host before the call returns."""
+        B, T, Fx = x0.shape
+        if len(schedule) != B:
+            raise ValueError(f"schedule: expected {B} rows, got {len(schedule)}")
+        x = self._f32(x0, "x").clone()
+        text_c = self._f32(text_c, "text_condition", (B, T, self.cfg.feat_dim))
+        speech_c = self._f32(speech_c, "speech_condition", (B, T, Fx))
+        pm = self._mask(padding_mask, (B, T))
+        rows = row_schedule_array(schedule)
+        rc = self.lib.zv_euler_sample_sched(self.h, _ptr(x), _ptr(text_c), _ptr(speech_c), _ptr(pm), B, T,
+                                            ctypes.cast(rows, ctypes.c_void_p), _stream())
+        if rc != 0 and "scheduled solve:" in self.lib.zv_last_error().decode():
+            raise ValueError(self.lib.zv_last_error().decode())
+        self._check(rc)
+        return x
+
+    def sched_stats(self) -> tuple:
+        """(decoder rows launched, steps run) of this engine's last scheduled solve (zv_sched_stats)."""
+        c = (ctypes.c_int64 * 2)()
+        self._check(self.lib.zv_sched_stats(self.h, ctypes.cast(c, ctypes.c_void_p)))
+        return int(c[0]), int(c[1])
 
     def reserve(self, max_batch: int, max_frames: int) -> None:
         """Pre-size the decoder workspace (zv_reserve)."""

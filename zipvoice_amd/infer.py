@@ -21,6 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .models import per_row_schedule
 from .noise import check_keys
 
 
@@ -208,6 +209,10 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
     initial noise to the item (``noise.seeded_normal``, stream 0): item i then starts from the
     noise ``generate_sentence(seed=seeds[i])`` starts from, whatever it is batched with.
 
+    ``num_step``, ``guidance_scale``, ``speed`` and ``t_shift`` each also take a sequence of one
+    value per item (a ValueError at any other length): the pool then runs as one scheduled solve
+    (``ZipVoice.sample``), every item integrated with its own settings.
+
     ``remove_long_sil`` (upstream ZipVoice's ``--remove-long-sil``; mono and one-channel
     Dialog models, stereo is out of scope): every decoded row goes through
     ``longform.WavJoiner.trim`` (``joiner``, default ``WavJoiner()``), which drops the
@@ -220,6 +225,8 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
         if x0 is not None:
             raise ValueError("give x0 or seeds, not both")
         seeds, _ = check_keys(seeds, None, B)
+    # (per-item settings are checked for their length here, before any GPU work)
+    per_row_schedule(B, num_step=num_step, t_shift=t_shift, guidance_scale=guidance_scale, speed=speed)
     feats, nfr, rms, _ = _prepare_prompts(items, feature_extractor, target_rms, dev)
     prompt_features = (feats + feat_bias) * feat_scale
     if remove_long_sil:

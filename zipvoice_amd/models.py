@@ -26,7 +26,7 @@ from .common import make_pad_mask, pad_labels, predict_features_lens, speaker_tu
 from .config import ModelConfig
 from .engine import HipEngine
 from .noise import check_keys, seeded_normal
-from .solver import DistillEulerSolver, EulerSolver
+from .solver import DistillEulerSolver, EulerSolver, RowSchedule
 from .weights import check_state_dict, load_checkpoint_state_dict, synthetic_state_dict
 
 
@@ -200,7 +200,12 @@ class ZipVoice:
         ``seed_streams`` one int in [0, 2^32) per row, default 0) draws row b with
         ``noise.seeded_normal`` from (seeds[b], seed_streams[b]), so a row's noise does not
         depend on what it is batched with; otherwise the noise is drawn with torch.randn on
-        the device as the reference does (:453-458)."""
+        the device as the reference does (:453-458).
+
+        ``num_step``, ``t_shift``, ``guidance_scale`` and ``speed`` (extra) each also take a
+        sequence of one value per row: the batch then runs as one scheduled solve
+        (``solver.sample_rows``), every row with its own settings.  Scalars, and the
+        reference's (batch, 1, 1) guidance tensor, take the unscheduled path."""
         if seeds is not None and x0 is not None:
             raise ValueError("give x0 or seeds, not both")
         if seed_streams is not None and seeds is None:
@@ -208,6 +213,13 @@ class ZipVoice:
         if seeds is not None:
             seeds, seed_streams = check_keys(seeds, seed_streams, len(tokens))
         eng = self._need_engine()
+        # per-request settings: a sequence of one value per row for any of these four sends the
+        # batch through the scheduled solve (solver.sample_rows), the others broadcast
+        schedule = per_row_schedule(len(tokens), num_step=num_step, t_shift=t_shift,
+                                    guidance_scale=guidance_scale, speed=speed)
+        if schedule is not None:
+            schedule, speed = schedule
+            speed = torch.tensor(speed, dtype=torch.float32, device=self.device)
         assert duration in ["real", "predict"]
         prompt_features_lens = prompt_features_lens.to(self.device)
         if duration == "predict":
@@ -235,11 +247,43 @@ class ZipVoice:
         x1_wo_prompt_lens = (~padding_mask).sum(-1) - prompt_features_lens
         Tg, Tp = (int(v) for v in torch.stack([x1_wo_prompt_lens.max(),
                                                 prompt_features_lens.max()]).tolist())
-        x1 = self.solver.sample(x=x0, text_condition=text_condition,
-                                speech_condition=speech_condition, padding_mask=padding_mask,
-                                num_step=num_step, guidance_scale=guidance_scale, t_shift=t_shift)
+        if schedule is not None:
+            x1 = self.solver.sample_rows(x=x0, text_condition=text_condition,
+                                         speech_condition=speech_condition,
+                                         padding_mask=padding_mask, schedule=schedule)
+        else:
+            x1 = self.solver.sample(x=x0, text_condition=text_condition,
+                                    speech_condition=speech_condition, padding_mask=padding_mask,
+                                    num_step=num_step, guidance_scale=guidance_scale,
+                                    t_shift=t_shift)
         return split_prompt(x1, prompt_features_lens, x1_wo_prompt_lens, Tg, Tp) + (
             prompt_features_lens,)
+
+
+def per_row_schedule(B: int, **settings):
+    """``sample``'s num_step / t_shift / guidance_scale / speed, each a scalar or a sequence of B
+    values.  None when all are scalars (or the reference's (B, 1, 1) guidance tensor: the
+    unscheduled path); else (one solver.RowSchedule per row, the B speeds) with the scalars
+    broadcast.  A sequence of another length is a ValueError."""
+    def is_seq(v):
+        return isinstance(v, (list, tuple)) or (isinstance(v, np.ndarray) and v.ndim == 1)
+    if not any(is_seq(v) for v in settings.values()):
+        return None
+    cols = {}
+    for name, v in settings.items():
+        if is_seq(v):
+            if len(v) != B:
+                raise ValueError(f"{name}: expected one value per row ({B}), got {len(v)}")
+            cols[name] = list(v)
+        elif torch.is_tensor(v) and v.numel() > 1:
+            if v.numel() != B:
+                raise ValueError(f"{name}: expected 1 or {B} values, got shape {tuple(v.shape)}")
+            cols[name] = v.reshape(B).tolist()
+        else:
+            cols[name] = [float(v) if name != "num_step" else v] * B
+    rows = [RowSchedule(num_step=int(n), guidance_scale=float(g), t_shift=float(s))
+            for n, g, s in zip(cols["num_step"], cols["guidance_scale"], cols["t_shift"])]
+    return rows, [float(s) for s in cols["speed"]]
 
 
 def split_prompt(x1: torch.Tensor, prompt_lens: torch.Tensor, gen_lens: torch.Tensor,

@@ -5,7 +5,8 @@ doubling, guidance combine and the Euler update) running inside the HIP engine
 (``zv_euler_sample``): no host synchronisation between steps."""
 from __future__ import annotations
 
-from typing import Union
+from dataclasses import dataclass
+from typing import Sequence, Union
 
 import torch
 
@@ -17,10 +18,31 @@ def get_time_steps(t_start: float = 0.0, t_end: float = 1.0, num_step: int = 10,
     return t_shift * ts / (1 + (t_shift - 1) * ts)
 
 
+@dataclass(frozen=True)
+class RowSchedule:
+    """One row's solver settings in a scheduled solve (``EulerSolver.sample_rows``): the arguments
+    ``EulerSolver.sample`` takes for a whole batch, per row."""
+    num_step: int
+    guidance_scale: float = 0.0
+    t_start: float = 0.0
+    t_end: float = 1.0
+    t_shift: float = 1.0
+
+
 class EulerSolver:
     def __init__(self, model, func_name: str = "forward_fm_decoder"):
         self.model = model
         self.func_name = func_name
+
+    def sample_rows(self, x: torch.Tensor, text_condition: torch.Tensor,
+                    speech_condition: torch.Tensor, padding_mask: torch.Tensor,
+                    schedule: Sequence[RowSchedule]) -> torch.Tensor:
+        """Row b integrated as ``sample`` would integrate it alone with ``schedule[b]``'s settings,
+        all rows in one call (``zv_euler_sample_sched``): a row leaves the decoder batch when its
+        steps are done, and a row with guidance scale 0 has no unconditional copy.  The reference
+        has no counterpart (its solver takes one setting per call)."""
+        return self.model.engine.euler_sample_sched(x, text_condition, speech_condition, padding_mask,
+                                                    list(schedule))
 
     def sample(self, x: torch.Tensor, text_condition: torch.Tensor,
                speech_condition: torch.Tensor, padding_mask: torch.Tensor, num_step: int = 10,
