@@ -159,6 +159,12 @@ int zv_attn2_check(int kernel, int form, int B, int L, int H, int nv, const floa
  * SwooshL -> bf16 (a plain linear's). */
 int zv_bench_gemm(int M, int N, int K, int variant, int iters, int out_mode, float* ms_out);
 
+/* Microbenchmark of the NonlinAttention in-projection (form ZV_LIN_NA = 7, N % 48 == 0) or the
+ * SelfAttention value projection (ZV_LIN_TRANS = 6) alone: average ms per launch of the 16-bit
+ * product through the engine's launch choice (ZV_TRANS_ALIGNED as the engine reads it), random
+ * operands, M rows in utterances of rpb rows, V^T rows of rpb rounded up to 64 frames. */
+int zv_bench_fused_linear(int form, int M, int N, int K, int rpb, int iters, float* ms_out);
+
 /* GEMM self-check (test infrastructure): variant 70 / 71 / 72 = the counted residual / residual +
  * bypass / plain epilogue of the 128x128 kernel (any other value is rejected) against its general
  * epilogue on the same random operands; mode 0 plain, 1 SwooshL (variant 72), 2 residual (70 / 71).
@@ -175,7 +181,8 @@ int zv_gemm_selftest(int M, int N, int K, int variant, int mode, float* maxdiff,
  * zero beyond K.  split: 1 = 16-bit product, 3 = hi/lo split products of both operands, 2 = the
  * weight-split product (ZV_LIN_PLAIN without activation, and ZV_LIN_TRANS).  The launch is the one
  * the engine would make for that shape and form, not a chosen instantiation; `launch` receives which
- * one it was: {BM, BN, SPLIT, EPI, ROLE, 256x256 kernel, grid blocks, STAGES * 16 + OCC}.
+ * one it was: {BM, BN, SPLIT, EPI, ROLE, 256x256 kernel, grid blocks, STAGES * 16 + OCC (+ 256 when
+ * the TRANS / NA launch ran utterance-aligned tiles: B * ceil(rpb / BM) * ceil(N / BN) of them)}.
  *
  * Outputs keep their padding: the caller passes every output buffer it wants with guard rows before
  * row 0 and after the last row and a row stride larger than the width (ldc % 4 == 0, ldch % 8 == 0),

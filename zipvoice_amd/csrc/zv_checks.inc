@@ -1,5 +1,5 @@
-// Test-infrastructure and microbenchmark entry points of the C ABI: zv_bench_gemm, zv_gemm_selftest,
-// zv_attn_plan, zv_attn2_check, zv_mx8_quantize, zv_mx8_gemm_check, zv_linear_check, zv_ffn_check,
+// Test-infrastructure and microbenchmark entry points of the C ABI: zv_bench_gemm, zv_bench_fused_linear,
+// zv_gemm_selftest, zv_attn_plan, zv_attn2_check, zv_mx8_quantize, zv_mx8_gemm_check, zv_linear_check, zv_ffn_check,
 // zv_dwconv_check, zv_stackedge_check, zv_bigvgan_check, zv_solve_check (and the host-only zv_time_steps,
 // zv_cfg_plan).
 // None of them builds an engine: each runs one launch (or a timed loop of one launch) of a kernel the
@@ -176,6 +176,46 @@ int zv_bench_gemm(int M, int N, int K, int variant, int iters, int out_mode, flo
     default:                                                               // 70: counted residual epilogue
       *ms_out = out_mode == 5 ? bench_variant<1>(p, iters, persistent, s) : bench_variant<2>(p, iters, persistent, s);
   }
+  ZV_API_END
+}
+
+// The NonlinAttention in-projection (ZV_LIN_NA) or the value projection (ZV_LIN_TRANS) alone, 16-bit
+// product, through LinearPolicy's launch choice (ZV_TRANS_ALIGNED read as the engine reads it), on
+// random operands in the engine's layout: utterances of rpb rows, V^T rows of round_up(rpb, 64) frames
+int zv_bench_fused_linear(int form, int M, int N, int K, int rpb, int iters, float* ms_out) {
+  ZV_API_BEGIN
+  ZV_REQUIRE((form == ZV_LIN_NA || form == ZV_LIN_TRANS) && M > 0 && N > 0 && K > 0 && rpb > 0 && iters > 0 &&
+                 ms_out && (form != ZV_LIN_NA || N % 48 == 0),
+             "zv_bench_fused_linear: form NA (N % 48 == 0) or TRANS, positive sizes");
+  ChkDev dev;
+  hipStream_t s = nullptr;
+  const long Kp = round_up(K, 64), Np = round_up(N, 128), Lpad = round_up(rpb, 64);
+  const int rows_t = form == ZV_LIN_NA ? N / 3 : N, nutt = cdiv(M, rpb);
+  bf16* A = dev.make<bf16>((size_t)M * Kp);
+  bf16* W = dev.make<bf16>((size_t)Np * Kp);
+  hipLaunchKernelGGL(zv_fill_rand_bf16, dim3(4096), dim3(256), 0, s, A, (long)M * Kp, 1u);
+  hipLaunchKernelGGL(zv_fill_rand_bf16, dim3(4096), dim3(256), 0, s, W, (long)Np * Kp, 2u);
+  GemmParams p{};
+  p.M = M; p.N = N; p.K = K; p.nz2 = 1; p.Brows = (int)Np;
+  p.Ah = A; p.lda = Kp; p.Bh = W; p.ldb = Kp;
+  p.bias = dev.zero<float>((size_t)N); p.rows_per_group = 1;
+  p.Cth = dev.zero<bf16>((size_t)nutt * rows_t * Lpad);
+  p.ldct = Lpad; p.rpb = rpb; p.sCt = (long)rows_t * Lpad;
+  if (form == ZV_LIN_NA) { p.ldch = round_up(rows_t, 8); p.Ch = dev.make<bf16>((size_t)M * p.ldch); }
+  LinearPolicy policy;
+  auto launch = [&]() {
+    if (form == ZV_LIN_NA) policy.launch_na_in<1>(p, s);
+    else policy.launch_value_t<1>(p, false, false, s);
+  };
+  ChkEvent e0, e1;
+  launch();
+  ZV_CHECK(hipEventRecord(e0.e, s));
+  for (int i = 0; i < iters; ++i) launch();
+  ZV_CHECK(hipEventRecord(e1.e, s));
+  ZV_CHECK(ZV_BLOCKING(hipEventSynchronize(e1.e)));
+  float ms = 0.f;
+  ZV_CHECK(hipEventElapsedTime(&ms, e0.e, e1.e));
+  *ms_out = ms / iters;
   ZV_API_END
 }
 

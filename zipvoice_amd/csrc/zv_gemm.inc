@@ -774,9 +774,95 @@ __device__ __forceinline__ void gemm_epilogue_glu_c(const GemmParams& p, f32x4 (
   });
 }
 
-template <int TM, int TN, int NS>
+// Utterance-aligned transposed stores (UTT tiling, zv_gemm_kernel: a wave's first row is frame l0,
+// a multiple of 32, of utterance ub; no tile crosses an utterance).  The accumulator gives a lane
+// (column lane & 15, rg = lane >> 4) rows 4 rg .. 4 rg + 3 of a strip: four consecutive frames of
+// one row of the transposed output.  The lane rounds them in registers and packs them into two
+// dwords; one v_permlane16_swap per dword against the next strip's (the pairing of zv_gemm256.inc's
+// direct epilogues) leaves it the 8 consecutive frames that start utt_fofs = {0, 16, 8, 24} past
+// the strip pair's first, written with one aligned 16-B store: no LDS round trip, no (utterance,
+// frame) walk, one address per store.  Frames at or past the utterance's length are never written
+// ([L, ldct) of V^T stays the workspace's zeros, which the attention kernels multiply by P = 0):
+// the one group per row that straddles L stores its frames singly, a group wholly outside (or of a
+// column >= N) goes to the sink.
+__device__ __forceinline__ int utt_fofs(int lane) {
+  const int g = lane >> 4;
+  return ((g & 1) << 4) | ((g >> 1) << 3);
+}
+// a lane's four values of one strip, rounded as split_store rounds them, as two packed dwords
+template <int NS>
+__device__ __forceinline__ void pack_trans4(const float (&v)[4], unsigned (&wh)[2], unsigned (&wl)[2]) {
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const bf16x2 h = {(bf16)v[2 * r], (bf16)v[2 * r + 1]};
+    wh[r] = __builtin_bit_cast(unsigned, h);
+    if constexpr (NS == 2) {
+      const bf16x2 l = {(bf16)(v[2 * r] - (float)h[0]), (bf16)(v[2 * r + 1] - (float)h[1])};
+      wl[r] = __builtin_bit_cast(unsigned, l);
+    }
+  }
+}
+// {(bf16)(x0 * t0), (bf16)(x1 * t1)} as one dword, as the row-tile NA epilogue rounds the product.
+// In the fp16-operand build hipcc compiles that epilogue's (bf16)__fmul_rn(x, t) to one
+// v_fma_mixlo_f16, whose fp16 result is not always the fp32 product's rounding (about one element
+// in 4,000 differed from a v_pk_mul_f32 + v_cvt_pk_f16_f32 pair on Gaussian operands,
+// tests/test_gpu_trans_aligned.py), and the vectoriser makes that pair of two adjacent products;
+// so the instruction is spelled out here (lo then hi half of the dword; s_nop: the swap that reads
+// the dword next needs two wait states after a VALU write, and hipcc does not look into the asm)
+__device__ __forceinline__ unsigned mul_pack16(float x0, float t0, float x1, float t1) {
+#ifdef ZV_OPERAND_F16
+  unsigned w;
+  asm("v_fma_mixlo_f16 %0, %1, %2, 0\n\tv_fma_mixhi_f16 %0, %3, %4, 0\n\ts_nop 1"
+      : "=&v"(w) : "v"(x0), "v"(t0), "v"(x1), "v"(t1));
+  return w;
+#else
+  const bf16x2 h = {(bf16)__fmul_rn(x0, t0), (bf16)__fmul_rn(x1, t1)};
+  return __builtin_bit_cast(unsigned, h);
+#endif
+}
+// wh / wl [s]: the packed hi / lo dwords of the lane's four frames of strips i + s (i even);
+// o: offset of the lane's 8-frame group in Cth / Ctl; nl: how many of its frames lie inside the
+// utterance (<= 0: none)
+template <int NS>
+__device__ __forceinline__ void store_trans8(const GemmParams& p, const unsigned (&wh)[2][2],
+                                             const unsigned (&wl)[2][2], long o, int nl, bool col_ok, int lane) {
+  typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+  u32x4_t uh, ul;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const auto sw = __builtin_amdgcn_permlane16_swap(wh[0][r], wh[1][r], false, false);
+    uh[r] = sw[0];
+    uh[2 + r] = sw[1];
+    if constexpr (NS == 2) {
+      const auto sl = __builtin_amdgcn_permlane16_swap(wl[0][r], wl[1][r], false, false);
+      ul[r] = sl[0];
+      ul[2 + r] = sl[1];
+    }
+  }
+  const bool full = col_ok && nl >= 8;
+  unsigned long long ha = full ? (unsigned long long)(p.Cth + o) : (unsigned long long)(p.sink + 512 + lane * 4);
+  asm volatile("" : "+v"(ha));
+  *(GLOBAL u32x4_t*)(ha) = uh;
+  if constexpr (NS == 2) {
+    unsigned long long la = full ? (unsigned long long)(p.Ctl + o) : (unsigned long long)(p.sink + 1024 + lane * 4);
+    asm volatile("" : "+v"(la));
+    *(GLOBAL u32x4_t*)(la) = ul;
+  }
+  if (col_ok && nl > 0 && nl < 8) {   // the group that straddles the utterance's end
+    uint16_t* th = reinterpret_cast<uint16_t*>(p.Cth) + o;
+    uint16_t* tl = NS == 2 ? reinterpret_cast<uint16_t*>(p.Ctl) + o : nullptr;
+#pragma unroll
+    for (int e = 0; e < 7; ++e)
+      if (e < nl) {
+        th[e] = (uint16_t)(uh[e >> 1] >> (16 * (e & 1)));
+        if constexpr (NS == 2) tl[e] = (uint16_t)(ul[e >> 1] >> (16 * (e & 1)));
+      }
+  }
+}
+
+template <int TM, int TN, int NS, bool UTT = false>
 __device__ __forceinline__ void gemm_epilogue_na_c(const GemmParams& p, f32x4 (&acc)[TM][TN],
-                                                   int m0, int n0, int lane, float* scr) {
+                                                   int m0, int n0, int ub, int l0, int lane, float* scr) {
   constexpr int LDW = EpiScratch<TN>::LDW;
   static_assert(TN == 3, "one 48-column [s16 | x16 | y16] group per wave");
   const int nbc = min(n0, p.N - 48);
@@ -788,6 +874,52 @@ __device__ __forceinline__ void gemm_epilogue_na_c(const GemmParams& p, f32x4 (&
   // x * tanh(s) (transposed): lane -> channel ch, rows 4 rg .. 4 rg + 3 of the strip
   const int ch = lane & 15, rg = lane >> 4;
   const float bs_ = p.bias[nbc + ch], bx = p.bias[nbc + 16 + ch];
+  if constexpr (UTT) {
+    static_assert(TM % 2 == 0, "aligned transposed stores pair the strips");
+    static_assert(NS == 1, "the counted NA epilogue runs the 16-bit product only (launch_na_in)");
+    // x * tanh(s) from the accumulators, 8 frames per lane (store_trans8)
+    const long orow = (long)ub * p.sCt + (long)(cbase16 + ch) * p.ldct;
+    static_for<TM / 2>([&](auto I_) {
+      constexpr int i = 2 * decltype(I_)::value;
+      unsigned wh[2][2], wl[2][2];
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        float xv[4], tv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          tv[r] = tanh_fast(acc[i + s][0][r] + bs_);
+          xv[r] = acc[i + s][1][r] + bx;
+        }
+        wh[s][0] = mul_pack16(xv[0], tv[0], xv[1], tv[1]);
+        wh[s][1] = mul_pack16(xv[2], tv[2], xv[3], tv[3]);
+      }
+      const int l = l0 + i * 16 + utt_fofs(lane);
+      store_trans8<NS>(p, wh, wl, orow + l, p.rpb - l, col_ok, lane);
+    });
+    // y keeps its staged form (only its 16 columns go through the strip); rows of the tile past
+    // the utterance's end belong to the next utterance's tiles
+    static_for<TM>([&](auto I_) {
+      constexpr int i = decltype(I_)::value;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) scr[(rg * 4 + r) * LDW + 32 + ch] = acc[i][2][r];
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+      __builtin_amdgcn_wave_barrier();
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = scr[yrow * LDW + 32 + c4 + e] + by[e];
+      bf16x4 h;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) h[e] = (bf16)v[e];
+      const bool ok = col_ok && l0 + i * 16 + yrow < p.rpb;
+      const long o = (long)(m0 + i * 16 + yrow) * p.ldch + cbase16 + c4;
+      unsigned long long ha = ok ? (unsigned long long)(p.Ch + o) : (unsigned long long)(p.sink + 512 + lane * 4);
+      asm volatile("" : "+v"(ha));
+      *(GLOBAL bf16x4*)(ha) = h;
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+    });
+    return;
+  }
   // (utterance, frame) of the lane's first transposed row; strips advance it by 16
   int bb = (m0 + rg * 4) / p.rpb, lf = (m0 + rg * 4) % p.rpb;
   static_for<TM>([&](auto I_) {
@@ -847,11 +979,37 @@ __device__ __forceinline__ void gemm_epilogue_na_c(const GemmParams& p, f32x4 (&
   });
 }
 
-template <int TM, int TN, int NS>
+template <int TM, int TN, int NS, bool UTT = false>
 __device__ __forceinline__ void gemm_epilogue_trans_c(const GemmParams& p, f32x4 (&acc)[TM][TN],
-                                                      int m0, int n0, int lane, float* scr) {
+                                                      int m0, int n0, int ub, int l0, int lane, float* scr) {
   constexpr int WN = EpiScratch<TN>::W, LDW = EpiScratch<TN>::LDW;
   constexpr int Q = (16 * WN) / (64 * 4);
+  if constexpr (UTT) {
+    static_assert(TM % 2 == 0, "aligned transposed stores pair the strips");
+    // from the accumulators, 8 frames of one output row per lane and store (store_trans8)
+    const int lf = l0 + utt_fofs(lane);
+    static_for<TN>([&](auto J_) {
+      constexpr int j = decltype(J_)::value;
+      const int n = n0 + j * 16 + (lane & 15);
+      const bool col_ok = n < p.N;
+      const float bn = p.bias ? p.bias[min(n, p.N - 1)] : 0.f;
+      const long orow = (long)ub * p.sCt + (long)n * p.ldct;
+      static_for<TM / 2>([&](auto I_) {
+        constexpr int i = 2 * decltype(I_)::value;
+        unsigned wh[2][2], wl[2][2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          float v[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = acc[i + s][j][r] + bn;
+          pack_trans4<NS>(v, wh[s], wl[s]);
+        }
+        const int l = lf + i * 16;
+        store_trans8<NS>(p, wh, wl, orow + l, p.rpb - l, col_ok, lane);
+      });
+    });
+    return;
+  }
   static_assert(64 % WN == 0 && Q >= 1, "a lane's column is fixed across strips");
   const int col = lane % WN, rg0 = lane / WN;     // q adds 64 / WN row groups
   const int n = n0 + col;
@@ -923,7 +1081,7 @@ __device__ __forceinline__ void gemm_epilogue_trans_c(const GemmParams& p, f32x4
 #endif
 template <int BM, int BN, int WGM, int WGN, int SPLIT, int EPI, int STAGES = 2, int OCC = 2,
           int BK = GEMM_BK, int RP = 0, int CONV = 0, int ROLE = 0,
-          int PRELOAD = ZV_GEMM_PRELOAD, int MXO = 0>
+          int PRELOAD = ZV_GEMM_PRELOAD, int MXO = 0, int UTT = 0>
 __global__ __launch_bounds__(64 * WGM * WGN, OCC) void zv_gemm_kernel(GemmParams p) {
   constexpr int NW = WGM * WGN;
   constexpr int WM = BM / WGM, WN = BN / WGN;
@@ -963,8 +1121,28 @@ __global__ __launch_bounds__(64 * WGM * WGN, OCC) void zv_gemm_kernel(GemmParams
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm0 = (wave / WGN) * WM, wn0 = (wave % WGN) * WN;
-  const int ntn = (p.N + BN - 1) / BN, ntm = (p.M + BM - 1) / BM;
+  static_assert(!UTT || (ROLE == 3 && (EPI == EPI_NA || EPI == EPI_TRANS) && !SWZ),
+                "utterance-aligned tiles: the counted NA / transposed epilogues");
+  // UTT: utterance-aligned M tiles.  M tile tm covers rows b * rpb + j * BM .. of utterance
+  // b = tm / tpu, j = tm % tpu (tpu = cdiv(rpb, BM) tiles per utterance): no tile crosses an
+  // utterance and a tile's first frame is a multiple of BM; the rows of an utterance's last tile
+  // past its end are loaded (clamped to M - 1 as everywhere) and never stored
+  const int tpu = UTT ? (p.rpb + BM - 1) / BM : 1;
+  const int ntn = (p.N + BN - 1) / BN, ntm = UTT ? (p.M / p.rpb) * tpu : (p.M + BM - 1) / BM;
   const int ntiles = ntn * ntm;
+  // a tile's first row and column (UTT: and its utterance, and the first row's frame in it)
+  auto tile_origin = [&](int tile, int& m0, int& n0, int& ub, int& l0) {
+    const int tm = tile / ntn;
+    n0 = (tile - tm * ntn) * BN;
+    if constexpr (UTT) {
+      ub = tm / tpu;
+      l0 = (tm - ub * tpu) * BM;
+      m0 = ub * p.rpb + l0;
+    } else {
+      ub = 0; l0 = 0;
+      m0 = tm * BM;
+    }
+  };
   const int G = gridDim.x, Q = G >> 3;
   const int bslot = (blockIdx.x & 7) * Q + (blockIdx.x >> 3);
   const int my_tiles = (bslot < ntiles) ? (ntiles - 1 - bslot) / G + 1 : 0;
@@ -986,8 +1164,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, OCC) void zv_gemm_kernel(GemmParams
   unsigned offa[APW], offb[BPW], offs[SPW];
   const int prow = lane / CPRW, ppos = lane % CPRW;
   auto set_ld_tile = [&]() {
-    const int tile = ld_it * G + bslot;
-    const int ld_m0 = (tile / ntn) * BM, ld_n0 = (tile % ntn) * BN;
+    int ld_m0, ld_n0, ld_ub, ld_l0;
+    tile_origin(ld_it * G + bslot, ld_m0, ld_n0, ld_ub, ld_l0);
 #pragma unroll
     for (int i = 0; i < APW; ++i) {
       const int row = (wave + i * NW) * RPP + prow;
@@ -1181,8 +1359,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, OCC) void zv_gemm_kernel(GemmParams
       if (ld_step < total) issue();
       mma_step(smem + (step % STAGES) * STAGE, acc);
     }
-    const int tile = it * G + bslot;
-    const int m0 = (tile / ntn) * BM, n0 = (tile % ntn) * BN;
+    int m0, n0, ub, l0;
+    tile_origin(it * G + bslot, m0, n0, ub, l0);
     __builtin_amdgcn_s_barrier();          // every wave done reading the last stage
     float* scr = reinterpret_cast<float*>(smem + ((step - 1) % STAGES) * STAGE + wave * SCR);
     if constexpr (ROLE >= 1 && EPI == EPI_STD && !RP && !SWZ)
@@ -1191,9 +1369,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, OCC) void zv_gemm_kernel(GemmParams
     else if constexpr (ROLE == 3 && EPI == EPI_GLU && !SWZ)
       gemm_epilogue_glu_c<TM, TN, NS>(p, acc, m0 + wm0, n0 + wn0, lane, scr);
     else if constexpr (ROLE == 3 && EPI == EPI_NA && !SWZ)
-      gemm_epilogue_na_c<TM, TN, NS>(p, acc, m0 + wm0, n0 + wn0, lane, scr);
+      gemm_epilogue_na_c<TM, TN, NS, UTT != 0>(p, acc, m0 + wm0, n0 + wn0, ub, l0 + wm0, lane, scr);
     else if constexpr (ROLE == 3 && EPI == EPI_TRANS && !SWZ)
-      gemm_epilogue_trans_c<TM, TN, NS>(p, acc, m0 + wm0, n0 + wn0, lane, scr);
+      gemm_epilogue_trans_c<TM, TN, NS, UTT != 0>(p, acc, m0 + wm0, n0 + wn0, ub, l0 + wm0, lane, scr);
     else
       gemm_epilogue<TM, TN, EPI, SWZ, RP>(p, acc, m0 + wm0, n0 + wn0, z1, z2, lane, scr);
     // drain the epilogue's own loads/stores with a wait hipcc can see, so its
@@ -1325,12 +1503,20 @@ static double gemm_alg_bytes(const GemmParams& p, int nz) {
 // infrastructure: zv_linear_check / zv_ffn_check return it, so a test can tell which instantiation
 // the engine's dispatch chose for a shape).  Written by launch_gemm, launch_gemm256 and
 // launch_ffn_t; no kernel reads it.  ffn: EPI = RV | ORIG << 1 | COPY << 2 | TP << 3, ROLE = NORM,
-// aux = chunk steps per block (w); GEMMs: aux = STAGES * 16 + OCC (0 for the 256x256 kernel)
+// aux = chunk steps per block (w); GEMMs: aux = STAGES * 16 + OCC (+ 256: utterance-aligned tiles; 0 for
+// the 256x256 kernel)
 struct ZvLaunchRec { int BM, BN, SPLIT, EPI, ROLE, k256, grid, aux; };
 static thread_local ZvLaunchRec g_zv_last_launch = {};
 
+// The utterance-aligned tiling's (UTT) preconditions: whole utterances of rpb rows, and rows of
+// the transposed output that start 16-B aligned at every multiple of 8 frames
+static bool gemm_utt_ok(const GemmParams& p) {
+  return p.rpb > 0 && p.M % p.rpb == 0 && p.ldct >= p.rpb && p.ldct % 8 == 0 && p.sCt % 8 == 0 && p.Cth &&
+         (uintptr_t)p.Cth % 16 == 0 && (uintptr_t)p.Ctl % 16 == 0;
+}
+
 template <int BM, int BN, int WGM, int WGN, int SPLIT, int EPI, int STAGES = 2, int OCC = 2,
-          int BK = GEMM_BK, int RP = 0, int CONV = 0, int ROLE = 0, int MXO = 0>
+          int BK = GEMM_BK, int RP = 0, int CONV = 0, int ROLE = 0, int MXO = 0, int UTT = 0>
 static void launch_gemm(const GemmParams& p, int nz, hipStream_t s, const char* tag,
                         bool persistent = true, int gridx = 0) {
   constexpr int NS = (SPLIT == 3) ? 2 : 1;
@@ -1340,7 +1526,7 @@ static void launch_gemm(const GemmParams& p, int nz, hipStream_t s, const char* 
   static unsigned long long attr = 0;   // per device (hipFuncSetAttribute is per device)
   if (!((attr >> zv_cur_device()) & 1)) {
     ZV_CHECK(hipFuncSetAttribute(
-        (const void*)zv_gemm_kernel<BM, BN, WGM, WGN, SPLIT, EPI, STAGES, OCC, BK, RP, CONV, ROLE, ZV_GEMM_PRELOAD, MXO>,
+        (const void*)zv_gemm_kernel<BM, BN, WGM, WGN, SPLIT, EPI, STAGES, OCC, BK, RP, CONV, ROLE, ZV_GEMM_PRELOAD, MXO, UTT>,
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr |= 1ull << zv_cur_device();
   }
@@ -1364,7 +1550,9 @@ static void launch_gemm(const GemmParams& p, int nz, hipStream_t s, const char* 
   // the DMA pieces address A / B as a scalar base + 32-bit per-lane byte offset
   ZV_REQUIRE((long)p.M * p.lda * (MX ? 1 : 2) < (1L << 32) && (long)p.Brows * p.ldb * (MX ? 1 : 2) < (1L << 32),
              "GEMM operand larger than the 4 GiB DMA offset range");
-  const int tiles = cdiv(p.N, BN) * cdiv(p.M, BM);
+  if constexpr (UTT)
+    ZV_REQUIRE(gemm_utt_ok(p), "utterance-aligned tiles: whole utterances, 16-B aligned V^T rows");
+  const int tiles = cdiv(p.N, BN) * (UTT ? (p.M / p.rpb) * cdiv(p.rpb, BM) : cdiv(p.M, BM));
   // persistent grid: blocks resident per CU by LDS (and at most 2), across all z
   constexpr int NWB = WGM * WGN;
   const int bpc = std::max(1, std::min({2, (int)((160 * 1024) / lds), std::max(1, OCC * 4 / NWB)}));
@@ -1380,10 +1568,10 @@ static void launch_gemm(const GemmParams& p, int nz, hipStream_t s, const char* 
     snprintf(dtag, sizeof(dtag), "%s M=%d N=%d K=%d z=%d tile=%dx%d", tag, p.M, p.N, p.K, nz, BM, BN);
     tag = dtag;
   }
-  g_zv_last_launch = ZvLaunchRec{BM, BN, SPLIT, EPI, ROLE, 0, G, STAGES * 16 + OCC};
+  g_zv_last_launch = ZvLaunchRec{BM, BN, SPLIT, EPI, ROLE, 0, G, STAGES * 16 + OCC + 256 * UTT};
   const double bytes = gemm_alg_bytes<SPLIT, ROLE, MXO>(p, nz);
   ZvProfScope prof(tag, 2.0 * p.M * p.N * (double)p.K * nz, bytes, s);
-  hipLaunchKernelGGL((zv_gemm_kernel<BM, BN, WGM, WGN, SPLIT, EPI, STAGES, OCC, BK, RP, CONV, ROLE, ZV_GEMM_PRELOAD, MXO>), dim3(G, 1, nz),
+  hipLaunchKernelGGL((zv_gemm_kernel<BM, BN, WGM, WGN, SPLIT, EPI, STAGES, OCC, BK, RP, CONV, ROLE, ZV_GEMM_PRELOAD, MXO, UTT>), dim3(G, 1, nz),
                      dim3(64 * WGM * WGN), lds, s, pr);
   ZV_LAUNCH_CHECK();
 }

@@ -1,5 +1,5 @@
 // The linears' launch policy: which GEMM instantiation (tile, K-ring depth, blocks per CU,
-// epilogue) a linear of the Zipformer runs on.  LinearPolicy holds the two run-time knobs the
+// epilogue) a linear of the Zipformer runs on.  LinearPolicy holds the three run-time knobs the
 // choice reads; zv_engine derives from it, and zv_linear_check (test infrastructure) constructs it
 // alone.  tests/test_gpu_linear_ref.py predict() mirrors linear16 / attn_in_wsplit arm for arm.
 //
@@ -67,9 +67,15 @@ struct Out {              // epilogue of a linear
 
 // one linear's launch: 2 x 2 waves, one tile per block; the template parameters that vary
 template <int BM, int BN, int SPLIT, int EPI, int STAGES = 2, int OCC = 2, int ROLE = 0, int MXO = 0,
-          int BK = GEMM_BK>
+          int BK = GEMM_BK, int UTT = 0>
 void gemm_tile(const GemmParams& p, hipStream_t s, const char* tag) {
-  launch_gemm<BM, BN, 2, 2, SPLIT, EPI, STAGES, OCC, BK, 0, 0, ROLE, MXO>(p, 1, s, tag, true, -1);
+  launch_gemm<BM, BN, 2, 2, SPLIT, EPI, STAGES, OCC, BK, 0, 0, ROLE, MXO, UTT>(p, 1, s, tag, true, -1);
+}
+// the counted NA / transposed linears: utterance-aligned M tiles (zv_gemm.inc UTT) or row tiles
+template <int BM, int BN, int SPLIT, int EPI, int STAGES, int OCC>
+void gemm_tile_t(const GemmParams& p, bool utt, hipStream_t s, const char* tag) {
+  if (utt) gemm_tile<BM, BN, SPLIT, EPI, STAGES, OCC, 3, 0, GEMM_BK, 1>(p, s, tag);
+  else gemm_tile<BM, BN, SPLIT, EPI, STAGES, OCC, 3>(p, s, tag);
 }
 
 struct LinearPolicy {
@@ -81,6 +87,11 @@ struct LinearPolicy {
   // linears with at least gemm256_min_tiles tiles (1 persistent, 2 one tile per block, 0 off)
   int gemm256 = 2;
   static constexpr int gemm256_min_tiles = 256;
+  // ZV_TRANS_ALIGNED: utterance-aligned tiles with 16-B transposed stores (zv_gemm.inc UTT /
+  // store_trans8) for the counted NA in-projection and value projection where gemm_utt_ok holds
+  // (1 both, 0 neither: the row tiles and per-element stores; 2 the NA in-projection alone, 3 the
+  // value projection alone).  Bitwise equal; profiles/trans_aligned_ab.txt
+  bool utt_na = true, utt_t = true;
 
   LinearPolicy() {
     auto envi = [](const char* k, int d) { const char* v = getenv(k); return v ? atoi(v) : d; };
@@ -88,6 +99,9 @@ struct LinearPolicy {
     if (res_counted == 1) res_counted = 31;            // 1: all (0 / 1 are the A/B tests' arms)
     else if (res_counted >= 32) res_counted &= 31;     // 32 + mask: exactly that mask (bisection)
     gemm256 = envi("ZV_GEMM256", 2);
+    const int ta = envi("ZV_TRANS_ALIGNED", 1);
+    utt_na = ta == 1 || ta == 2;
+    utt_t = ta == 1 || ta == 3;
   }
 
   // The tile regimes, by how many 128 x 128 tiles the launch has.  The residual and small plain
@@ -315,7 +329,7 @@ struct LinearPolicy {
       // (64-row tiles at 3 blocks per CU at every size: 32.5 -> 31.4 ms per C2 step against 128-row
       // tiles for the large launches, round 6, profiles/r06_ffn_rows_na_tile_ab.txt; bitwise equal)
       if ((res_counted & 4) && p.bias && p.N % 48 == 0 && p.ldch % 4 == 0)
-        return gemm_tile<64, 96, 1, EPI_NA, 2, 3, 3>(p, s, "gemm_bf16_na");
+        return gemm_tile_t<64, 96, 1, EPI_NA, 2, 3>(p, utt_na && gemm_utt_ok(p), s, "gemm_bf16_na");
     }
     gemm_tile<128, 96, SPLIT, EPI_NA>(p, s, SPLIT == 3 ? "gemm_fp32_na" : "gemm_bf16_na");
   }
@@ -325,13 +339,14 @@ struct LinearPolicy {
   template <int SPLIT>
   void launch_value_t(const GemmParams& p, bool sa_split, bool has_lo, hipStream_t s) {
     const char* tag = SPLIT == 3 ? "gemm_fp32_t" : "gemm_bf16_t";
+    const bool utt = utt_t && gemm_utt_ok(p);
     if (sa_split) {                    // fp16 parity mode: a . (w_hi + w_lo)
       ZV_REQUIRE(has_lo && (res_counted & 16), "weight-split value projection");
-      gemm_tile<64, 64, 2, EPI_TRANS, ZV_WSPLIT_T_STAGES, ZV_WSPLIT_T_STAGES < 4 ? 2 : 1, 3>(p, s, "gemm_wsplit_t");
+      gemm_tile_t<64, 64, 2, EPI_TRANS, ZV_WSPLIT_T_STAGES, ZV_WSPLIT_T_STAGES < 4 ? 2 : 1>(p, utt, s, "gemm_wsplit_t");
     } else if (res_counted & 16) {
       // (a 4-deep K ring: one 64-row tile per block has 8 K steps and little else in flight;
       // 2 -> 4 stages: 24.0 -> 18.9 ms per C2 step, profiles/r05_vt_stages_ab.txt)
-      gemm_tile<64, 64, SPLIT, EPI_TRANS, 4, 2, 3>(p, s, tag);
+      gemm_tile_t<64, 64, SPLIT, EPI_TRANS, 4, 2>(p, utt, s, tag);
     } else {
       gemm_tile<64, 64, SPLIT, EPI_TRANS>(p, s, tag);
     }

@@ -186,6 +186,7 @@ SIGNATURES = {
     "zv_device_bytes": (ctypes.c_int64, [_P]),
     "zv_profile": (_I, [_I]),
     "zv_bench_gemm": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
+    "zv_bench_fused_linear": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
     "zv_gemm_selftest": (_I, [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "zv_linear_check": (_I, [ctypes.POINTER(ZvLinearCheckArgs)]),
     "zv_ffn_check": (_I, [ctypes.POINTER(ZvFfnCheckArgs)]),
