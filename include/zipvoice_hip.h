@@ -800,6 +800,74 @@ int zv_wavjoin_apply_docs(zv_wavjoin_handle h, const float* wav, int64_t wav_ld,
                           int32_t* spans, void* stream);
 int64_t zv_wavjoin_device_bytes(zv_wavjoin_handle h);
 
+/* The stateful join: the same join handed over push by push (zipvoice_amd/longform.py
+ * WavJoiner.stream, generate_long_stream; tests/wavjoin_stream_ref.py restates it in
+ * float64).  A stream owns D independent slots; a slot is one open document, as in
+ * zv_wavjoin_apply_docs, and D = 1 is the single-text case.  The stream borrows the joiner's
+ * parameters and scratch: the joiner must outlive it, and calls on a joiner and its streams
+ * are ordered by the caller (one device stream, or events), as calls on the joiner alone are.
+ *
+ * State.  After any push a slot holds on the device, for its last non-empty chunk p so far:
+ * m_p, g_p, the raw (ungained) last H_p = min(fade, m_p / 2) trimmed samples
+ * y_p[m_p - H_p, m_p) of every channel, and its stream position (the samples it has emitted).
+ * A fresh or reset slot holds nothing and is at position 0.  The storage, C * fade floats and
+ * a few words per slot, is allocated at create (zv_wavjoin_stream_device_bytes); a push
+ * allocates nothing for it.
+ *
+ * A push gives slot d the consecutive chunks [doc_ptr[d], doc_ptr[d + 1]) of its B chunks,
+ * a range that may be empty.  Frames, kept frames and the trimmed chunks y_b are as above.
+ * The chain of non-empty chunks starts at the slot's held chunk p, if it holds one: the
+ * first non-empty chunk b of the push then has F_b = min(fade, m_p / 2, m_b / 2) <= H_p, as
+ * if p had come in the same call; without a held chunk it has F_b = 0.  Column 0 of row d is
+ * the slot's position, so the held chunk starts at off_p = H_p - m_p (negative, never
+ * reported) and off_b = off_p + m_p - F_b = H_p - F_b >= 0.  The push writes to row d, in
+ * this order,
+ *   1. the held samples that are now final, g_p * y_p[m_p - H_p, m_p - F_b);
+ *   2. the F_b cross-faded samples, out[off_b + j] = g_p * y_p[m_p - F_b + j] * (1 - w)
+ *      + g_b * y_b[j] * w with w = (j + 1) / (F_b + 1): the fp32 expression of
+ *      zv_wavjoin_apply, on the raw held samples with g_p beside them;
+ *   3. its chunks, as zv_wavjoin_apply writes them,
+ *   4. except the last H = min(fade, m / 2) samples of its last non-empty chunk, which
+ *      become the slot's new held tail, raw, with that chunk's m and gain.
+ * A slot that gets no non-empty chunk writes nothing and keeps its state.  With
+ * host_final[d] != 0 the tail (the new one, or without a non-empty chunk the held one,
+ * g_p * y_p[m_p - H_p, m_p)) is written too, the slot then holds nothing, and it is closed: a
+ * closed slot takes no chunks and no second final until zv_wavjoin_stream_reset, which also
+ * puts its position back to 0.  Open or closed is host state, as host_final is.
+ *
+ * Invariant.  For any split of a chunk sequence into pushes, the last one final, the pieces
+ * of a row in push order are bitwise the row zv_wavjoin_apply (zv_wavjoin_apply_docs) writes
+ * for the whole sequence: pushes with B = 0, pushes whose chunks are all empty, a closing
+ * push without chunks and a predecessor several pushes back included.  spans and positions
+ * agree as well: off_b + pos_d is the chunk's off_b in the one-shot row.
+ *
+ * wav, lens, gains, spans: as for zv_wavjoin_apply, with spans[b] = {m_b, off_b, F_b} and
+ * off_b relative to column 0 of this push's row (-1 for an empty chunk).  doc_ptr: D + 1
+ * HOST int32, rising from doc_ptr[0] = 0 to doc_ptr[D] = B, or NULL with D == 1 (one slot of
+ * all B chunks); being a host array it is checked, and its values travel as launch
+ * arguments.  host_final: D host bytes, or NULL for none.  out: [D, C, out_ld]; out_len:
+ * device int64 [D, 2], {n_d, pos_d}: the samples this push wrote to row d and the samples the
+ * slot had emitted before it.  Columns [n_d, out_cap) are zero-filled, nothing is stored at
+ * or past out_cap, and the state advances whatever out_cap is; a slot loses nothing when
+ * out_cap >= fade + the sum of its chunks' lens in the push.
+ *
+ * Rejected: null handles, C not 1 or 2 or D < 1 at create, B < 0, doc_ptr NULL with D != 1,
+ * a doc_ptr that does not rise from 0 to B, out_cap > out_ld, chunks or a final for a closed
+ * slot, reset of a d outside [-1, D) (-1: every slot).  A rejected push changes nothing.
+ * The properties of zv_wavjoin_apply hold: no atomics, every output column written exactly
+ * once, results independent of the launch geometry, 64-bit positions, bit copies at gain 1
+ * outside overlaps; a warm push makes no host-blocking runtime call, and reset is ordered on
+ * its stream and does not block.  zv_wavjoin_apply and zv_wavjoin_apply_docs are unchanged. */
+typedef struct zv_wavjoin_stream* zv_wavjoin_stream_handle;
+zv_wavjoin_stream_handle zv_wavjoin_stream_create(zv_wavjoin_handle joiner, int C, int D);
+void zv_wavjoin_stream_destroy(zv_wavjoin_stream_handle s);
+int zv_wavjoin_stream_reset(zv_wavjoin_stream_handle s, int d, void* stream);
+int zv_wavjoin_stream_push(zv_wavjoin_stream_handle s, const float* wav, int64_t wav_ld,
+                           const int32_t* lens, const float* gains, int B, const int32_t* doc_ptr,
+                           const uint8_t* host_final, float* out, int64_t out_ld, int64_t out_cap,
+                           int64_t* out_len, int32_t* spans, void* stream);
+int64_t zv_wavjoin_stream_device_bytes(zv_wavjoin_stream_handle s);
+
 /* ------------------------------------------------------------------------
  * Seeded noise: standard normals that are a pure function of (seed, stream, element
  * index), drawn on the device (zipvoice_amd/noise.py seeded_normal; the seeds / seed

@@ -1892,6 +1892,43 @@ int zv_wavjoin_apply(zv_wavjoin_handle h, const float* wav, int64_t wav_ld, cons
 
 int64_t zv_wavjoin_device_bytes(zv_wavjoin_handle h) { return h ? (int64_t)h->bytes : 0; }
 
+zv_wavjoin_stream_handle zv_wavjoin_stream_create(zv_wavjoin_handle joiner, int C, int D) {
+  return api_create([&] {
+    std::unique_ptr<zv_wavjoin_stream> h(new zv_wavjoin_stream());
+    h->init(joiner, C, D);
+    return h.release();
+  });
+}
+
+void zv_wavjoin_stream_destroy(zv_wavjoin_stream_handle s) { delete s; }
+
+int zv_wavjoin_stream_reset(zv_wavjoin_stream_handle s, int d, void* stream) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(s != nullptr, "null wavjoin stream handle");
+  s->reset(d, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int zv_wavjoin_stream_push(zv_wavjoin_stream_handle s, const float* wav, int64_t wav_ld,
+                           const int32_t* lens, const float* gains, int B, const int32_t* doc_ptr,
+                           const uint8_t* host_final, float* out, int64_t out_ld, int64_t out_cap,
+                           int64_t* out_len, int32_t* spans, void* stream) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(s != nullptr, "null wavjoin stream handle");
+  ZV_REQUIRE(B >= 0, "B must be non-negative");
+  ZV_REQUIRE(doc_ptr || s->D == 1, "doc_ptr is NULL but D is not 1");
+  ZV_REQUIRE(out_cap <= out_ld, "out_cap exceeds out_ld");
+  ZV_REQUIRE(out_cap >= 0 && wav_ld >= 0 && wav_ld <= 0x7fffffffLL, "bad out_cap / wav_ld");
+  ZV_REQUIRE(out_len && (out || out_cap == 0) && ((wav && lens) || B == 0), "null argument");
+  s->push(wav, (long)wav_ld, lens, gains, B, doc_ptr, host_final, out, (long)out_ld, (long)out_cap,
+          reinterpret_cast<long*>(out_len), spans, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int64_t zv_wavjoin_stream_device_bytes(zv_wavjoin_stream_handle s) {
+  return s ? (int64_t)s->bytes : 0;
+}
+
 int64_t zv_vocoder_device_bytes(zv_vocoder_handle v) {
   if (!v) return 0;
   return (int64_t)(v->store.weight_bytes + v->x.bytes + v->frames.bytes + v->col.bytes() +

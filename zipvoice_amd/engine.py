@@ -246,6 +246,13 @@ SIGNATURES = {
     "zv_wavjoin_apply_docs": (_I, [_P, _P, ctypes.c_int64, _P, _P, _I, _I, _P, _I, _P,
                                    ctypes.c_int64, ctypes.c_int64, _P, _P, _P]),
     "zv_wavjoin_device_bytes": (ctypes.c_int64, [_P]),
+    # the stateful join (zipvoice_amd/longform.py WavJoinStream)
+    "zv_wavjoin_stream_create": (_P, [_P, _I, _I]),
+    "zv_wavjoin_stream_destroy": (None, [_P]),
+    "zv_wavjoin_stream_reset": (_I, [_P, _I, _P]),
+    "zv_wavjoin_stream_push": (_I, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _P, _P, ctypes.c_int64,
+                                    ctypes.c_int64, _P, _P, _P]),
+    "zv_wavjoin_stream_device_bytes": (ctypes.c_int64, [_P]),
     # seeded noise (zipvoice_amd/noise.py)
     "zv_noise_normal": (_I, [_P, _P, _I, ctypes.c_int64, ctypes.c_int64, _P, _P]),
     "zv_noise_check": (_I, [ctypes.POINTER(ZvNoiseCheckArgs)]),

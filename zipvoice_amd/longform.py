@@ -13,6 +13,9 @@ module's own (and ``include/zipvoice_hip.h`` for the join).  Its parts:
   case, a pause trim per row.
 * ``generate_long``: prompt -> chunks -> ``model.sample`` in batches that share the one
   prompt -> vocoder -> one join.
+* ``WavJoiner.stream`` / ``WavJoinStream``: the same join push by push (``zv_wavjoin_stream_*``);
+  ``generate_long_stream`` / ``stream_groups``: ``generate_long`` as a generator that yields
+  the audio group by group, bitwise the samples of the one-call join.
 * ``plan_long_batch`` / ``generate_long_batch``: several texts with their own prompts; the
   chunks of all of them are pooled into the ``model.sample`` batches, and one ``join_docs``
   writes one waveform per text.
@@ -264,8 +267,182 @@ class WavJoiner:
                 _eng._ptr(out), n, n, _eng._ptr(out_len), None, _eng._stream()), self._lib)
         return (out[:, 0] if squeeze else out), out_len
 
+    def stream(self, channels: int = 1, device=None) -> "WavJoinStream":
+        """A stateful join on this joiner's parameters (``zv_wavjoin_stream_*``): chunks go in
+        push by push, and the pieces that come out, concatenated, are bitwise ``__call__``
+        on all of them.  ``device``: the GPU it lives on (default: the current one)."""
+        return WavJoinStream(self, channels, device)
+
+
+class _PendingPiece:
+    """A queued push of a ``WavJoinStream``.  ``wait()`` blocks until the push has run and
+    returns (piece (C, n) on the device, spans (B, 3) int32 on the device, off_b relative to
+    the piece); ``position`` is then the stream position of the piece's first sample."""
+
+    def __init__(self, stream, out, spans, host_len, event, cap):
+        self._stream, self._out, self._spans = stream, out, spans
+        self._host_len, self._event, self._cap = host_len, event, cap
+        self.position, self._n = None, None
+
+    def wait(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self._host_len is not None:
+            # the one host wait: n depends on the data.  Ask first: waiting on an event that is
+            # done was seen to last until the work queued after it had drained (DESIGN.md §3a)
+            if not self._event.query():
+                self._event.synchronize()
+            self._n, self.position = (int(v) for v in self._host_len.tolist())
+            self._stream._pinned.append(self._host_len)   # back to the stream for a later push
+            self._host_len = None
+            self._stream.position = max(self._stream.position, self.position + self._n)
+        if self._n > self._cap:
+            raise RuntimeError(f"piece of {self._n} samples exceeds the allocated {self._cap}")
+        return self._out[:, :self._n], self._spans
+
+
+class WavJoinStream:
+    """One open document of a stateful join (a D = 1 ``zv_wavjoin_stream``; definition in
+    include/zipvoice_hip.h).  Between pushes the device keeps the last min(fade, m / 2)
+    samples of the last non-empty chunk, because their cross-fade depends on the chunk that
+    comes next; ``final`` releases them.  Keeps its ``WavJoiner`` alive; calls on the two are
+    ordered on the current device stream."""
+
+    def __init__(self, joiner: WavJoiner, channels: int = 1, device=None):
+        self.joiner, self.channels = joiner, int(channels)
+        dev = torch.device("cuda") if device is None else torch.device(device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self._h = None
+        jh = joiner._handle(dev)
+        self._lib = joiner._lib
+        with torch.cuda.device(dev):
+            self._h = self._lib.zv_wavjoin_stream_create(jh, self.channels, 1)
+        if not self._h:
+            raise ValueError(self._lib.zv_last_error().decode())
+        self.position = 0                             # samples emitted by the pieces waited for
+        self.closed = False
+        # pinned {n, pos} buffers: a pending piece borrows one and hands it back in wait(), so
+        # a warm push does not go to the pinned-memory allocator
+        self._pinned: List[torch.Tensor] = []
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                torch.cuda.synchronize(self.device)
+            except Exception:
+                pass
+            self._lib.zv_wavjoin_stream_destroy(self._h)
+            self._h = None
+
+    def device_bytes(self) -> int:
+        """The held tail and the slot's words on the device."""
+        return int(self._lib.zv_wavjoin_stream_device_bytes(self._h))
+
+    @torch.inference_mode()
+    def push_async(self, wavs: torch.Tensor, lens, gains=None, final: bool = False
+                   ) -> _PendingPiece:
+        """Queue a push and return without waiting: arguments as ``push``.  The piece's
+        length comes back through a pinned, non-blocking copy and an event, so work queued
+        between this call and ``wait()`` overlaps the wait."""
+        if self.closed:
+            raise RuntimeError("the stream is closed; reset() it first")
+        if wavs.dim() == 2:
+            wavs = wavs.unsqueeze(1)
+        if wavs.dim() == 3 and wavs.shape[1] != self.channels:
+            raise ValueError(f"the stream has {self.channels} channel(s), got "
+                             f"{tuple(wavs.shape)}")
+        if wavs.is_cuda and wavs.device != self.device:
+            raise ValueError(f"the stream lives on {self.device}, got wavs on {wavs.device}")
+        _, dev, wavs, lens_host, ln, g = self.joiner._prepare(wavs.to(self.device), lens, gains)
+        B, C, n = wavs.shape
+        # a slot emits at most its held tail (<= fade) and its chunks; lens on the device are
+        # not read here, so the padded length bounds them
+        cap = self.joiner.fade + (sum(lens_host) if lens_host is not None else B * n)
+        out = torch.empty((C, max(cap, 1)), dtype=torch.float32, device=dev)
+        out_len = torch.empty(2, dtype=torch.int64, device=dev)
+        spans = torch.empty((max(B, 1), 3), dtype=torch.int32, device=dev)
+        host_len = (self._pinned.pop() if self._pinned
+                    else torch.empty(2, dtype=torch.int64, pin_memory=True))
+        fin = (ctypes.c_uint8 * 1)(1 if final else 0)
+        with torch.cuda.device(dev):
+            _eng._check(self._lib.zv_wavjoin_stream_push(
+                self._h, _eng._ptr(wavs), n, _eng._ptr(ln), _eng._ptr(g), B, None, fin,
+                _eng._ptr(out), out.shape[1], cap, _eng._ptr(out_len), _eng._ptr(spans),
+                _eng._stream()), self._lib)
+            host_len.copy_(out_len, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+        self.closed = bool(final)
+        return _PendingPiece(self, out, spans[:B], host_len, event, cap)
+
+    def push(self, wavs: torch.Tensor, lens, gains=None, final: bool = False
+             ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """wavs (B, n) or (B, C, n), lens and gains as in ``WavJoiner.__call__`` (lens may
+        also be a device tensor, which costs no host wait but allocates for the padded
+        length) -> (piece (C, n) on the device, spans (B, 3): m_b, off_b relative to the
+        piece, F_b).  Allocates fade + sum(lens) columns, or fade + B * n with ``lens`` on the
+        device; the piece is a view of that buffer and keeps all of it alive (``clone()`` a
+        piece that is kept for long).  ``final`` also emits the held tail and closes the
+        stream."""
+        return self.push_async(wavs, lens, gains, final).wait()
+
+    def close(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """A final push of no chunks: the held tail, gained."""
+        empty = torch.empty((0, self.channels, 0), dtype=torch.float32, device=self.device)
+        return self.push(empty, [], None, final=True)
+
+    def reset(self) -> None:
+        """Forget the held tail and the position (ordered on the current stream) and reopen."""
+        with torch.cuda.device(self.device):
+            _eng._check(self._lib.zv_wavjoin_stream_reset(self._h, 0, _eng._stream()), self._lib)
+        self.position, self.closed = 0, False
+
 
 # ------------------------------------------------------------------------------ pipeline
+def _long_prepare(tokens, prompt_tokens, prompt_wav, model, feature_extractor, break_ids,
+                  soft_break_ids, max_seconds, speed, target_rms, feat_scale, feat_bias,
+                  sampling_rate, prompt_sampling_rate):
+    """What ``generate_long`` and ``generate_long_stream`` do before the first chunk runs:
+    the prompt, prepared once as ``infer.generate_sentence`` does, and the text cut by
+    ``chunk_budget`` and ``chunk_tokens``.  Returns (prompt_features (1, P, F) on the device,
+    the prompt's RMS before normalisation, the chunks)."""
+    from .infer import _prompt_rms_normalise, _resampler
+    dev = model.device
+    w = torch.as_tensor(np.asarray(prompt_wav) if not torch.is_tensor(prompt_wav) else prompt_wav,
+                        dtype=torch.float32)
+    if w.dim() == 1:
+        w = w.unsqueeze(0)
+    if prompt_sampling_rate != sampling_rate:
+        w = _resampler(prompt_sampling_rate, sampling_rate)(w.to(dev))
+    w, prompt_rms = _prompt_rms_normalise(w, target_rms)
+    feats = feature_extractor.extract(w.to(dev), sampling_rate=sampling_rate)
+    prompt_features = ((feats.unsqueeze(0) + feat_bias) * feat_scale).to(dev)
+    budget = chunk_budget(len(prompt_tokens), w.shape[-1] / sampling_rate, max_seconds, speed)
+    chunks = chunk_tokens(tokens, break_ids, budget, soft_break_ids)
+    if not chunks:
+        raise ValueError("no tokens to synthesise")
+    return prompt_features, prompt_rms, chunks
+
+
+def _long_group(model, vocoder, grp, first, prompt_tokens, prompt_features, seed, x0, speed,
+                t_shift, num_step, guidance_scale, feat_scale, feat_bias):
+    """One group of consecutive chunks, ``grp[i]`` being chunk ``first + i`` of the text:
+    ``model.sample`` on rows that repeat the prompt (with a seed, row i draws from
+    (seed, stream = first + i)), then the vocoder.  Returns (wavs (nb, n), frames (nb,))."""
+    nb, dev, P = len(grp), model.device, prompt_features.size(1)
+    pred, pred_lens, _, _ = model.sample(
+        tokens=grp, prompt_tokens=[prompt_tokens] * nb,
+        prompt_features=prompt_features.expand(nb, -1, -1).contiguous(),
+        prompt_features_lens=torch.full((nb,), P, dtype=torch.int64, device=dev),
+        speed=speed, t_shift=t_shift, duration="predict", num_step=num_step,
+        guidance_scale=guidance_scale, x0=x0,
+        seeds=None if seed is None else [seed] * nb,
+        seed_streams=None if seed is None else list(range(first, first + nb)))
+    wav = vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale, feat_bias=feat_bias,
+                                  clamp=True)
+    return wav, pred_lens
+
+
 @torch.inference_mode()
 def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model, vocoder,
                   feature_extractor, break_ids, soft_break_ids=(), max_seconds: float = 25.0,
@@ -290,27 +467,14 @@ def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model
     per-chunk gain.  Returns (wav (1, N) on the device, metrics with t, wav_seconds, rtf,
     num_chunks, num_batches); with ``return_chunks`` also the list of per-chunk waveforms
     (untrimmed, before the gain) and the joiner's spans."""
-    from .infer import _prompt_rms_normalise, _resampler
     if seed is not None:
         if x0 is not None:
             raise ValueError("give x0 or seed, not both")
         seed = check_keys([seed])[0][0]
     dev = model.device
-    w = torch.as_tensor(np.asarray(prompt_wav) if not torch.is_tensor(prompt_wav) else prompt_wav,
-                        dtype=torch.float32)
-    if w.dim() == 1:
-        w = w.unsqueeze(0)
-    if prompt_sampling_rate != sampling_rate:
-        w = _resampler(prompt_sampling_rate, sampling_rate)(w.to(dev))
-    w, prompt_rms = _prompt_rms_normalise(w, target_rms)
-    feats = feature_extractor.extract(w.to(dev), sampling_rate=sampling_rate)
-    prompt_features = ((feats.unsqueeze(0) + feat_bias) * feat_scale).to(dev)
-    P = prompt_features.size(1)
-
-    budget = chunk_budget(len(prompt_tokens), w.shape[-1] / sampling_rate, max_seconds, speed)
-    chunks = chunk_tokens(tokens, break_ids, budget, soft_break_ids)
-    if not chunks:
-        raise ValueError("no tokens to synthesise")
+    prompt_features, prompt_rms, chunks = _long_prepare(
+        tokens, prompt_tokens, prompt_wav, model, feature_extractor, break_ids, soft_break_ids,
+        max_seconds, speed, target_rms, feat_scale, feat_bias, sampling_rate, prompt_sampling_rate)
     groups = [chunks[i:i + batch_size] for i in range(0, len(chunks), int(batch_size))]
     if x0 is not None and len(x0) != len(groups):
         raise ValueError(f"x0 must hold one tensor per sample() call ({len(groups)}), got {len(x0)}")
@@ -321,18 +485,11 @@ def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model
     t0 = dt.datetime.now()
     wavs, lens = [], []
     for gi, grp in enumerate(groups):
-        nb = len(grp)
-        pred, pred_lens, _, _ = model.sample(
-            tokens=grp, prompt_tokens=[prompt_tokens] * nb,
-            prompt_features=prompt_features.expand(nb, -1, -1).contiguous(),
-            prompt_features_lens=torch.full((nb,), P, dtype=torch.int64, device=dev),
-            speed=speed, t_shift=t_shift, duration="predict", num_step=num_step,
-            guidance_scale=guidance_scale, x0=None if x0 is None else x0[gi],
-            seeds=None if seed is None else [seed] * nb,
-            seed_streams=None if seed is None else list(range(gi * int(batch_size),
-                                                              gi * int(batch_size) + nb)))
-        wavs.append(vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale,
-                                            feat_bias=feat_bias, clamp=True))
+        wav, pred_lens = _long_group(
+            model, vocoder, grp, gi * int(batch_size), prompt_tokens, prompt_features, seed,
+            None if x0 is None else x0[gi], speed, t_shift, num_step, guidance_scale, feat_scale,
+            feat_bias)
+        wavs.append(wav)
         lens.append(pred_lens)
     lens_host = [int(v) * hop for v in torch.cat(lens).tolist()]
     K, n = len(chunks), max(x.shape[1] for x in wavs)
@@ -354,6 +511,89 @@ def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model
     if return_chunks:
         return out, metrics, [batch[i, :lens_host[i]] for i in range(K)], spans
     return out, metrics
+
+
+def stream_groups(K: int, first_batch: int = 1, batch_size: int = 32) -> List[List[int]]:
+    """The ``model.sample`` calls of ``generate_long_stream`` over K chunks (host only): the
+    first group takes min(first_batch, K) chunks, so the first audio waits for a small
+    batch; the rest follow in text order in groups of ``batch_size``."""
+    K, first_batch, batch_size = int(K), int(first_batch), int(batch_size)
+    if K < 0 or first_batch < 1 or batch_size < 1:
+        raise ValueError("K must be non-negative, first_batch and batch_size at least 1")
+    first = min(first_batch, K)
+    groups = [list(range(first))] if first else []
+    return groups + [list(range(i, min(i + batch_size, K))) for i in range(first, K, batch_size)]
+
+
+@torch.inference_mode()
+def generate_long_stream(tokens: List[int], prompt_tokens: List[int], prompt_wav, model, vocoder,
+                         feature_extractor, break_ids, soft_break_ids=(),
+                         max_seconds: float = 25.0, first_batch: int = 1, batch_size: int = 32,
+                         seed: Optional[int] = None, joiner: Optional[WavJoiner] = None,
+                         return_chunks: bool = False, num_step: int = 16,
+                         guidance_scale: float = 1.0, speed: float = 1.0, t_shift: float = 0.5,
+                         target_rms: float = 0.1, feat_scale: float = 0.1, feat_bias: float = 0.0,
+                         sampling_rate: int = 24000, prompt_sampling_rate: int = 24000):
+    """``generate_long`` as a generator that hands the audio over group by group (mono and
+    one-channel Dialog models; no ``x0``: seeds are the batch-invariant path).
+
+    The prompt, the chunks and the per-chunk seeding (chunk k draws from (seed, stream = k))
+    are ``generate_long``'s; ``stream_groups`` forms the groups.  Every group runs
+    ``model.sample`` and ``vocoder.decode_features`` and is then pushed into one
+    ``WavJoinStream`` with the RMS restore as its chunks' gain; the last group's push is
+    final.  Streaming changes when samples are handed over, never their value: the pieces,
+    concatenated, are bitwise the ``WavJoiner`` join of all chunks in one call.
+
+    Yields one (piece (1, n) on the device, info) per group, n >= 0.  Piece g is handed over
+    as soon as its length is back (a pinned copy and an event); group g + 1 is queued when
+    the consumer asks for the next piece.  Queueing it first was measured and is worse:
+    ``model.sample`` reads its frame count back at its start and holds the host through most
+    of its solve, so piece 0, ready after 83 ms, left the generator after 270 ms (DESIGN.md
+    §3a).  ``WavJoinStream.push_async`` is there for a caller whose producer does not block.
+    The price of this order: the GPU is idle for as long as the consumer keeps piece g before
+    it asks for the next one, so a consumer hands the piece on (to a queue, a socket writer)
+    and comes straight back.  A push gets ``lens`` on the device, so each piece is a view of a
+    buffer of fade + (rows * padded length) columns, which it keeps alive.
+    info: group, chunks_done, num_chunks, position (samples emitted, this piece included),
+    final, t (seconds on the host clock from the first group's start, taken as
+    ``generate_long`` takes its ``t``, to this piece's completion: the first yield's ``t`` is
+    the time to first audio); with ``return_chunks`` also chunks (the group's waveforms,
+    untrimmed, before the gain) and spans (m_b, off_b relative to the piece, F_b)."""
+    if seed is not None:
+        seed = check_keys([seed])[0][0]
+    dev = model.device
+    prompt_features, prompt_rms, chunks = _long_prepare(
+        tokens, prompt_tokens, prompt_wav, model, feature_extractor, break_ids, soft_break_ids,
+        max_seconds, speed, target_rms, feat_scale, feat_bias, sampling_rate, prompt_sampling_rate)
+    K = len(chunks)
+    groups = stream_groups(K, first_batch, batch_size)
+    joiner = joiner if joiner is not None else WavJoiner()
+    hop = vocoder.cfg.hop_length
+    gain = prompt_rms / target_rms if prompt_rms < target_rms else None
+
+    js = joiner.stream(1, device=dev)
+    torch.cuda.synchronize(dev)
+    t0 = dt.datetime.now()
+
+    def queue(gi):
+        idx = groups[gi]
+        wav, pred_lens = _long_group(
+            model, vocoder, [chunks[i] for i in idx], idx[0], prompt_tokens, prompt_features,
+            seed, None, speed, t_shift, num_step, guidance_scale, feat_scale, feat_bias)
+        lens = pred_lens.to(dev, torch.int32) * hop          # stays on the device: no wait here
+        return wav, lens, js.push_async(wav, lens, None if gain is None else [gain] * len(idx),
+                                        final=gi == len(groups) - 1)
+
+    for gi, idx in enumerate(groups):
+        wav, lens, pending = queue(gi)
+        piece, spans = pending.wait()
+        info = {"group": gi, "chunks_done": idx[-1] + 1, "num_chunks": K,
+                "position": pending.position + piece.shape[1], "final": gi == len(groups) - 1,
+                "t": (dt.datetime.now() - t0).total_seconds()}
+        if return_chunks:
+            info["chunks"] = [wav[i, :n] for i, n in enumerate(lens.tolist())]
+            info["spans"] = spans
+        yield piece, info
 
 
 # ------------------------------------------------------------------------------ pooled
