@@ -869,6 +869,78 @@ int zv_wavjoin_stream_push(zv_wavjoin_stream_handle s, const float* wav, int64_t
 int64_t zv_wavjoin_stream_device_bytes(zv_wavjoin_stream_handle s);
 
 /* ------------------------------------------------------------------------
+ * Speech editing: the two assembly passes around the solve of an edit, which regenerates
+ * marked spans of a recording and keeps the rest (zipvoice_amd/edit.py, ZipVoice.sample_edit /
+ * sample_intermediate).  NO reference counterpart: the reference's sample_intermediate
+ * (zipvoice/models/zipvoice.py:488-534) takes a ready speech condition and returns features,
+ * so the tables and the junction rule are defined here (tests/edit_ref.py restates them in
+ * numpy).  fp32, no atomics, every output element written exactly once: results are bitwise
+ * reproducible and do not depend on the launch geometry.
+ *
+ * Tables.  Both calls take, as HOST arrays, the segments of all rows one row after the other
+ * and row_ptr [B + 1] int32 rising from 0: row b owns segments [row_ptr[b], row_ptr[b + 1]),
+ * a range that may be empty (an empty row).  Being host arrays they are validated completely
+ * before anything is queued; a bad table is an error string (it names the row) and launches
+ * nothing.  The checked table is written into pinned staging owned by the handle and copied to
+ * the handle's device table on `stream`; a staging buffer is taken again only once the GPU has
+ * marked its copy done, so calls queued back to back on a handle each keep their own table
+ * until it has been read.  Calls on one handle are ordered by the caller (one device stream, or
+ * events).  The device table grows on demand (zv_edit_device_bytes, 0 before the first call); a
+ * warm call makes no host-blocking runtime call.
+ *
+ * zv_edit_gather.  A frame table has rows (dst, src, len) int32: output frames
+ * [dst, dst + len) of the row are original frames [src, src + len) (a kept segment), or
+ * generated when src == -1.  Required: len > 0; the segments of a row tile [0, T_b) in order
+ * (dst of the first is 0, dst of each next is dst + len of the one before) with T_b <= T; a
+ * kept segment lies in [0, lens[b]); 0 <= lens[b] <= Lmax.
+ *   feat [B, Lmax, F] device, fill [B, T, F] device or NULL, out [B, T, F] device, mask
+ *   [B, T] device uint8 or NULL, lens [B] host int32.
+ *   out[b, t] = feat[b, src + (t - dst)] on a kept segment, fill[b, t] (0 without fill) on a
+ *   generated one, 0 for t >= T_b, all bitwise copies; mask[b, t] = 1 exactly on generated
+ *   frames.  One call with fill == NULL builds the speech condition of an edit; one with the
+ *   solver's output as fill puts the original frames back over it.  out may be fill itself; it
+ *   must not overlap feat.  F % 4 == 0 with 16-byte aligned feat / fill / out moves four
+ *   features per thread as 16-byte loads and stores, anything else one feature per thread.
+ *   Rejected: a null handle, feat, lens, row_ptr or out, B outside [1, 65535], Lmax, F or
+ *   T < 1, a table that breaks a rule above.
+ *
+ * zv_edit_splice.  A sample table has rows (out, src, len, kind) int32: output samples
+ * [out, out + len) of the row are samples [src, src + len) of the row's original waveform
+ * (kind 0) or of its generated waveform (kind 1).  Required: len > 0; the segments of a row
+ * tile [0, N_b) in order with N_b <= out_cols; a segment lies inside its source's valid samples
+ * [0, lens[b]) or [0, gen_lens[b]); lens[b] <= ld, gen_lens[b] <= ldg.
+ *   orig [B, C, ld] device, gen [B, C, ldg] device, out [B, C, out_ld] device, C in {1, 2};
+ *   lens, gen_lens [B] host int32; gains [B] host fp32, the factor on row b's generated
+ *   samples; fade >= 0 samples.
+ *   Away from the junctions out is the table's gather: original samples bitwise, generated
+ *   samples times the row's gain (bitwise at a gain of exactly 1).  At the junction at output
+ *   position p between consecutive segments i and i + 1 of a row, with lim the valid samples of
+ *   a segment's source,
+ *     h = min(fade, len_i / 2, len_{i+1} / 2, lim_i - (src_i + len_i), src_{i+1})
+ *   (integer halves; the last two keep both reads below inside their buffers), and for
+ *   j in [0, 2h), q = p - h + j, w = (j + 0.5) / (2h):
+ *     out[q] = g_i * x_i[src_i + (q - out_i)] * (1 - w) + g_{i+1} * x_{i+1}[src_{i+1} + (q - p)] * w
+ *   in fp32: segment i read on past its end, segment i + 1 read from before its start, g = 1
+ *   for an original segment and the row's gain for a generated one.  The rule is the same for
+ *   kept | generated, generated | kept and the kept | kept junction a deletion leaves; the
+ *   len / 2 clamps keep the windows of neighbouring junctions apart.  Columns [N_b, out_cols)
+ *   are zero-filled and nothing is stored at or past out_cols.
+ *   Rejected: a null handle or array, B < 1, C not 1 or 2, fade < 0, ld, ldg or out_cols
+ *   outside [1, 2^31), out_cols > out_ld, a table that breaks a rule above.
+ * ---------------------------------------------------------------------- */
+typedef struct zv_edit* zv_edit_handle;
+zv_edit_handle zv_edit_create(void);
+void zv_edit_destroy(zv_edit_handle h);
+int64_t zv_edit_device_bytes(zv_edit_handle h);
+int zv_edit_gather(zv_edit_handle h, const float* feat, int B, int Lmax, int F, const int32_t* host_lens,
+                   const float* fill, const int32_t* host_table, const int32_t* host_row_ptr, int T,
+                   float* out, uint8_t* mask, void* stream);
+int zv_edit_splice(zv_edit_handle h, const float* orig, int64_t ld, const int32_t* host_lens, const float* gen,
+                   int64_t ldg, const int32_t* host_gen_lens, int B, int C, const int32_t* host_table,
+                   const int32_t* host_row_ptr, const float* host_gains, int fade, float* out, int64_t out_ld,
+                   int64_t out_cols, void* stream);
+
+/* ------------------------------------------------------------------------
  * Seeded noise: standard normals that are a pure function of (seed, stream, element
  * index), drawn on the device (zipvoice_amd/noise.py seeded_normal; the seeds / seed
  * arguments of sample, generate_sentence, generate_batch, generate_long and

@@ -1431,6 +1431,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
 #include "zv_fbank.inc"
 #include "zv_resample.inc"
 #include "zv_wavjoin.inc"
+#include "zv_edit.inc"
 
 // ===========================================================================
 // C ABI
@@ -1927,6 +1928,48 @@ int zv_wavjoin_stream_push(zv_wavjoin_stream_handle s, const float* wav, int64_t
 
 int64_t zv_wavjoin_stream_device_bytes(zv_wavjoin_stream_handle s) {
   return s ? (int64_t)s->bytes : 0;
+}
+
+zv_edit_handle zv_edit_create(void) {
+  return api_create([&] { return new zv_edit(); });
+}
+
+void zv_edit_destroy(zv_edit_handle h) { delete h; }
+
+int64_t zv_edit_device_bytes(zv_edit_handle h) { return h ? (int64_t)h->device_bytes() : 0; }
+
+int zv_edit_gather(zv_edit_handle h, const float* feat, int B, int Lmax, int F, const int32_t* host_lens,
+                   const float* fill, const int32_t* host_table, const int32_t* host_row_ptr, int T,
+                   float* out, uint8_t* mask, void* stream) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(h != nullptr, "null edit handle");
+  ZV_REQUIRE(B >= 1 && B <= 65535, "B must be in [1, 65535]");
+  ZV_REQUIRE(Lmax >= 1 && F >= 1 && T >= 1, "Lmax, F and T must be at least 1");
+  ZV_REQUIRE((int64_t)B * T * F <= (int64_t)1 << 40 && (int64_t)B * Lmax * F <= (int64_t)1 << 40,
+             "batch too large");
+  ZV_REQUIRE(feat && host_lens && host_row_ptr && out, "zv_edit_gather: null argument");
+  ZV_REQUIRE(host_table || host_row_ptr[B] == 0, "zv_edit_gather: null table");
+  h->gather(feat, B, Lmax, F, host_lens, fill, host_table, host_row_ptr, T, out, mask, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int zv_edit_splice(zv_edit_handle h, const float* orig, int64_t ld, const int32_t* host_lens, const float* gen,
+                   int64_t ldg, const int32_t* host_gen_lens, int B, int C, const int32_t* host_table,
+                   const int32_t* host_row_ptr, const float* host_gains, int fade, float* out, int64_t out_ld,
+                   int64_t out_cols, void* stream) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(h != nullptr, "null edit handle");
+  ZV_REQUIRE(B >= 1, "B must be at least 1");
+  ZV_REQUIRE(C == 1 || C == 2, "C must be 1 or 2");
+  ZV_REQUIRE(fade >= 0, "fade must be non-negative");
+  ZV_REQUIRE(ld >= 1 && ld <= 0x7fffffffLL && ldg >= 1 && ldg <= 0x7fffffffLL, "bad ld / ldg");
+  ZV_REQUIRE(out_cols >= 1 && out_cols <= out_ld && out_cols <= 0x7fffffffLL, "out_cols must be in [1, out_ld]");
+  ZV_REQUIRE(orig && host_lens && gen && host_gen_lens && host_row_ptr && host_gains && out,
+             "zv_edit_splice: null argument");
+  ZV_REQUIRE(host_table || host_row_ptr[B] == 0, "zv_edit_splice: null table");
+  h->splice(orig, (long)ld, host_lens, gen, (long)ldg, host_gen_lens, B, C, host_table, host_row_ptr, host_gains,
+            fade, out, (long)out_ld, (long)out_cols, (hipStream_t)stream);
+  ZV_API_END
 }
 
 int64_t zv_vocoder_device_bytes(zv_vocoder_handle v) {

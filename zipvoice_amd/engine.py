@@ -253,6 +253,13 @@ SIGNATURES = {
     "zv_wavjoin_stream_push": (_I, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _P, _P, ctypes.c_int64,
                                     ctypes.c_int64, _P, _P, _P]),
     "zv_wavjoin_stream_device_bytes": (ctypes.c_int64, [_P]),
+    # speech editing (zipvoice_amd/edit.py, HipEngine.edit_gather / edit_splice)
+    "zv_edit_create": (_P, []),
+    "zv_edit_destroy": (None, [_P]),
+    "zv_edit_device_bytes": (ctypes.c_int64, [_P]),
+    "zv_edit_gather": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "zv_edit_splice": (_I, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _I, _I, _P, _P, _P, _I,
+                            _P, ctypes.c_int64, ctypes.c_int64, _P]),
     # seeded noise (zipvoice_amd/noise.py)
     "zv_noise_normal": (_I, [_P, _P, _I, ctypes.c_int64, ctypes.c_int64, _P, _P]),
     "zv_noise_check": (_I, [ctypes.POINTER(ZvNoiseCheckArgs)]),
@@ -397,6 +404,10 @@ class HipEngine:
                 torch.cuda.synchronize(self.device)
             except Exception:
                 pass
+            e = getattr(self, "_edit", None)
+            if e:
+                self.lib.zv_edit_destroy(e)
+                self._edit = None
             self.lib.zv_destroy(h)
             self.h = None
 
@@ -529,6 +540,86 @@ class HipEngine:
         c = (ctypes.c_int64 * 2)()
         self._check(self.lib.zv_sched_stats(self.h, ctypes.cast(c, ctypes.c_void_p)))
         return int(c[0]), int(c[1])
+
+    # ------------------------------------------------------------------ speech editing
+    def _edit_handle(self):
+        """The engine's zv_edit handle (device table + pinned staging), made on first use."""
+        if not getattr(self, "_edit", None):
+            with torch.cuda.device(self.device):
+                self._edit = self.lib.zv_edit_create()
+            if not self._edit:
+                raise RuntimeError(self.lib.zv_last_error().decode())
+        return self._edit
+
+    def _edit_check(self, rc: int):
+        if rc != 0 and "edit table:" in self.lib.zv_last_error().decode():
+            raise ValueError(self.lib.zv_last_error().decode())
+        self._check(rc)
+
+    @staticmethod
+    def _host_i32(a, shape, name: str) -> np.ndarray:
+        a = np.ascontiguousarray(np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int32))
+        if a.shape != tuple(shape):
+            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {a.shape}")
+        return a
+
+    def edit_device_bytes(self) -> int:
+        return int(self.lib.zv_edit_device_bytes(self._edit_handle()))
+
+    def edit_gather(self, feat: torch.Tensor, lens, table, row_ptr, T: int,
+                    fill: Optional[torch.Tensor] = None):
+        """zv_edit_gather: ``feat`` (B, Lmax, F) with ``lens`` (B,) original frame counts and a
+        frame table (edit.plan_edit_batch: ``table`` (n, 3) rows (dst, src, len), ``row_ptr``
+        (B + 1,), host arrays) -> (out (B, T, F), mask (B, T) bool, True on generated frames).
+        Kept frames are copied from ``feat``, generated ones from ``fill`` (B, T, F) or zero, frames
+        past a row's new length are zero.  A bad table is a ValueError and launches nothing."""
+        feat = self._f32(feat, "feat")
+        B, Lmax, F = feat.shape
+        lens = self._host_i32(lens, (B,), "lens")
+        row_ptr = self._host_i32(row_ptr, (B + 1,), "row_ptr")
+        table = self._host_i32(np.asarray(table).reshape(-1, 3), (max(int(row_ptr[-1]), 0), 3), "table")
+        if fill is not None:
+            fill = self._f32(fill, "fill", (B, T, F))
+        out = torch.empty((B, int(T), F), dtype=torch.float32, device=self.device)
+        mask = torch.empty((B, int(T)), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            self._edit_check(self.lib.zv_edit_gather(
+                self._edit_handle(), _ptr(feat), B, Lmax, F, lens.ctypes.data, _ptr(fill),
+                table.ctypes.data, row_ptr.ctypes.data, int(T), _ptr(out), _ptr(mask), _stream()))
+        return out, mask.bool()
+
+    def edit_splice(self, orig: torch.Tensor, lens, gen: torch.Tensor, gen_lens, table, row_ptr,
+                    gains=None, fade: int = 240, out_cols: Optional[int] = None) -> torch.Tensor:
+        """zv_edit_splice: ``orig`` (B, C, n) with ``lens`` (B,) true sample counts, ``gen``
+        (B, C, m) with ``gen_lens`` valid samples and a sample table (edit.sample_table_batch:
+        ``table`` (n, 4) rows (out, src, len, kind), ``row_ptr``) -> (B, C, out_cols): the table's
+        gather with a linear cross-fade of up to ``fade`` samples to either side of every
+        junction; ``gains`` (B,) host floats scale the generated samples.  Zero past a row's length;
+        out_cols defaults to the longest row."""
+        if orig.dim() == 2:
+            orig, gen = orig.unsqueeze(1), gen.unsqueeze(1)
+        orig, gen = self._f32(orig, "orig"), self._f32(gen, "gen")
+        B, C, n = orig.shape
+        if gen.dim() != 3 or gen.shape[:2] != (B, C):
+            raise ValueError(f"gen: expected ({B}, {C}, m), got {tuple(gen.shape)}")
+        lens = self._host_i32(lens, (B,), "lens")
+        gen_lens = self._host_i32(gen_lens, (B,), "gen_lens")
+        row_ptr = self._host_i32(row_ptr, (B + 1,), "row_ptr")
+        table = self._host_i32(np.asarray(table).reshape(-1, 4), (max(int(row_ptr[-1]), 0), 4), "table")
+        g = np.ones(B, np.float32) if gains is None else np.ascontiguousarray(np.asarray(gains, np.float32))
+        if g.shape != (B,):
+            raise ValueError("gains must have shape (B,)")
+        if out_cols is None:
+            ends = [int(table[row_ptr[b + 1] - 1, 0] + table[row_ptr[b + 1] - 1, 2])
+                    for b in range(B) if row_ptr[b + 1] > row_ptr[b]]
+            out_cols = max(ends + [1])
+        out = torch.empty((B, C, int(out_cols)), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._edit_check(self.lib.zv_edit_splice(
+                self._edit_handle(), _ptr(orig), n, lens.ctypes.data, _ptr(gen), gen.shape[2],
+                gen_lens.ctypes.data, B, C, table.ctypes.data, row_ptr.ctypes.data, g.ctypes.data,
+                int(fade), _ptr(out), int(out_cols), int(out_cols), _stream()))
+        return out
 
     def reserve(self, max_batch: int, max_frames: int) -> None:
         """Pre-size the decoder workspace (zv_reserve)."""

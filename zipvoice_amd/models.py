@@ -259,6 +259,93 @@ class ZipVoice:
         return split_prompt(x1, prompt_features_lens, x1_wo_prompt_lens, Tg, Tp) + (
             prompt_features_lens,)
 
+    # ------------------------------------------------------------------ editing
+    def sample_edit(self, tokens: List[List[int]], features: torch.Tensor,
+                    features_lens: torch.Tensor, spans, num_step: int = 5,
+                    guidance_scale: float = 0.5, t_shift: float = 1.0, t_start: float = 0.0,
+                    t_end: float = 1.0, x0: Optional[torch.Tensor] = None,
+                    seeds: Optional[Sequence[int]] = None,
+                    seed_streams: Optional[Sequence[int]] = None, keep_original: bool = True):
+        """Regenerate marked spans of ``features`` (B, Lmax, F; ``features_lens`` frames per row)
+        and keep the rest: the infill the model is trained for (``forward``, zipvoice.py:358-363).
+        No reference counterpart beyond ``sample_intermediate``.
+
+        ``tokens`` is the whole new transcript of each row; ``spans[b]`` the row's edits
+        ``(s, e, n)``, "replace original frames [s, e) by n generated ones" (``edit.plan_edit``;
+        ``e == s`` inserts, ``n == 0`` deletes).  The text condition is the ground-truth-duration
+        one over the new lengths (the reference's ``forward_text_train``), the speech condition
+        the kept frames at their new places and zeros on the generated ones
+        (``engine.edit_gather``).  ``num_step`` / ``t_shift`` / ``guidance_scale``, ``x0``,
+        ``seeds`` and ``seed_streams`` are ``sample``'s.  With ``keep_original`` the kept frames
+        of the result are the input's, bit for bit; without it they are the solver's.
+
+        Returns (x1 (B, T, F), the new lengths (B,), mask (B, T) bool: True on generated
+        frames)."""
+        from .edit import plan_edit_batch
+        if seeds is not None and x0 is not None:
+            raise ValueError("give x0 or seeds, not both")
+        if seed_streams is not None and seeds is None:
+            raise ValueError("seed_streams needs seeds")
+        if seeds is not None:
+            seeds, seed_streams = check_keys(seeds, seed_streams, len(tokens))
+        eng = self._need_engine()
+        B = len(tokens)
+        schedule = per_row_schedule(B, num_step=num_step, t_shift=t_shift,
+                                    guidance_scale=guidance_scale, speed=1.0)
+        if features.dim() != 3 or features.size(0) != B:
+            raise ValueError(f"features must be (B = {B}, L, F), got {tuple(features.shape)}")
+        plan = plan_edit_batch(features_lens.tolist() if torch.is_tensor(features_lens)
+                               else features_lens, spans)
+        if int(plan.lens.max()) > features.size(1):
+            raise ValueError("features_lens exceed the frames of features")
+        new_lens = torch.from_numpy(plan.new_lens.astype(np.int64)).to(self.device)
+        embed, tokens_lens = self.forward_text_embed(tokens)
+        text_condition, padding_mask = self.forward_text_condition(embed, tokens_lens, new_lens)
+        num_frames, F = text_condition.size(1), features.size(-1)
+        speech_condition, mask = eng.edit_gather(features, plan.lens, plan.table, plan.row_ptr,
+                                                 num_frames)
+        if seeds is not None:
+            x0 = seeded_normal(seeds, (num_frames, F), seed_streams, device=self.device)
+        elif x0 is None:
+            x0 = torch.randn(B, num_frames, F, device=self.device)
+        elif tuple(x0.shape) != (B, num_frames, F):
+            raise ValueError(f"x0 must have shape {(B, num_frames, F)}, got {tuple(x0.shape)}")
+        if schedule is not None:
+            rows = [RowSchedule(num_step=r.num_step, guidance_scale=r.guidance_scale,
+                                t_start=float(t_start), t_end=float(t_end), t_shift=r.t_shift)
+                    for r in schedule[0]]
+            x1 = self.solver.sample_rows(x=x0, text_condition=text_condition,
+                                         speech_condition=speech_condition,
+                                         padding_mask=padding_mask, schedule=rows)
+        else:
+            x1 = self.solver.sample(x=x0, text_condition=text_condition,
+                                    speech_condition=speech_condition, padding_mask=padding_mask,
+                                    num_step=num_step, guidance_scale=guidance_scale,
+                                    t_start=float(t_start), t_end=float(t_end), t_shift=t_shift)
+        if keep_original:
+            x1, _ = eng.edit_gather(features, plan.lens, plan.table, plan.row_ptr, num_frames,
+                                    fill=x1)
+        return x1, new_lens, mask
+
+    def sample_intermediate(self, tokens: List[List[int]], features: torch.Tensor,
+                            features_lens: torch.Tensor, noise: torch.Tensor,
+                            speech_condition_mask: torch.Tensor, t_start: float, t_end: float,
+                            num_step: int = 1, guidance_scale=None):
+        """zipvoice.py:488-534: the solve from ``t_start`` to ``t_end`` with the speech condition
+        ``where(speech_condition_mask, 0, features)``.  The same path as ``sample_edit`` driven
+        by a mask: its runs of True inside a row's frames are spans with ``n = e - s``.
+        ``guidance_scale`` is a float or the reference's (batch, 1, 1) tensor.  Returns
+        (x_t_end (B, T, F), its lengths)."""
+        from .edit import mask_spans
+        lens = [int(v) for v in features_lens.tolist()]
+        m = speech_condition_mask.cpu().numpy()
+        spans = [mask_spans(m[b], lens[b]) for b in range(len(lens))]
+        x, x_lens, _ = self.sample_edit(
+            tokens=tokens, features=features, features_lens=features_lens, spans=spans,
+            num_step=num_step, guidance_scale=0.0 if guidance_scale is None else guidance_scale,
+            t_shift=1.0, t_start=t_start, t_end=t_end, x0=noise, keep_original=False)
+        return x, x_lens
+
 
 def per_row_schedule(B: int, **settings):
     """``sample``'s num_step / t_shift / guidance_scale / speed, each a scalar or a sequence of B
