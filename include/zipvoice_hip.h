@@ -22,6 +22,8 @@
  *                      (zipvoice/models/modules/solver.py:40-165)
  *   zv_euler_sample    EulerSolver.sample (zipvoice/models/modules/solver.py:182-240)
  *   zv_euler_sample_sched  EulerSolver.sample run per row with that row's own scalars (defined below)
+ *   zv_session_*       the same as a long-lived session that rows enter and leave between steps
+ *                      (continuous batching; defined below)
  *   zv_text_encode     ZipVoice.forward_text_embed (zipvoice/models/zipvoice.py:187-212,
  *                      ZipVoiceDialog override zipvoice/models/zipvoice_dialog.py:127-159)
  *   zv_text_condition  ZipVoice.forward_text_condition (zipvoice/models/zipvoice.py:214-251)
@@ -497,6 +499,50 @@ typedef struct {
 } zv_sched_check_args;
 int zv_sched_check(zv_sched_check_args* a);
 
+/* A session tick's host plan (host only, no GPU; what zv_session_step itself runs;
+ * tests/test_session_plan.py).  Slot b holds a row when rows[b].num_step > 0 (0 marks a free slot)
+ * and is active while done[b] < num_step.  The tick is zv_sched_plan's step rule over the active
+ * slots, in slot order, with slot b at its own index k = done[b] of its own grid: dec_t = ts_b[k],
+ * act_dt = ts_b[k + 1] - ts_b[k], the copy rule at the row's own t, the copies first; act_row and
+ * dec_src name slots.  *T_k = the longest lens[b] over the active slots (0 with none).  out as
+ * zv_sched_plan's: active, copies and the arrays of this tick; steps = the ticks left until every
+ * slot is done and total_rows = the decoder rows of those ticks, if nothing is admitted (with
+ * every done[b] = 0: zv_sched_plan's).  Rejected: slots outside [1, 32767], an occupied slot with
+ * done outside [0, num_step], lens outside [1, 2^30) or a schedule zv_sched_plan would reject. */
+int zv_session_plan(const zv_row_sched* rows, const int32_t* done, const int32_t* lens, int slots,
+                    int distill, zv_sched_plan_out* out, int32_t* T_k);
+
+/* The session's kernels, one launch at a time through the launch functions the engine calls (test
+ * infrastructure: tests/test_gpu_session_kernels.py; builds no engine; synchronous).  Outputs are
+ * canary-filled by the caller with `guard` guard rows (flat outputs: elements) at both ends.  Every
+ * index is checked on the host before the launch.  The slot buffers are (slots, max_frames, F).
+ *   ZV_SS_ADMIT   x, tc, sc: the request rows (n, T_io, Fx / Ft / Fs = Fx); slot / len (n) -> out, out_tc,
+ *                 out_sc (guard + slots * max_frames * F + guard) and mout (guard + slots * max_frames
+ *                 + guard): the named slots written whole, the others left
+ *   ZV_SS_RETIRE  x: the slot buffer; slot / len (n) -> out (guard + n * T_io * Fx + guard)
+ *   ZV_SS_BUILD_INPUT  x, tc, sc: the slot buffers; src / zero_text / zero_speech (N) -> oh / ol (guard +
+ *                 N * T_k + guard, ld); ol NULL: no lo half
+ *   ZV_SS_MASK_GATHER  mask: the slot buffer; src (N) -> mout (guard + N * T_k + guard)
+ *   ZV_SS_EULER   x: the slot buffer, v (N * T_k * Fx); row / dt / scale / cond / uncond (A, rows distinct)
+ *                 -> out (guard + slots * max_frames * Fx + guard), in place over x
+ * launch: {kind, kernel form (1: the quad kernel), grid.x, block threads, grid.y, 0...}. */
+enum zv_session_kind { ZV_SS_ADMIT = 0, ZV_SS_RETIRE = 1, ZV_SS_BUILD_INPUT = 2, ZV_SS_MASK_GATHER = 3,
+                       ZV_SS_EULER = 4 };
+typedef struct {
+  int kind, guard;
+  int slots, max_frames, n, T_io, T_k, N, A;
+  int Fx, Ft, Fs;
+  int64_t ld;
+  const int32_t* slot; const int32_t* len;
+  const int32_t* src; const uint8_t* zero_text; const uint8_t* zero_speech;
+  const float* x; const float* tc; const float* sc; const uint8_t* mask; const float* v;
+  const int32_t* row; const float* dt; const float* scale; const int32_t* cond; const int32_t* uncond;
+  float* out; float* out_tc; float* out_sc; uint16_t* oh; uint16_t* ol; uint8_t* mout;
+  int launch[8];
+  int num_cus;
+} zv_session_check_args;
+int zv_session_check(zv_session_check_args* a);
+
 /* Attention plan (host only, no GPU; test infrastructure): the LDS bytes of the fused
  * attention consumers a layer of sequence length L would launch — SelfAttention (sa_plo < 0:
  * the plain kernel, 0 / 1: the Toeplitz kernel without / with the table's lo half),
@@ -570,6 +616,56 @@ int zv_euler_sample_rows(zv_handle h, float* x, const float* text_c, const float
 int zv_euler_sample_sched(zv_handle h, float* x, const float* text_c, const float* speech_c,
                           const uint8_t* pad, int B, int T, const zv_row_sched* rows, void* stream);
 int zv_sched_stats(zv_handle h, int64_t* out);
+
+/* Solve session: continuous batching.  The scheduled solve as a long-lived object with `slots` row
+ * slots of `max_frames` frames: between any two decoder steps finished rows are taken out and waiting
+ * rows put into the free slots, and every row still integrates its own grid from its own step 0 with
+ * its own scalars, as EulerSolver.sample (solver.py:182-240) would integrate that row inside a padded
+ * batch: in a step it is padded with zeros to T_k, the longest row active in that step.  A row whose
+ * length is a multiple of every downsampling factor ends exactly as it would alone; any other row's
+ * last valid frames see the frames just past its end (SimpleDownsample groups ds frames, as the
+ * reference's), so its result depends on T_k, i.e. on which rows are in flight beside it, as a row of
+ * any padded batch depends on its padding.  The reference has no counterpart.  A row stays in its
+ * slot from admit to retire (the step's row map gathers the active slots into the decoder batch).
+ * Every entry is queued on `stream`; the host arrays are read before the call returns.  Use one
+ * stream per ENGINE: all sessions of an engine and its other entries (zv_euler_sample_sched, the
+ * velocity and solve calls) share the decoder workspace and one device table, and are ordered only
+ * by the stream.  The tables go up from the engine's pinned staging, and a warm admit / step / retire
+ * makes no host-blocking runtime call and no device-to-host read (the host knows which rows finish
+ * from the schedules alone) while at most 8 uploads (one per admit, step or retire) are queued and
+ * not yet run by the GPU; a host that runs further ahead makes the engine allocate one more pinned
+ * staging slot per upload in flight (a blocking hipHostMalloc, kept until the engine is destroyed).
+ *   create   the session owns x (slots, max_frames, Fx), text and speech conditions and the padding
+ *            mask, all zero, and sizes the decoder workspace for 2 * slots rows of max_frames (as
+ *            zv_reserve), so a step never moves it.  slots in [1, 32767].  The engine must outlive the
+ *            session: every entry of a session whose engine is gone returns an error.
+ *   admit    row i of x0 / speech_c (n, T_in, Fx) and text_c (n, T_in, feat_dim) (device) goes into
+ *            slot host_slots[i] with the schedule host_rows[i]: frames [0, len) copied, [len,
+ *            max_frames) zero in all three, pad[t] = t >= len.  One launch.  Rejected, with nothing
+ *            queued or changed: n < 1; a slot outside [0, slots), not free or named twice; len < 1, len
+ *            > T_in or len > max_frames; a schedule zv_sched_plan would reject.
+ *   step     one tick: every occupied slot with steps left runs one Euler step at its own step index
+ *            on its own grid (zv_session_plan below), at the decoder length T_k = the longest active
+ *            row, exactly; frames >= T_k of a slot and the other slots are not touched.  A session
+ *            whose rows were all admitted before the first tick runs zv_euler_sample_sched's decoder
+ *            batches at T = max len.  No active slot: nothing is launched.
+ *   retire   frames [0, len) of slot host_slots[i]'s x go to row i of out (n, T_out, Fx) (device), [len,
+ *            T_out) zero; the slot is then free and may be admitted again at once.  One launch.
+ *            Rejected: n < 1, a slot outside [0, slots), free, with steps left or named twice, T_out
+ *            shorter than a row.
+ *   state    host_steps_left [slots]: the steps each slot still has to run, -1 for a free slot; stats
+ *            [4]: ticks run, decoder rows launched, the sum over the ticks of decoder rows x T_k, the
+ *            last tick's T_k.  Either may be NULL. */
+typedef struct zv_session* zv_session_handle;
+zv_session_handle zv_session_create(zv_handle h, int slots, int max_frames);
+void zv_session_destroy(zv_session_handle s);
+int zv_session_admit(zv_session_handle s, int n, const int32_t* host_slots, const int32_t* host_lens,
+                     const zv_row_sched* host_rows, const float* x0, const float* text_c,
+                     const float* speech_c, int T_in, void* stream);
+int zv_session_step(zv_session_handle s, void* stream);
+int zv_session_retire(zv_session_handle s, int n, const int32_t* host_slots, float* out, int T_out,
+                      void* stream);
+int zv_session_state(zv_session_handle s, int32_t* host_steps_left, int64_t* stats);
 
 /* Text encoder (+ dialog speaker-turn embeddings).
  *  tokens: [B, S] int64 (already padded with pad_id, one extra pad per row);

@@ -1094,6 +1094,195 @@ int zv_sched_check(zv_sched_check_args* a) {
   ZV_API_END
 }
 
+// a session tick's host plan (session_tick, zv_session.inc: the function zv_engine::session_step runs)
+int zv_session_plan(const zv_row_sched* rows_, const int32_t* done, const int32_t* lens, int slots, int distill,
+                    zv_sched_plan_out* out, int32_t* T_k) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(rows_ && done && lens && out && T_k, "zv_session_plan: null argument");
+  ZV_REQUIRE(slots >= 1 && slots <= SESSION_MAX_SLOTS, "session: slots must be in [1, 32767]");
+  const SchedRow* rows = reinterpret_cast<const SchedRow*>(rows_);
+  std::vector<std::vector<float>> ts(slots);
+  int left = 0;
+  for (int b = 0; b < slots; ++b) {
+    if (rows[b].num_step == 0) continue;
+    const std::string at = "session: slot " + std::to_string(b) + ": ";
+    sched_check_row(rows[b], at);
+    ZV_REQUIRE(done[b] >= 0 && done[b] <= rows[b].num_step, at + "done outside [0, num_step]");
+    ZV_REQUIRE(lens[b] >= 1 && lens[b] < (1 << 30), at + "length outside [1, 2^30)");
+    ts[b] = solve_time_steps(rows[b].t_start, rows[b].t_end, rows[b].num_step, rows[b].t_shift);
+    left = std::max(left, rows[b].num_step - done[b]);
+  }
+  const SessTick tk = session_tick(rows, done, lens, ts, slots, distill != 0);
+  const SchedStep& st = tk.st;
+  out->steps = left;
+  out->total_rows = 0;
+  std::vector<int> d(done, done + slots);
+  for (int j = 0; j < left; ++j) {             // the ticks to come, if nothing is admitted
+    const SessTick nx = session_tick(rows, d.data(), lens, ts, slots, distill != 0);
+    out->total_rows += nx.st.U + nx.st.A;
+    for (const SchedUpd& u : nx.st.upd) d[u.row] += 1;
+  }
+  out->active = st.A;
+  out->copies = st.U;
+  *T_k = tk.Tk;
+  for (int j = 0; j < st.U + st.A; ++j) {
+    if (out->dec_src) out->dec_src[j] = st.src[j];
+    if (out->dec_zero_text) out->dec_zero_text[j] = st.zt[j];
+    if (out->dec_zero_speech) out->dec_zero_speech[j] = st.zs[j];
+    if (out->dec_t) out->dec_t[j] = st.t[j];
+  }
+  for (int i = 0; i < st.A; ++i) {
+    if (out->act_row) out->act_row[i] = st.upd[i].row;
+    if (out->act_dt) out->act_dt[i] = st.upd[i].dt;
+    if (out->act_scale) out->act_scale[i] = distill ? st.gdec[i] : (st.upd[i].vu < 0 ? 0.0f : st.upd[i].g);
+    if (out->act_cond) out->act_cond[i] = st.upd[i].vc;
+    if (out->act_uncond) out->act_uncond[i] = st.upd[i].vu;
+  }
+  ZV_API_END
+}
+
+// ---------------------------------------------------------------------------
+// zv_session_check: the solve session's kernels (admit, retire, and the strided operand build, mask
+// gather and Euler update) through the launch functions zv_engine::session_* calls, on host arrays
+// with canary-guarded outputs.  Every index is checked here before a launch.
+// ---------------------------------------------------------------------------
+int zv_session_check(zv_session_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && a->kind >= ZV_SS_ADMIT && a->kind <= ZV_SS_EULER && a->guard >= 0, "zv_session_check: bad arguments");
+  const int kind = a->kind, S = a->slots, maxT = a->max_frames, Tk = a->T_k, N = a->N;
+  const int Fx = a->Fx, Ft = a->Ft, Fs = a->Fs;
+  const size_t G = (size_t)a->guard;
+  ZV_REQUIRE(S > 0 && S <= SESSION_MAX_SLOTS && maxT > 0, "zv_session_check: slots in [1, 32767], max_frames > 0");
+  ZV_REQUIRE(kind == ZV_SS_MASK_GATHER || Fx > 0, "zv_session_check: Fx > 0");
+  ZV_REQUIRE((long)S * maxT * std::max(1, std::max(Fx, std::max(Ft, Fs))) < (1L << 30),
+             "zv_session_check: slot buffers under 2^30 values");
+  const size_t st = (size_t)S * maxT;
+  ChkDev dev;
+  hipStream_t s = nullptr;
+  EdgeLaunch ran{};
+  int gy = 0;
+  auto sync = [&] { ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize())); };
+  auto rows_tab = [&](int lim) {               // slot / len (n) -> device SessRow table
+    const int n = a->n;
+    ZV_REQUIRE(n > 0 && n <= S && a->slot && a->len, "zv_session_check: slot and len of 1 to `slots` rows");
+    std::vector<SessRow> t(n);
+    std::vector<char> seen(S, 0);
+    for (int i = 0; i < n; ++i) {
+      ZV_REQUIRE(a->slot[i] >= 0 && a->slot[i] < S && !seen[a->slot[i]], "zv_session_check: slots distinct and inside [0, slots)");
+      ZV_REQUIRE(a->len[i] >= 1 && a->len[i] <= lim && a->len[i] <= maxT, "zv_session_check: a length outside [1, min(T_io, max_frames)]");
+      seen[a->slot[i]] = 1;
+      t[i] = SessRow{a->slot[i], a->len[i]};
+    }
+    return dev.up(t.data(), (size_t)n);
+  };
+  auto row_map = [&](bool flags) {
+    ZV_REQUIRE(N > 0 && N <= 65535 && a->src && (!flags || (a->zero_text && a->zero_speech)),
+               "zv_session_check: src (and the zero flags) of N decoder rows");
+    ZV_REQUIRE(Tk > 0 && Tk <= maxT, "zv_session_check: T_k must be in [1, max_frames]");
+    std::vector<int> m(N);
+    for (int j = 0; j < N; ++j) {
+      ZV_REQUIRE(a->src[j] >= 0 && a->src[j] < S, "zv_session_check: a source slot outside [0, slots)");
+      m[j] = sched_map_entry(a->src[j], flags && a->zero_text[j] != 0, flags && a->zero_speech[j] != 0);
+    }
+    return dev.up(m.data(), (size_t)N);
+  };
+  if (kind == ZV_SS_ADMIT) {
+    const int n = a->n, Tin = a->T_io;
+    ZV_REQUIRE(Tin > 0 && Ft > 0 && Fs == Fx && a->x && a->tc && a->sc && a->out && a->out_tc && a->out_sc && a->mout,
+               "zv_session_check: ADMIT needs x, tc, sc, out, out_tc, out_sc, mout and Fs = Fx");
+    const SessRow* tab = rows_tab(Tin);
+    const float* x0 = dev.up(a->x, (size_t)n * Tin * Fx);
+    const float* tc0 = dev.up(a->tc, (size_t)n * Tin * Ft);
+    const float* sc0 = dev.up(a->sc, (size_t)n * Tin * Fx);
+    // (the guards are rounded up to 4 values on the device so a 16-byte aligned base stays one)
+    const size_t Gd = (G + 3) / 4 * 4;
+    std::vector<float> hx(Gd - G + st * Fx + 2 * G), ht(Gd - G + st * Ft + 2 * G);
+    std::vector<float> hs(hx.size());
+    memcpy(&hx[Gd - G], a->out, (st * Fx + 2 * G) * sizeof(float));
+    memcpy(&ht[Gd - G], a->out_tc, (st * Ft + 2 * G) * sizeof(float));
+    memcpy(&hs[Gd - G], a->out_sc, (st * Fx + 2 * G) * sizeof(float));
+    float* ox = dev.up(hx.data(), hx.size());
+    float* ot = dev.up(ht.data(), ht.size());
+    float* os = dev.up(hs.data(), hs.size());
+    uint8_t* om = dev.up(a->mout, st + 2 * G);
+    ran = launch_session_admit(x0, tc0, sc0, n, Tin, ox + Gd, ot + Gd, os + Gd, om + G, tab, maxT, Fx, Ft, s);
+    gy = n;
+    sync();
+    dev.down(a->out, ox + (Gd - G), st * Fx + 2 * G);
+    dev.down(a->out_tc, ot + (Gd - G), st * Ft + 2 * G);
+    dev.down(a->out_sc, os + (Gd - G), st * Fx + 2 * G);
+    dev.down(a->mout, om, st + 2 * G);
+  } else if (kind == ZV_SS_RETIRE) {
+    const int n = a->n, Tout = a->T_io;
+    ZV_REQUIRE(Tout > 0 && a->x && a->out, "zv_session_check: RETIRE needs x and out");
+    const SessRow* tab = rows_tab(Tout);
+    const float* x = dev.up(a->x, st * Fx);
+    const size_t Gd = (G + 3) / 4 * 4, no = (size_t)n * Tout * Fx + 2 * G;
+    std::vector<float> ho(Gd - G + no);
+    memcpy(&ho[Gd - G], a->out, no * sizeof(float));
+    float* o = dev.up(ho.data(), ho.size());
+    ran = launch_session_retire(x, o + Gd, n, Tout, tab, maxT, Fx, s);
+    gy = n;
+    sync();
+    dev.down(a->out, o + (Gd - G), no);
+  } else if (kind == ZV_SS_BUILD_INPUT) {
+    const int Fin = Fx + Ft + Fs;
+    ZV_REQUIRE(Ft > 0 && Fs > 0 && a->ld >= Fin && a->x && a->tc && a->sc && a->oh,
+               "zv_session_check: BUILD_INPUT needs x, tc, sc, oh, ld >= Fx + Ft + Fs");
+    const int* map = row_map(true);
+    const size_t n16 = ((size_t)N * Tk + 2 * G) * a->ld;
+    const float* x = dev.up(a->x, st * Fx);
+    const float* tc = dev.up(a->tc, st * Ft);
+    const float* sc = dev.up(a->sc, st * Fs);
+    uint16_t* oh = dev.up(a->oh, n16);
+    uint16_t* ol = a->ol ? dev.up(a->ol, n16) : nullptr;
+    ran = launch_session_build_input(x, tc, sc, reinterpret_cast<bf16*>(oh) + G * a->ld,
+                                     ol ? reinterpret_cast<bf16*>(ol) + G * a->ld : nullptr, a->ld, map, N, Tk, maxT,
+                                     Fx, Ft, Fs, s);
+    gy = N;
+    sync();
+    dev.down(a->oh, oh, n16);
+    if (ol) dev.down(a->ol, ol, n16);
+  } else if (kind == ZV_SS_MASK_GATHER) {
+    ZV_REQUIRE(a->mask && a->mout, "zv_session_check: MASK_GATHER needs the mask and mout");
+    const int* map = row_map(false);
+    const uint8_t* in = dev.up(a->mask, st);
+    uint8_t* o = dev.up(a->mout, (size_t)N * Tk + 2 * G);
+    ran = launch_session_gather_u8(in, o + G, map, N, Tk, maxT, s);
+    gy = N;
+    sync();
+    dev.down(a->mout, o, (size_t)N * Tk + 2 * G);
+  } else {
+    const int A = a->A;
+    ZV_REQUIRE(N > 0 && A > 0 && A <= S && Tk > 0 && Tk <= maxT && a->x && a->v && a->out && a->row && a->dt &&
+                   a->scale && a->cond && a->uncond,
+               "zv_session_check: EULER needs x, v, out and row / dt / scale / cond / uncond of A <= slots active rows");
+    std::vector<SchedUpd> upd(A);
+    std::vector<char> seen(S, 0);
+    for (int i = 0; i < A; ++i) {
+      ZV_REQUIRE(a->row[i] >= 0 && a->row[i] < S && !seen[a->row[i]], "zv_session_check: active slots distinct and inside [0, slots)");
+      ZV_REQUIRE(a->cond[i] >= 0 && a->cond[i] < N && a->uncond[i] >= -1 && a->uncond[i] < N,
+                 "zv_session_check: a velocity row outside [0, N)");
+      seen[a->row[i]] = 1;
+      upd[i] = SchedUpd{a->row[i], a->dt[i], a->scale[i], a->cond[i], a->uncond[i]};
+    }
+    const size_t n = st * Fx;
+    const float* v = dev.up(a->v, (size_t)N * Tk * Fx);
+    const SchedUpd* du = dev.up(upd.data(), (size_t)A);
+    std::vector<float> ho(a->out, a->out + n + 2 * G);
+    memcpy(&ho[G], a->x, n * sizeof(float));              // in place over x, as the engine's tick
+    float* o = dev.up(ho.data(), ho.size());
+    ran = launch_session_euler_update(o + G, v, du, A, (long)Tk * Fx, (long)maxT * Fx, s);
+    gy = A;
+    sync();
+    dev.down(a->out, o, n + 2 * G);
+  }
+  const int rec[8] = {kind, ran.form, ran.blocks, ran.threads, gy, 0, 0, 0};
+  memcpy(a->launch, rec, sizeof(rec));
+  a->num_cus = zv_num_cus();
+  ZV_API_END
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------

@@ -1212,6 +1212,44 @@ struct SchedPlan {
   std::vector<std::vector<float>> ts;        // per input row: its grid
   std::vector<SchedStep> steps;
 };
+// a row's settings, checked (`at` names the row in the message)
+static void sched_check_row(const SchedRow& r, const std::string& at) {
+  ZV_REQUIRE(r.num_step >= 1, at + "num_step must be at least 1");
+  ZV_REQUIRE(r.num_step <= 65536, at + "num_step above 65536");
+  ZV_REQUIRE(std::isfinite(r.t_start) && std::isfinite(r.t_end) && std::isfinite(r.t_shift) && std::isfinite(r.g),
+             at + "t_start, t_end, t_shift and guidance_scale must be finite");
+  ZV_REQUIRE(r.t_shift > 0.0f, at + "t_shift must be positive");
+}
+// One step's tables from its active rows, in order: each with its input row, its own t and next t and
+// its scale.  The scheduled solve gives every row the step's shared index k, a solve session
+// (zv_session.inc) the row's own.
+struct SchedAct { int row; float t, t_next, g; };
+static SchedStep sched_step(const std::vector<SchedAct>& act, bool distill) {
+  SchedStep st;
+  std::vector<CfgPlan> plan;
+  for (const SchedAct& a : act) {
+    plan.push_back(cfg_plan(a.t, a.g, false, false, distill));
+    if (plan.back().copies == 2) ++st.U;
+  }
+  st.A = (int)act.size();
+  const int N = st.U + st.A;
+  st.src.resize(N); st.zt.resize(N); st.zs.resize(N); st.t.resize(N);
+  st.upd.resize(st.A); st.gdec.resize(st.A);
+  int u = 0;
+  for (int i = 0; i < st.A; ++i) {
+    const int b = act[i].row, jc = st.U + i;
+    const float t = act[i].t;
+    st.src[jc] = b; st.zt[jc] = 0; st.zs[jc] = 0; st.t[jc] = t;
+    int ju = -1;
+    if (plan[i].copies == 2) {
+      ju = u++;
+      st.src[ju] = b; st.zt[ju] = 1; st.zs[ju] = (unsigned char)plan[i].zero_speech; st.t[ju] = t;
+    }
+    st.upd[i] = SchedUpd{b, act[i].t_next - t, plan[i].g, jc, ju};
+    st.gdec[i] = act[i].g;
+  }
+  return st;
+}
 static SchedPlan sched_plan(const SchedRow* rows, int B, bool distill) {
   ZV_REQUIRE(rows != nullptr, "scheduled solve: null schedule");
   ZV_REQUIRE(B >= 1 && B <= 32767, "scheduled solve: B must be in [1, 32767]");
@@ -1219,44 +1257,17 @@ static SchedPlan sched_plan(const SchedRow* rows, int B, bool distill) {
   p.ts.resize(B);
   for (int b = 0; b < B; ++b) {
     const SchedRow& r = rows[b];
-    const std::string at = "scheduled solve: row " + std::to_string(b) + ": ";
-    ZV_REQUIRE(r.num_step >= 1, at + "num_step must be at least 1");
-    ZV_REQUIRE(r.num_step <= 65536, at + "num_step above 65536");
-    ZV_REQUIRE(std::isfinite(r.t_start) && std::isfinite(r.t_end) && std::isfinite(r.t_shift) && std::isfinite(r.g),
-               at + "t_start, t_end, t_shift and guidance_scale must be finite");
-    ZV_REQUIRE(r.t_shift > 0.0f, at + "t_shift must be positive");
+    sched_check_row(r, "scheduled solve: row " + std::to_string(b) + ": ");
     p.ts[b] = solve_time_steps(r.t_start, r.t_end, r.num_step, r.t_shift);
     p.K = std::max(p.K, r.num_step);
   }
   p.steps.resize(p.K);
   for (int k = 0; k < p.K; ++k) {
-    SchedStep& st = p.steps[k];
-    std::vector<int> act;
-    std::vector<CfgPlan> plan;
+    std::vector<SchedAct> act;
     for (int b = 0; b < B; ++b)
-      if (k < rows[b].num_step) {
-        act.push_back(b);
-        plan.push_back(cfg_plan(p.ts[b][k], rows[b].g, false, false, distill));
-        if (plan.back().copies == 2) ++st.U;
-      }
-    st.A = (int)act.size();
-    const int N = st.U + st.A;
-    st.src.resize(N); st.zt.resize(N); st.zs.resize(N); st.t.resize(N);
-    st.upd.resize(st.A); st.gdec.resize(st.A);
-    int u = 0;
-    for (int i = 0; i < st.A; ++i) {
-      const int b = act[i], jc = st.U + i;
-      const float t = p.ts[b][k];
-      st.src[jc] = b; st.zt[jc] = 0; st.zs[jc] = 0; st.t[jc] = t;
-      int ju = -1;
-      if (plan[i].copies == 2) {
-        ju = u++;
-        st.src[ju] = b; st.zt[ju] = 1; st.zs[ju] = (unsigned char)plan[i].zero_speech; st.t[ju] = t;
-      }
-      st.upd[i] = SchedUpd{b, p.ts[b][k + 1] - t, plan[i].g, jc, ju};
-      st.gdec[i] = rows[b].g;
-    }
-    p.total_rows += N;
+      if (k < rows[b].num_step) act.push_back(SchedAct{b, p.ts[b][k], p.ts[b][k + 1], rows[b].g});
+    p.steps[k] = sched_step(act, distill);
+    p.total_rows += p.steps[k].U + p.steps[k].A;
   }
   return p;
 }

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -26,6 +27,7 @@
 #include "zv_ffn.inc"
 #include "zv_attn.inc"
 #include "zv_elem.inc"
+#include "zv_session.inc"
 #include "zv_flash.inc"
 #include "zv_flash2.inc"
 #include "zv_weights.inc"
@@ -216,6 +218,24 @@ static void release_stream_set(const StreamSet& set) {
 
 }  // namespace
 
+// A solve session's state (zv_session_*; the body is zv_engine::session_*, the kernels and the tick's
+// plan zv_session.inc).  Device: the slot buffers.  Host: per slot the row's schedule (num_step 0: the
+// slot is free), its grid, its length and the steps it has done, so which rows finish is known from
+// the schedules alone.
+struct zv_engine;
+struct zv_session {
+  zv_engine* eng = nullptr;                  // null once the engine is gone: every entry then fails
+  int slots = 0, maxT = 0;
+  DBuf x, tc, sc, pad;                       // (slots, maxT, Fx / Ft / Fx) floats, (slots, maxT) bytes
+  float *dx = nullptr, *dtc = nullptr, *dsc = nullptr;
+  uint8_t* dpad = nullptr;
+  std::vector<SchedRow> rows;
+  std::vector<std::vector<float>> ts;
+  std::vector<int> lens, done;
+  int64_t ticks = 0, dec_rows = 0, dec_row_frames = 0, last_T = 0;
+  ~zv_session();
+};
+
 // ===========================================================================
 struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fused-epilogue launches)
   zv_config cfg;
@@ -393,6 +413,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   }
 
   ~zv_engine() {
+    for (zv_session* q : sessions) q->eng = nullptr;   // a session left behind answers with an error
     drop_graphs();
     // the stream set outlives the engine: drain what this engine queued on it, then return it
     release_stream_set(streams);
@@ -1344,6 +1365,9 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   SchedSlot& sched_slot(size_t bytes) {
     for (SchedSlot& sl : sched_slots)
       if (sl.cap >= bytes && sl.idle()) return sl;
+    return sched_slot_new(bytes);
+  }
+  SchedSlot& sched_slot_new(size_t bytes) {
     SchedSlot sl;
     sl.cap = (size_t)round_up((long)std::max<size_t>(bytes, 64 * 1024), 4096);
     ZV_CHECK(ZV_BLOCKING(hipHostMalloc((void**)&sl.base, sl.cap + 64, hipHostMallocMapped | hipHostMallocPortable)));
@@ -1351,6 +1375,16 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     ZV_CHECK(ZV_BLOCKING(hipHostGetDevicePointer((void**)&sl.mark_dev, (void*)sl.base, 0)));
     sched_slots.push_back(sl);
     return sched_slots.back();
+  }
+  // the first `words` words of a slot's table to the device table, the completion mark behind them
+  // (the device table is sized for 64 KiB at least: tables of a few KB never move it)
+  unsigned* sched_send(SchedSlot& sl, size_t words, hipStream_t s) {
+    unsigned* dtab = sched_tab.get<unsigned>(std::max<size_t>(words, 16 * 1024));
+    ZV_CHECK(hipMemcpyAsync(dtab, sl.base + 16, words * 4, hipMemcpyHostToDevice, s));
+    sl.issued += 1;
+    hipLaunchKernelGGL(zv_mark_kernel, dim3(1), dim3(1), 0, s, sl.mark_dev, sl.issued);
+    ZV_LAUNCH_CHECK();
+    return dtab;
   }
 
   void euler_sample_sched(float* x, const float* tc, const float* sc, const uint8_t* pad, int B, int T,
@@ -1381,12 +1415,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
       memcpy(tab + off[k].upd, st.upd.data(), (size_t)st.A * sizeof(SchedUpd));
       memcpy(tab + off[k].g, st.gdec.data(), (size_t)st.A * 4);
     }
-    // (sized for 64 KiB at least: schedules of a few KB never move it)
-    unsigned* dtab = sched_tab.get<unsigned>(std::max<size_t>(words, 16 * 1024));
-    ZV_CHECK(hipMemcpyAsync(dtab, tab, words * 4, hipMemcpyHostToDevice, s));
-    sl.issued += 1;
-    hipLaunchKernelGGL(zv_mark_kernel, dim3(1), dim3(1), 0, s, sl.mark_dev, sl.issued);
-    ZV_LAUNCH_CHECK();
+    unsigned* dtab = sched_send(sl, words, s);
     sched_rows_run = 0;
     sched_steps_run = 0;
     for (int k = 0; k < plan.K; ++k) {
@@ -1412,6 +1441,150 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     }
   }
 
+  // ---------------------------------------------------------------- solve session
+  // zv_session_* bodies: continuous batching.  The scheduled solve with its state kept across calls: a
+  // row enters a free slot between any two steps (admit), every tick runs one Euler step of each
+  // active slot at the slot's own step index (session_tick, zv_session.inc: sched_step over the active
+  // slots), and a finished row is read out and its slot freed (retire).  Rows never move: the tick's
+  // row map gathers the active slots into the decoder batch at T_k = the longest active row.
+  // Every table (admit / retire rows, the tick's map | t | updates | scales) goes up through the
+  // scheduled solve's staging and device table; all of it is ordered on the caller's stream.  open
+  // sizes the decoder workspace for 2 * slots rows of max_frames and leaves SESSION_STAGING staging
+  // slots allocated, so a warm admit / tick / retire makes no host-blocking runtime call while no
+  // more uploads than that are in flight.
+  // posp_reuse is false on every tick.  The stack's key (stack<SPLIT>) is rewritten only where the
+  // host code of stack<> runs; a replayed graph of zv_euler_sample runs its captured launch_posp into
+  // the same buffers with its own L and leaves the key as it was, so between two calls the key does
+  // not say what the buffers hold.  (The reuse inside one solve is safe: nothing else runs in it.)
+  static constexpr size_t SESSION_STAGING = 8;
+  std::vector<zv_session*> sessions;
+
+  zv_session* session_open(int slots, int maxT) {
+    ZV_REQUIRE(slots >= 1 && slots <= SESSION_MAX_SLOTS, "session: slots must be in [1, 32767]");
+    ZV_REQUIRE(maxT >= 1, "session: max_frames must be at least 1");
+    const int Fx = stereo() ? 2 * cfg.feat_dim : cfg.feat_dim, Ft = cfg.feat_dim;
+    sess_check_sizes(maxT, Fx, Ft);
+    std::unique_ptr<zv_session> q(new zv_session());
+    q->slots = slots;
+    q->maxT = maxT;
+    const size_t nx = (size_t)slots * maxT * Fx, nt = (size_t)slots * maxT * Ft;
+    q->dx = q->x.get<float>(nx);               // (zero-filled: every slot starts as an all-zero row)
+    q->dtc = q->tc.get<float>(nt);
+    q->dsc = q->sc.get<float>(nx);
+    q->dpad = q->pad.get<uint8_t>((size_t)slots * maxT);
+    q->rows.assign(slots, SchedRow{0, 0.f, 0.f, 0.f, 0.f});
+    q->ts.resize(slots);
+    q->lens.assign(slots, 0);
+    q->done.assign(slots, 0);
+    // the workspace, as zv_reserve: one uncaptured guided velocity over every slot at max_frames, and
+    // the two buffers a tick takes that this velocity may not (distill has no copies)
+    const size_t nrows = (distill() ? 1 : 2) * (size_t)slots;
+    (void)ws_dec.mask2.get<uint8_t>(nrows * maxT);
+    (void)ws_dec.vout.get<float>(nrows * maxT * Fx);
+    DBuf bv;
+    float* v = bv.get<float>(nx);
+    velocity(0.25f, 1.0f, nullptr, false, q->dx, q->dtc, q->dsc, q->dpad, slots, maxT, v, false, 0.f, false, nullptr);
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    (void)sched_tab.get<unsigned>(16 * 1024);
+    while (sched_slots.size() < SESSION_STAGING) (void)sched_slot_new(0);
+    q->eng = this;
+    sessions.push_back(q.get());
+    return q.release();
+  }
+
+  void session_admit(zv_session& q, int n, const int32_t* slot, const int32_t* len, const SchedRow* rows,
+                     const float* x0, const float* tc0, const float* sc0, int T_in, hipStream_t s) {
+    ZV_REQUIRE(n >= 1, "session: admit takes at least one row");
+    ZV_REQUIRE(slot && len && rows && x0 && tc0 && sc0, "session: admit: null argument");
+    ZV_REQUIRE(T_in >= 1, "session: admit: T_in must be at least 1");
+    std::vector<char> seen(q.slots, 0);
+    for (int i = 0; i < n; ++i) {
+      const std::string at = "session: admit row " + std::to_string(i) + ": ";
+      ZV_REQUIRE(slot[i] >= 0 && slot[i] < q.slots, at + "slot outside [0, slots)");
+      ZV_REQUIRE(q.rows[slot[i]].num_step == 0, at + "slot is not free");
+      ZV_REQUIRE(!seen[slot[i]], at + "slot named twice");
+      seen[slot[i]] = 1;
+      ZV_REQUIRE(len[i] >= 1 && len[i] <= T_in && len[i] <= q.maxT, at + "length must be in [1, min(T_in, max_frames)]");
+      sched_check_row(rows[i], at);
+    }
+    const int Fx = stereo() ? 2 * cfg.feat_dim : cfg.feat_dim, Ft = cfg.feat_dim;
+    static_assert(sizeof(SessRow) == 8, "SessRow is two 4-byte words");
+    SchedSlot& sl = sched_slot((size_t)n * sizeof(SessRow));
+    SessRow* tab = reinterpret_cast<SessRow*>(sl.base + 16);
+    for (int i = 0; i < n; ++i) tab[i] = SessRow{slot[i], len[i]};
+    const SessRow* dtab = reinterpret_cast<const SessRow*>(sched_send(sl, 2 * (size_t)n, s));
+    launch_session_admit(x0, tc0, sc0, n, T_in, q.dx, q.dtc, q.dsc, q.dpad, dtab, q.maxT, Fx, Ft, s);
+    for (int i = 0; i < n; ++i) {
+      const int b = slot[i];
+      q.rows[b] = rows[i];
+      q.ts[b] = solve_time_steps(rows[i].t_start, rows[i].t_end, rows[i].num_step, rows[i].t_shift);
+      q.lens[b] = len[i];
+      q.done[b] = 0;
+    }
+  }
+
+  void session_step(zv_session& q, hipStream_t s) {
+    const SessTick tk = session_tick(q.rows.data(), q.done.data(), q.lens.data(), q.ts, q.slots, distill());
+    const SchedStep& st = tk.st;
+    if (st.A == 0) return;
+    const int N = st.U + st.A, Tk = tk.Tk;
+    const int Fx = stereo() ? 2 * cfg.feat_dim : cfg.feat_dim;
+    const int Ft = cfg.feat_dim, Fin = 2 * Fx + Ft;
+    const bool split = cfg.precision == ZV_FP32 || cfg.precision == ZV_MIXED;   // as build_xin
+    // the tick's table, as one step of the scheduled solve's: map [N] | t [N] | updates [A] | scales [A]
+    const size_t o_t = N, o_upd = 2 * (size_t)N, o_g = o_upd + 5 * (size_t)st.A, words = o_g + st.A;
+    SchedSlot& sl = sched_slot(words * 4);
+    unsigned* tab = sl.base + 16;
+    int* m = reinterpret_cast<int*>(tab);
+    for (int j = 0; j < N; ++j) m[j] = sched_map_entry(st.src[j], st.zt[j] != 0, st.zs[j] != 0);
+    memcpy(tab + o_t, st.t.data(), (size_t)N * 4);
+    memcpy(tab + o_upd, st.upd.data(), (size_t)st.A * sizeof(SchedUpd));
+    memcpy(tab + o_g, st.gdec.data(), (size_t)st.A * 4);
+    const unsigned* dtab = sched_send(sl, words, s);
+    const int* map = reinterpret_cast<const int*>(dtab);
+    Act xin = ws_dec.xin.get((long)N * Tk, round_up(Fin, 64), split);
+    launch_session_build_input(q.dx, q.dtc, q.dsc, xin.h, xin.l, xin.ld, map, N, Tk, q.maxT, Fx, Ft, Fx, s);
+    uint8_t* padN = ws_dec.mask2.get<uint8_t>((size_t)N * Tk);
+    launch_session_gather_u8(q.dpad, padN, map, N, Tk, q.maxT, s);
+    float* v = ws_dec.vout.get<float>((size_t)N * Tk * Fx);
+    const float* tv = reinterpret_cast<const float*>(dtab + o_t);
+    const float* gv = distill() ? reinterpret_cast<const float*>(dtab + o_g) : nullptr;
+    decoder(xin, Fin, N, Tk, padN, tv, gv, v, false, s);
+    launch_session_euler_update(q.dx, v, reinterpret_cast<const SchedUpd*>(dtab + o_upd), st.A, (long)Tk * Fx,
+                                (long)q.maxT * Fx, s);
+    for (const SchedUpd& u : st.upd) q.done[u.row] += 1;
+    q.ticks += 1;
+    q.dec_rows += N;
+    q.dec_row_frames += (int64_t)N * Tk;
+    q.last_T = Tk;
+  }
+
+  void session_retire(zv_session& q, int n, const int32_t* slot, float* out, int T_out, hipStream_t s) {
+    ZV_REQUIRE(n >= 1, "session: retire takes at least one row");
+    ZV_REQUIRE(slot && out, "session: retire: null argument");
+    std::vector<char> seen(q.slots, 0);
+    for (int i = 0; i < n; ++i) {
+      const std::string at = "session: retire row " + std::to_string(i) + ": ";
+      ZV_REQUIRE(slot[i] >= 0 && slot[i] < q.slots, at + "slot outside [0, slots)");
+      ZV_REQUIRE(q.rows[slot[i]].num_step > 0, at + "slot is free");
+      ZV_REQUIRE(q.done[slot[i]] == q.rows[slot[i]].num_step, at + "slot has steps left");
+      ZV_REQUIRE(!seen[slot[i]], at + "slot named twice");
+      seen[slot[i]] = 1;
+      ZV_REQUIRE(T_out >= q.lens[slot[i]], at + "T_out is shorter than the row");
+    }
+    const int Fx = stereo() ? 2 * cfg.feat_dim : cfg.feat_dim;
+    SchedSlot& sl = sched_slot((size_t)n * sizeof(SessRow));
+    SessRow* tab = reinterpret_cast<SessRow*>(sl.base + 16);
+    for (int i = 0; i < n; ++i) tab[i] = SessRow{slot[i], q.lens[slot[i]]};
+    const SessRow* dtab = reinterpret_cast<const SessRow*>(sched_send(sl, 2 * (size_t)n, s));
+    launch_session_retire(q.dx, out, n, T_out, dtab, q.maxT, Fx, s);
+    for (int i = 0; i < n; ++i) {
+      q.rows[slot[i]].num_step = 0;
+      q.done[slot[i]] = 0;
+      q.lens[slot[i]] = 0;
+    }
+  }
+
   void text_encode(const int64_t* tok, const uint8_t* pad, const int8_t* spk, int B, int S,
                    float* out, hipStream_t s) {
     const long n = (long)B * S;
@@ -1425,6 +1598,12 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     if (spk && spk_table) launch_spk_add(out, spk, spk_table, n, cfg.feat_dim, s);
   }
 };
+
+zv_session::~zv_session() {
+  if (!eng) return;
+  std::vector<zv_session*>& v = eng->sessions;
+  v.erase(std::remove(v.begin(), v.end(), this), v.end());
+}
 
 #include "zv_vocoder.inc"
 #include "zv_bigvgan.inc"
@@ -1692,6 +1871,55 @@ int zv_sched_stats(zv_handle h, int64_t* out) {
   ZV_REQUIRE(h != nullptr && out != nullptr, "zv_sched_stats: null argument");
   out[0] = h->sched_rows_run;
   out[1] = h->sched_steps_run;
+  ZV_API_END
+}
+
+// ---------------------------------------------------------------- solve session
+static zv_engine* session_engine(zv_session_handle q) {
+  ZV_REQUIRE(q != nullptr, "null session handle");
+  ZV_REQUIRE(q->eng != nullptr, "the solve session's engine has been destroyed");
+  check_ready(q->eng);
+  return q->eng;
+}
+
+zv_session_handle zv_session_create(zv_handle h, int slots, int max_frames) {
+  return api_create([&] {
+    check_ready(h);
+    return h->session_open(slots, max_frames);
+  });
+}
+
+void zv_session_destroy(zv_session_handle q) { delete q; }
+
+int zv_session_admit(zv_session_handle q, int n, const int32_t* host_slots, const int32_t* host_lens,
+                     const zv_row_sched* host_rows, const float* x0, const float* text_c, const float* speech_c,
+                     int T_in, void* stream) {
+  ZV_API_BEGIN
+  session_engine(q)->session_admit(*q, n, host_slots, host_lens, reinterpret_cast<const SchedRow*>(host_rows), x0,
+                                   text_c, speech_c, T_in, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int zv_session_step(zv_session_handle q, void* stream) {
+  ZV_API_BEGIN
+  session_engine(q)->session_step(*q, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int zv_session_retire(zv_session_handle q, int n, const int32_t* host_slots, float* out, int T_out, void* stream) {
+  ZV_API_BEGIN
+  session_engine(q)->session_retire(*q, n, host_slots, out, T_out, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int zv_session_state(zv_session_handle q, int32_t* host_steps_left, int64_t* stats) {
+  ZV_API_BEGIN
+  session_engine(q);
+  for (int b = 0; host_steps_left && b < q->slots; ++b)
+    host_steps_left[b] = q->rows[b].num_step > 0 ? q->rows[b].num_step - q->done[b] : -1;
+  if (stats) {
+    stats[0] = q->ticks; stats[1] = q->dec_rows; stats[2] = q->dec_row_frames; stats[3] = q->last_T;
+  }
   ZV_API_END
 }
 

@@ -148,6 +148,17 @@ class ZvSchedCheckArgs(ctypes.Structure):
         ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
 
 
+class ZvSessionCheckArgs(ctypes.Structure):
+    """zv_session_check_args (test infrastructure; tests/test_gpu_session_kernels.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kind", "guard", "slots", "max_frames", "n", "T_io", "T_k", "N", "A",
+                                            "Fx", "Ft", "Fs")] + [
+        ("ld", ctypes.c_int64)] + [
+        (n, ctypes.c_void_p) for n in ("slot", "len", "src", "zero_text", "zero_speech", "x", "tc", "sc", "mask", "v",
+                                       "row", "dt", "scale", "cond", "uncond", "out", "out_tc", "out_sc", "oh", "ol",
+                                       "mout")] + [
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+
+
 def row_schedule_array(schedule):
     """A sequence of rows with num_step / t_start / t_end / t_shift / guidance_scale attributes (or
     5-tuples in that order) as a ctypes array of zv_row_sched."""
@@ -212,6 +223,15 @@ SIGNATURES = {
     "zv_sched_stats": (_I, [_P, _P]),
     "zv_sched_plan": (_I, [_P, _I, _I, _I, ctypes.POINTER(ZvSchedPlanOut)]),
     "zv_sched_check": (_I, [ctypes.POINTER(ZvSchedCheckArgs)]),
+    # solve session (HipEngine.open_session, SolveSession)
+    "zv_session_create": (_P, [_P, _I, _I]),
+    "zv_session_destroy": (None, [_P]),
+    "zv_session_admit": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "zv_session_step": (_I, [_P, _P]),
+    "zv_session_retire": (_I, [_P, _I, _P, _P, _I, _P]),
+    "zv_session_state": (_I, [_P, _P, _P]),
+    "zv_session_plan": (_I, [_P, _P, _P, _I, _I, ctypes.POINTER(ZvSchedPlanOut), _P]),
+    "zv_session_check": (_I, [ctypes.POINTER(ZvSessionCheckArgs)]),
     "zv_text_encode": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "zv_text_condition": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P]),
     "zv_speech_condition": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
@@ -541,6 +561,11 @@ class HipEngine:
         self._check(self.lib.zv_sched_stats(self.h, ctypes.cast(c, ctypes.c_void_p)))
         return int(c[0]), int(c[1])
 
+    def open_session(self, slots: int, max_frames: int) -> "SolveSession":
+        """A solve session of ``slots`` rows of up to ``max_frames`` frames on this engine
+        (zv_session_create): continuous batching, rows admitted and retired between steps."""
+        return SolveSession(self, slots, max_frames)
+
     # ------------------------------------------------------------------ speech editing
     def _edit_handle(self):
         """The engine's zv_edit handle (device table + pinned staging), made on first use."""
@@ -655,3 +680,104 @@ class HipEngine:
         self._check(self.lib.zv_speech_condition(self.h, _ptr(pf), B, Tp, F, _ptr(pl), int(num_frames),
                                             _ptr(out), _stream()))
         return out
+
+
+class SolveSession:
+    """Continuous batching on one engine (zv_session_*): ``slots`` row slots of ``max_frames`` frames
+    that live across calls.  Between any two decoder steps finished rows are retired and waiting rows
+    admitted into the free slots; every row integrates its own grid from its own step 0 and ends as
+    ``EulerSolver.sample`` would leave it when run on that row alone.  All calls are queued on the
+    current stream; slot numbers, lengths and schedules are host values, and the host knows which rows
+    finish from the schedules alone (``steps_left``), so a warm admit / step / retire neither blocks
+    the host nor reads from the device.  The engine must outlive the session."""
+
+    def __init__(self, eng: "HipEngine", slots: int, max_frames: int):
+        self.eng, self.lib, self.device = eng, eng.lib, eng.device
+        self.slots, self.max_frames = int(slots), int(max_frames)
+        self.Fx = (2 if eng.cfg.stereo else 1) * eng.cfg.feat_dim
+        self._lens = [0] * self.slots
+        self.h = None
+        with torch.cuda.device(self.device):
+            self.h = self.lib.zv_session_create(eng.h, self.slots, self.max_frames)
+        if not self.h:
+            msg = self.lib.zv_last_error().decode()
+            raise ValueError(msg) if "session: " in msg else RuntimeError(f"zipvoice_hip: {msg}")
+
+    def close(self) -> None:
+        h = getattr(self, "h", None)
+        if h:
+            try:
+                torch.cuda.synchronize(self.device)
+            except Exception:
+                pass
+            self.lib.zv_session_destroy(h)
+            self.h = None
+
+    __del__ = close
+
+    def _check(self, rc: int):
+        if rc != 0 and "session: " in self.lib.zv_last_error().decode():
+            raise ValueError(self.lib.zv_last_error().decode())
+        _check(rc, self.lib)
+
+    def _handle(self):
+        if not self.h:
+            raise RuntimeError("the solve session is closed")
+        return self.h
+
+    def admit(self, slots, x0, text_c, speech_c, lens, schedule) -> None:
+        """Row i of ``x0`` / ``speech_c`` (n, T_in, Fx) and ``text_c`` (n, T_in, feat_dim) goes into the
+        free slot ``slots[i]`` with ``lens[i]`` valid frames and the settings ``schedule[i]``
+        (solver.RowSchedule or a 5-tuple, as ``euler_sample_sched``).  A bad request is a ValueError
+        and changes nothing."""
+        n, T_in, _ = x0.shape
+        if not (len(slots) == len(lens) == len(schedule) == n):
+            raise ValueError(f"admit: expected {n} slots, lens and schedule rows, got {len(slots)}, {len(lens)}, "
+                             f"{len(schedule)}")
+        x0 = self.eng._f32(x0, "x0", (n, T_in, self.Fx))
+        text_c = self.eng._f32(text_c, "text_condition", (n, T_in, self.eng.cfg.feat_dim))
+        speech_c = self.eng._f32(speech_c, "speech_condition", (n, T_in, self.Fx))
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32))
+        ln = np.ascontiguousarray(np.asarray(lens, dtype=np.int32))
+        rows = row_schedule_array(list(schedule))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.zv_session_admit(self._handle(), n, sl.ctypes.data, ln.ctypes.data,
+                                                  ctypes.cast(rows, ctypes.c_void_p), _ptr(x0), _ptr(text_c),
+                                                  _ptr(speech_c), T_in, _stream()))
+        for s, l in zip(sl.tolist(), ln.tolist()):
+            self._lens[s] = l
+
+    def step(self) -> None:
+        """One tick: every slot with steps left runs one Euler step at its own step index."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.zv_session_step(self._handle(), _stream()))
+
+    def retire(self, slots, T_out: Optional[int] = None) -> torch.Tensor:
+        """The finished rows of ``slots`` as (n, T_out, Fx), zero past each row's length (``T_out``
+        defaults to the longest of them); the slots are free afterwards."""
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32))
+        n = int(sl.size)
+        if T_out is None:
+            T_out = max([self._lens[s] for s in sl.tolist() if 0 <= s < self.slots] + [1])
+        out = torch.empty((n, int(T_out), self.Fx), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.zv_session_retire(self._handle(), n, sl.ctypes.data, _ptr(out), int(T_out),
+                                                   _stream()))
+        for s in sl.tolist():
+            self._lens[s] = 0
+        return out
+
+    def _state(self):
+        left = (ctypes.c_int32 * self.slots)()
+        st = (ctypes.c_int64 * 4)()
+        self._check(self.lib.zv_session_state(self._handle(), ctypes.cast(left, ctypes.c_void_p),
+                                              ctypes.cast(st, ctypes.c_void_p)))
+        return list(left), tuple(int(v) for v in st)
+
+    def steps_left(self) -> list:
+        """Per slot, the steps it still has to run; -1 for a free slot (host state, no GPU call)."""
+        return self._state()[0]
+
+    def stats(self) -> tuple:
+        """(ticks run, decoder rows launched, sum over the ticks of decoder rows x T_k, the last tick's T_k)."""
+        return self._state()[1]

@@ -1,0 +1,164 @@
+"""Continuous batching for serving: requests enter and leave a running solve between decoder steps.
+
+``ContinuousBatcher`` keeps one ``engine.SolveSession`` of ``max_rows`` slots.  Every ``step()`` retires
+the rows whose steps are done (prompt split, vocoder and RMS restore as one batch), admits queued
+requests into the free slots in arrival order (prompt features, text and speech conditions and the
+initial noise as one batch per admitted group) and runs one tick, in which every row in flight
+advances one Euler step on its own grid.  A request therefore waits at most one decoder step before it
+starts, whatever else is running, and the decoder batch stays as full as the queue allows.
+
+Each request ends as ``infer.generate_sentence`` would leave it with the same initial noise; two
+requests admitted together before the first tick run the decoder batches of ``infer.generate_batch``
+with per-item settings.  The reference has no counterpart.
+"""
+from __future__ import annotations
+
+import collections
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .common import predict_features_lens
+from .feature import compute_num_frames
+from .infer import _prepare_prompts, _resampler
+from .models import per_row_schedule, split_prompt
+from .noise import check_keys, seeded_normal
+
+
+class ContinuousBatcher:
+    """``submit`` queues a request and returns its ticket; ``step`` retires, admits and ticks, returning
+    ``[(ticket, wav (1, N))]`` of the requests that have finished; ``drain`` steps until nothing is left.
+    ``last_mel`` holds ``(ticket, mel (T_i, n_mels))`` of the rows the last retiring step returned, before
+    the vocoder.  ``max_frames`` bounds a request's prompt + generated frames."""
+
+    def __init__(self, model, vocoder, feature_extractor, max_rows: int, max_frames: int,
+                 target_rms: float = 0.1, feat_scale: float = 0.1, feat_bias: float = 0.0):
+        self.model, self.vocoder, self.fx = model, vocoder, feature_extractor
+        self.max_rows, self.max_frames = int(max_rows), int(max_frames)
+        self.target_rms, self.feat_scale, self.feat_bias = target_rms, feat_scale, feat_bias
+        self.session = model.solver.open_session(self.max_rows, self.max_frames)
+        self._queue = collections.deque()
+        self._rows = {}                       # slot -> (ticket, frames, prompt frames, prompt rms)
+        self._next_ticket = 0
+        self._done: List[Tuple[int, torch.Tensor]] = []      # retired, not yet returned by step()
+        self.last_mel: List[Tuple[int, torch.Tensor]] = []   # (ticket, mel (T_i, n_mels)) of the last retire
+
+    def close(self) -> None:
+        self.session.close()
+
+    def _frames(self, tokens, prompt_tokens, prompt_wav, prompt_sampling_rate, speed) -> Tuple[int, int]:
+        """(prompt frames, predicted frames of prompt + text) of a request, on the host."""
+        cfg = self.fx.config
+        n = int(np.asarray(prompt_wav).size) if not torch.is_tensor(prompt_wav) else int(prompt_wav.numel())
+        if prompt_sampling_rate is not None and int(prompt_sampling_rate) != cfg.sampling_rate:
+            n = _resampler(int(prompt_sampling_rate), cfg.sampling_rate).plan.out_len(n)
+        p = compute_num_frames(n, cfg.hop_length)
+        total = predict_features_lens(torch.tensor([p]), torch.tensor([len(prompt_tokens)]),
+                                      torch.tensor([len(tokens)]), float(speed))
+        return p, int(total[0])
+
+    def submit(self, tokens, prompt_tokens, prompt_wav, prompt_sampling_rate=None, num_step: int = 16,
+               guidance_scale: float = 1.0, speed: float = 1.0, t_shift: float = 0.5,
+               seed: Optional[int] = None) -> int:
+        """Queue one request; returns its ticket.  A request longer than ``max_frames`` is a ValueError."""
+        if seed is not None:
+            check_keys([seed], None, 1)
+        if int(num_step) < 1:
+            raise ValueError("num_step must be at least 1")
+        p, total = self._frames(tokens, prompt_tokens, prompt_wav, prompt_sampling_rate, speed)
+        if total > self.max_frames:
+            raise ValueError(f"request of {total} frames exceeds the batcher's max_frames ({self.max_frames})")
+        ticket = self._next_ticket
+        self._next_ticket += 1
+        item = (list(tokens), list(prompt_tokens), prompt_wav) + (
+            () if prompt_sampling_rate is None else (int(prompt_sampling_rate),))
+        self._queue.append((ticket, item, int(num_step), float(guidance_scale), float(speed), float(t_shift), seed,
+                            total))
+        return ticket
+
+    def pending(self) -> Tuple[int, int]:
+        """(queued, in-flight) request counts."""
+        return len(self._queue), len(self._rows)
+
+    @torch.inference_mode()
+    def _retire(self) -> List[Tuple[int, torch.Tensor]]:
+        left = self.session.steps_left()
+        slots = [s for s in sorted(self._rows) if left[s] == 0]
+        if not slots:
+            return []
+        dev = self.model.device
+        rows = [self._rows.pop(s) for s in slots]
+        x1 = self.session.retire(slots)
+        plens = torch.tensor([r[2] for r in rows], device=dev)
+        glens = torch.tensor([r[1] - r[2] for r in rows], device=dev)
+        pred, pred_lens, _ = split_prompt(x1, plens, glens, max(r[1] - r[2] for r in rows), max(r[2] for r in rows))
+        wav = self.vocoder.decode_features(pred, pred_lens, feat_scale=self.feat_scale, feat_bias=self.feat_bias,
+                                           clamp=True)
+        hop = self.vocoder.cfg.hop_length
+        out, self.last_mel = [], []
+        for i, (ticket, frames, p, rms) in enumerate(rows):
+            w = wav[i, :(frames - p) * hop]
+            if rms < self.target_rms:
+                w = w * rms / self.target_rms
+            out.append((ticket, w.unsqueeze(0)))
+            self.last_mel.append((ticket, pred[i, :frames - p]))
+        return out
+
+    @torch.inference_mode()
+    def _admit(self) -> None:
+        left = self.session.steps_left()
+        free = [s for s in range(self.max_rows) if left[s] < 0]
+        n = min(len(free), len(self._queue))
+        if n == 0:
+            return
+        # (the requests stay queued until the session has taken them: a failure below loses none)
+        reqs = [self._queue[i] for i in range(n)]
+        m, dev = self.model, self.model.device
+        items = [r[1] for r in reqs]
+        feats, nfr, rms, _ = _prepare_prompts(items, self.fx, self.target_rms, dev)
+        prompt_features = (feats + self.feat_bias) * self.feat_scale
+        schedule, speeds = per_row_schedule(n, num_step=[r[2] for r in reqs], guidance_scale=[r[3] for r in reqs],
+                                            speed=[r[4] for r in reqs], t_shift=[r[5] for r in reqs])
+        tc, pm = m.forward_text_inference_ratio_duration(
+            tokens=[it[0] for it in items], prompt_tokens=[it[1] for it in items], prompt_features_lens=nfr,
+            speed=torch.tensor(speeds, dtype=torch.float32, device=dev))
+        T_in = tc.shape[1]
+        sc = m.engine.speech_condition(prompt_features, nfr, T_in)
+        lens = (~pm).sum(-1).tolist()
+        long = [i for i, v in enumerate(lens) if v > self.max_frames]
+        if long:                                          # submit's host count was short: drop it, keep the rest queued
+            del self._queue[long[0]]
+            raise ValueError(f"request {reqs[long[0]][0]} has {lens[long[0]]} frames, more than max_frames "
+                             f"({self.max_frames}); it was dropped")
+        F = prompt_features.size(-1)
+        seeds = [r[6] for r in reqs]
+        if all(s is not None for s in seeds):
+            x0 = seeded_normal(seeds, (T_in, F), device=dev)
+        else:
+            x0 = torch.randn(n, T_in, F, device=dev)
+            keyed = [i for i, s in enumerate(seeds) if s is not None]
+            if keyed:
+                x0[keyed] = seeded_normal([seeds[i] for i in keyed], (T_in, F), device=dev)
+        slots = free[:n]
+        self.session.admit(slots, x0, tc, sc, lens, schedule)
+        for _ in range(n):
+            self._queue.popleft()
+        for s, r, frames, p, q in zip(slots, reqs, lens, nfr.tolist(), rms):
+            self._rows[s] = (r[0], frames, int(p), q)
+
+    def step(self) -> List[Tuple[int, torch.Tensor]]:
+        """Retire the finished rows, admit queued requests into the free slots, run one tick.
+        Returns [(ticket, wav (1, N) on the device)] of the requests finished by the previous ticks."""
+        self._done += self._retire()                      # (kept if the admission below raises: the next step returns them)
+        self._admit()
+        self.session.step()
+        done, self._done = self._done, []
+        return done
+
+    def drain(self) -> List[Tuple[int, torch.Tensor]]:
+        """Step until the queue and the session are empty; every remaining result, in finishing order."""
+        out = []
+        while self._queue or self._rows or self._done:
+            out += self.step()
+        return out

@@ -44,6 +44,11 @@ class EulerSolver:
         return self.model.engine.euler_sample_sched(x, text_condition, speech_condition, padding_mask,
                                                     list(schedule))
 
+    def open_session(self, slots: int, max_frames: int):
+        """A solve session for continuous batching (``engine.HipEngine.open_session``): rows are
+        admitted and retired between decoder steps, each integrated as ``sample_rows`` would."""
+        return self.model.engine.open_session(slots, max_frames)
+
     def sample(self, x: torch.Tensor, text_condition: torch.Tensor,
                speech_condition: torch.Tensor, padding_mask: torch.Tensor, num_step: int = 10,
                guidance_scale: Union[float, torch.Tensor] = 0.0, t_start: float = 0.0,
