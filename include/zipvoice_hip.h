@@ -110,6 +110,29 @@ int zv_reserve(zv_handle h, int max_batch, int max_frames);
 /* Total bytes of device memory held (weights + workspace). */
 int64_t zv_device_bytes(zv_handle h);
 
+/* Padding mode of the flow-matching decoder (no reference counterpart: the reference has the first
+ * behaviour only).  A decoder stack with downsampling factor ds > 1 sums groups of ds frames and
+ * right-pads the last group (SimpleDownsample, zipformer.py:887-913).
+ *   ZV_PAD_BATCH (default)  the group is padded as the reference pads the batch tensor: a masked
+ *                           row's last group takes in the frames past the row's end, so a row whose
+ *                           length is no multiple of ds depends on the padded length and on what
+ *                           lies there.
+ *   ZV_PAD_ROW              every row is downsampled as the reference downsamples it alone: with
+ *                           n_b = 1 + the last unmasked frame of row b (T for a fully masked row),
+ *                           out[b, i] = sum_k w[k] in[b, min(i ds + k, n_b - 1)] for every i < dL.
+ *                           A row's valid frames are then a function of its own valid frames only,
+ *                           and equal the reference's result for the row alone at T = n_b to rounding
+ *                           (not bitwise: kernel choices may still follow the batch's shape).
+ * The lengths come from the padding mask each decoder call receives, so every entry point that
+ * passes a mask follows the mode (zv_fm_decoder, zv_velocity, zv_euler_sample*, zv_session_step, the
+ * editing solves); a call without a mask, the text encoder (factor 1) and the vocoders are not
+ * affected.  zv_set_padding fails, changing nothing, for any other mode and while a session of the
+ * engine has an occupied slot (a row's solve never changes mode midway).  zv_get_padding returns the
+ * mode, -1 for a null handle. */
+enum zv_padding { ZV_PAD_BATCH = 0, ZV_PAD_ROW = 1 };
+int zv_set_padding(zv_handle h, int mode);
+int zv_get_padding(zv_handle h);
+
 /* Launch profiler (process-wide): when enabled, every GEMM / attention launch is
  * bracketed by HIP events on its stream.  zv_profile(0/1) also clears the log
  * (2 = on, with GEMM records keyed by shape);
@@ -322,6 +345,22 @@ typedef struct {
   int num_cus;
 } zv_stackedge_check_args;
 int zv_stackedge_check(zv_stackedge_check_args* a);
+
+/* The row padding mode's kernels as zv_engine launches them (test infrastructure: pins them against
+ * float64 in tests/test_gpu_padrow_ref.py; synchronous).  mask (B, L) bytes -> lens (guard + B + guard)
+ * int32, the rows' lengths (zv_row_len_kernel); x (B * L, C), w (ds) and those lengths -> out
+ * (guard + B * dL + guard, C), dL = ceil(L / ds) (zv_downsample_row_kernel).  lens and out are
+ * canary-filled by the caller.  launch: {0, length-kernel blocks, length-kernel threads, downsample
+ * blocks, downsample threads, 0...}. */
+typedef struct {
+  int B, L, C, ds, guard;
+  const uint8_t* mask; const float* x; const float* w;
+  int32_t* lens;
+  float* out;
+  int launch[8];
+  int num_cus;
+} zv_padrow_check_args;
+int zv_padrow_check(zv_padrow_check_args* a);
 
 /* The BigVGAN kernels one at a time, and one AMP step, through the launches and weight relayouts that
  * zv_bigvgan's finalize / decode use (test infrastructure: pins csrc/zv_bigvgan.inc, the implicit-conv

@@ -806,6 +806,34 @@ int zv_stackedge_check(zv_stackedge_check_args* a) {
   ZV_API_END
 }
 
+// zv_padrow_check: the row padding mode's two kernels through the engine's launches: the lengths of
+// a host mask, then the downsample of x clamped at them, both between canary guards
+int zv_padrow_check(zv_padrow_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && a->B > 0 && a->L > 0 && a->C > 0 && a->C % 4 == 0 && a->ds >= 1 && a->guard >= 0 && a->mask &&
+                 a->x && a->w && a->lens && a->out,
+             "zv_padrow_check: bad arguments");
+  const int B = a->B, L = a->L, C = a->C, ds = a->ds, G = a->guard;
+  const int dL = (L + ds - 1) / ds;
+  const long M = (long)B * L, Md = (long)B * dL;
+  ChkDev dev;
+  hipStream_t s = nullptr;
+  const uint8_t* mask = dev.up(a->mask, (size_t)M);
+  const float* in = dev.up(a->x, (size_t)M * C);
+  const float* w = dev.up(a->w, (size_t)ds);
+  int32_t* n = dev.up(a->lens, (size_t)B + 2 * G);
+  float* d = dev.up(a->out, (size_t)(Md + 2 * G) * C);
+  const EdgeLaunch r0 = launch_row_len(mask, n + G, B, L, s);
+  const EdgeLaunch r1 = launch_downsample_row(in, d + (size_t)G * C, n + G, B, L, dL, C, ds, w, s);
+  ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+  dev.down(a->lens, n, (size_t)B + 2 * G);
+  dev.down(a->out, d, (size_t)(Md + 2 * G) * C);
+  const int rec[8] = {0, r0.blocks, r0.threads, r1.blocks, r1.threads, 0, 0, 0};
+  memcpy(a->launch, rec, sizeof(rec));
+  a->num_cus = zv_num_cus();
+  ZV_API_END
+}
+
 // ---------------------------------------------------------------------------
 // zv_solve_check: the kernels around the decoder (operand build, Euler / CFG, mask copy, fill, timestep
 // embedding, the small fp32 linear, the positional projection, the text-side lookups) through the

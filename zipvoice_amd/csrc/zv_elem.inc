@@ -881,6 +881,45 @@ __global__ void zv_mask_downsample_kernel(const uint8_t* in, uint8_t* out, int B
   out[idx] = in[(long)b * L + (long)i * ds];
 }
 
+// ---- row padding mode (ZV_PAD_ROW; no reference counterpart: the reference pads the batch tensor) --
+// row lengths from the key padding mask: n[b] = 1 + the last l with pad[b, l] == 0, T for a row
+// without one.  One wave per row; lane j reads bytes j, j + 64, ... (coalesced) and keeps the largest
+// unmasked index it saw, then a butterfly max over the 64 lanes.  A maximum of integers: the result
+// does not depend on the order, so not on the launch geometry either.  Lane 0 writes.
+__global__ __launch_bounds__(64) void zv_row_len_kernel(const uint8_t* pad, int* n, int T) {
+  const uint8_t* row = pad + (long)blockIdx.x * T;
+  int last = -1;
+  for (int l = threadIdx.x; l < T; l += 64)
+    if (row[l] == 0) last = l;   // (l grows: the lane's last hit is its largest)
+  for (int off = 32; off > 0; off >>= 1) last = max(last, __shfl_xor(last, off, 64));
+  if (threadIdx.x == 0) n[blockIdx.x] = last < 0 ? T : last + 1;
+}
+
+// SimpleDownsample of every row as the reference runs it on that row alone at T = n[b]: the frames
+// past a row's end are its own last frame, out[b, i] = sum_k w[k] in[b, min(i ds + k, n[b] - 1)] for
+// every i < dL.  The form of zv_downsample_kernel (f32x4 per thread, C % 4 == 0, k = 0 .. ds - 1 in
+// order); n[b] = L gives that kernel's bits.  Host guarantees 1 <= n[b] <= L (zv_row_len_kernel).
+__global__ void zv_downsample_row_kernel(const float* in, float* out, const int* n, int B, int L,
+                                         int dL, int C, int ds, const float* w) {
+  const long total = (long)B * dL * C / 4;
+  for (long i4 = blockIdx.x * (long)blockDim.x + threadIdx.x; i4 < total;
+       i4 += (long)gridDim.x * blockDim.x) {
+    const long idx = i4 * 4;
+    const int c = (int)(idx % C);
+    const long bi = idx / C;
+    const int i = (int)(bi % dL);
+    const long b = bi / dL;
+    const int last = n[b] - 1;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < ds; ++k) {
+      int l = i * ds + k;
+      if (l > last) l = last;
+      acc += *reinterpret_cast<const f32x4*>(in + (b * L + l) * C + c) * w[k];
+    }
+    *reinterpret_cast<f32x4*>(out + idx) = acc;
+  }
+}
+
 // ---- the stack-boundary launches (zv_engine and zv_stackedge_check) ---------
 // each returns what it launched: kernel form (0 where there is one), grid blocks, block threads
 struct EdgeLaunch { int form, blocks, threads; };
@@ -889,6 +928,20 @@ static EdgeLaunch launch_downsample(const float* in, float* out, int B, int L, i
                                     const float* w, hipStream_t s) {
   const dim3 grid = grid1d((long)B * dL * C);
   hipLaunchKernelGGL(zv_downsample_kernel, grid, dim3(256), 0, s, in, out, B, L, dL, C, ds, w);
+  ZV_LAUNCH_CHECK();
+  return {0, (int)grid.x, 256};
+}
+// one 64-thread block per row, whatever B and T
+static EdgeLaunch launch_row_len(const uint8_t* pad, int* n, int B, int T, hipStream_t s) {
+  hipLaunchKernelGGL(zv_row_len_kernel, dim3((unsigned)B), dim3(64), 0, s, pad, n, T);
+  ZV_LAUNCH_CHECK();
+  return {0, B, 64};
+}
+// n (device, B entries in [1, L]): the table launch_row_len wrote
+static EdgeLaunch launch_downsample_row(const float* in, float* out, const int* n, int B, int L, int dL,
+                                        int C, int ds, const float* w, hipStream_t s) {
+  const dim3 grid = grid1d((long)B * dL * C);
+  hipLaunchKernelGGL(zv_downsample_row_kernel, grid, dim3(256), 0, s, in, out, n, B, L, dL, C, ds, w);
   ZV_LAUNCH_CHECK();
   return {0, (int)grid.x, 256};
 }

@@ -141,6 +141,9 @@ struct Workspace {
   // the fused FeedForward's persistent schedule (zv_ffn.inc): one 256 KiB tile slot per CU, one
   // flag word per CU (zero between launches) and the spin-timeout counter
   DBuf ffn_part, ffn_flag;
+  // the rows' lengths (int32 per decoder row, zv_row_len_kernel): taken by every masked pass with a
+  // downsampled stack, written and read in the row padding mode (ZV_PAD_ROW) only
+  DBuf rowlen;
   // per-stack positional projections, kept across the Euler steps of one solve (they depend on
   // the stack's length and weights only; Pass::posp_reuse)
   static constexpr int POSP_STACKS = 8;
@@ -152,7 +155,7 @@ struct Workspace {
     size_t s = 0;
     for (const DBuf& b : posPs) s += b.bytes;
     for (const DBuf* b : {&main, &dsrc, &cur, &temb0, &temb1, &tstack, &tvec, &gvec, &posP, &mask2,
-                          &maskds, &vout, &stats, &ffn_part, &ffn_flag})
+                          &maskds, &vout, &stats, &ffn_part, &ffn_flag, &rowlen})
       s += b->bytes;
     for (const ActBuf* b : {&xin, &main_a, &dsrc_a, &cur_a, &qkp, &W, &hidden, &na_y, &na_xt, &na_o,
                             &sa_vt, &sa_o, &glu, &dw, &emb, &cur8, &dwo})
@@ -299,6 +302,11 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   int glu_dw = 1;
   // exact-path counters of the second-generation consumers (FlashParams::fallback; zv_attn_fallbacks)
   unsigned* attn_fallback = nullptr;
+  // zv_set_padding: how the downsampled stacks right-pad a masked row's last group of ds frames.
+  // ZV_PAD_BATCH: with the batch tensor's frames past the row's end, as the reference does on the
+  // padded batch (zv_downsample_kernel); ZV_PAD_ROW: with the row's own last frame, as the reference
+  // does on the row alone (zv_row_len_kernel once per zipformer() call, zv_downsample_row_kernel)
+  int padding = ZV_PAD_BATCH;
 
   explicit zv_engine(const zv_config& c) : cfg(c) {
     auto envi = [](const char* k, int d) { const char* v = getenv(k); return v ? atoi(v) : d; };
@@ -329,10 +337,11 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     int B, T, N, has_pad;
     float g, t0, t1, shift;
     int cfg_mode;            // 0: scalar g; 1: per-row g with CFG; 2: per-row g without CFG
+    int padding;             // zv_padding: a solve captured in one mode is never replayed in the other
     unsigned long gen;
     bool operator<(const GraphKey& o) const {
-      return std::tie(B, T, N, has_pad, g, t0, t1, shift, cfg_mode, gen) <
-             std::tie(o.B, o.T, o.N, o.has_pad, o.g, o.t0, o.t1, o.shift, o.cfg_mode, o.gen);
+      return std::tie(B, T, N, has_pad, g, t0, t1, shift, cfg_mode, padding, gen) <
+             std::tie(o.B, o.T, o.N, o.has_pad, o.g, o.t0, o.t1, o.shift, o.cfg_mode, o.padding, o.gen);
     }
   };
   static constexpr size_t MAX_GRAPHS = 8, MAX_SEEN = 256;
@@ -1106,6 +1115,17 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
         small_linear(Z.stacks[si].time_emb, e0, E, N, tstack + si * (size_t)N * D, D, 1, nullptr,
                      s);
     }
+    // the rows' lengths, once for all downsampled stacks (the mask is at full rate).  The table is
+    // taken in either mode, so a reservation made in one sizes the other; without a mask there is
+    // no row end to honour and the batch kernel runs
+    const int* nrow = nullptr;
+    if (pad && std::any_of(Z.stacks.begin(), Z.stacks.end(), [](const StackW& S) { return S.ds > 1; })) {
+      int* n = ws.rowlen.get<int>((size_t)N);
+      if (padding == ZV_PAD_ROW) {
+        launch_row_len(pad, n, N, T, s);
+        nrow = n;
+      }
+    }
     for (size_t si = 0; si < Z.stacks.size(); ++si) {
       const StackW& S = Z.stacks[si];
       const float* te = tstack ? tstack + si * (size_t)N * D : nullptr;
@@ -1115,7 +1135,8 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
         const int dL = (T + S.ds - 1) / S.ds;
         float* d = ws.dsrc.get<float>((size_t)N * dL * D);
         Act d_a = ws.dsrc_a.get((long)N * dL, D, split || ios);
-        launch_downsample(main, d, N, T, dL, D, S.ds, S.ds_w, s);
+        if (nrow) launch_downsample_row(main, d, nrow, N, T, dL, D, S.ds, S.ds_w, s);
+        else launch_downsample(main, d, N, T, dL, D, S.ds, S.ds_w, s);
         uint8_t* pds = nullptr;
         if (pad) {
           pds = ws.maskds.get<uint8_t>((size_t)N * dL);
@@ -1289,7 +1310,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     uint8_t* spad = pad ? gpad.get<uint8_t>((size_t)B * T) : nullptr;
     float* sgr = grows ? ggrows.get<float>((size_t)B) : nullptr;
     GraphKey key{B, T, num_step, pad ? 1 : 0, grows ? 0.f : g, t0, t1, shift,
-                 grows ? (cfg_rows ? 1 : 2) : 0, g_ws_generation};
+                 grows ? (cfg_rows ? 1 : 2) : 0, padding, g_ws_generation};
     auto it = graphs.find(key);
     // seen-once shapes are keyed without the workspace generation: the warm-up run itself grows
     // the workspace, and the next call of the shape should capture, not warm up again
@@ -1599,6 +1620,11 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
   }
 };
 
+// whether any slot holds a row (admitted and not yet retired)
+static bool session_occupied(const zv_session& q) {
+  return std::any_of(q.rows.begin(), q.rows.end(), [](const SchedRow& r) { return r.num_step > 0; });
+}
+
 zv_session::~zv_session() {
   if (!eng) return;
   std::vector<zv_session*>& v = eng->sessions;
@@ -1720,6 +1746,19 @@ int zv_reserve(zv_handle h, int max_batch, int max_frames) {
   ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
   ZV_API_END
 }
+
+int zv_set_padding(zv_handle h, int mode) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(h != nullptr, "null engine handle");
+  ZV_REQUIRE(mode == ZV_PAD_BATCH || mode == ZV_PAD_ROW, "zv_set_padding: the mode is ZV_PAD_BATCH or ZV_PAD_ROW");
+  for (const zv_session* q : h->sessions)
+    ZV_REQUIRE(!session_occupied(*q), "zv_set_padding: a session of this engine has an occupied slot "
+                                      "(retire its rows first: a row's solve never changes mode midway)");
+  h->padding = mode;
+  ZV_API_END
+}
+
+int zv_get_padding(zv_handle h) { return h ? h->padding : -1; }
 
 int zv_attn_fallbacks(zv_handle h, int reset, int64_t* host_counts) {
   ZV_API_BEGIN

@@ -102,6 +102,13 @@ class ZvStackedgeCheckArgs(ctypes.Structure):
         ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
 
 
+class ZvPadrowCheckArgs(ctypes.Structure):
+    """zv_padrow_check_args (test infrastructure; tests/test_gpu_padrow_ref.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("B", "L", "C", "ds", "guard")] + [
+        (n, ctypes.c_void_p) for n in ("mask", "x", "w", "lens", "out")] + [
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+
+
 class ZvBigvganCheckArgs(ctypes.Structure):
     """zv_bigvgan_check_args (test infrastructure; tests/test_gpu_bigvgan_ref.py)."""
     _fields_ = [(n, ctypes.c_int) for n in ("kind", "split", "mode", "guard", "B", "Lmax", "Ls", "halo", "scale",
@@ -195,6 +202,8 @@ SIGNATURES = {
     "zv_finalize": (_I, [_P]),
     "zv_reserve": (_I, [_P, _I, _I]),
     "zv_device_bytes": (ctypes.c_int64, [_P]),
+    "zv_set_padding": (_I, [_P, _I]),
+    "zv_get_padding": (_I, [_P]),
     "zv_profile": (_I, [_I]),
     "zv_bench_gemm": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
     "zv_bench_fused_linear": (_I, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
@@ -203,6 +212,7 @@ SIGNATURES = {
     "zv_ffn_check": (_I, [ctypes.POINTER(ZvFfnCheckArgs)]),
     "zv_dwconv_check": (_I, [ctypes.POINTER(ZvDwconvCheckArgs)]),
     "zv_stackedge_check": (_I, [ctypes.POINTER(ZvStackedgeCheckArgs)]),
+    "zv_padrow_check": (_I, [ctypes.POINTER(ZvPadrowCheckArgs)]),
     "zv_bigvgan_check": (_I, [ctypes.POINTER(ZvBigvganCheckArgs)]),
     "zv_solve_check": (_I, [ctypes.POINTER(ZvSolveCheckArgs)]),
     "zv_time_steps": (_I, [_F, _F, _I, _F, _P]),
@@ -384,6 +394,17 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+# zv_padding
+PADDING_MODES = ("batch", "row")
+
+
+def padding_id(mode) -> int:
+    """The zv_padding value of a mode name; any other value is a ValueError."""
+    if not isinstance(mode, str) or mode not in PADDING_MODES:
+        raise ValueError(f"padding must be one of {list(PADDING_MODES)}, got {mode!r}")
+    return PADDING_MODES.index(mode)
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -455,6 +476,19 @@ class HipEngine:
 
     def device_bytes(self) -> int:
         return int(self.lib.zv_device_bytes(self.h))
+
+    @property
+    def padding(self) -> str:
+        """The decoder's padding mode (zv_get_padding / zv_set_padding): "batch" (default) pads a
+        downsampled stack's last group of frames from the padded batch tensor, as the reference does
+        on a batch; "row" pads every row with its own last frame, as the reference does on the row
+        alone, so a row's valid frames do not depend on its company or on what lies past its end.
+        Engine-wide; setting it raises while a solve session of the engine has an occupied slot."""
+        return PADDING_MODES[int(self.lib.zv_get_padding(self.h))]
+
+    @padding.setter
+    def padding(self, mode: str) -> None:
+        self._check(self.lib.zv_set_padding(self.h, padding_id(mode)))
 
     def attn_fallbacks(self, reset: bool = False) -> tuple:
         """(low, high, total) exact-path runs of the second-generation attention consumers since

@@ -203,7 +203,11 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
     prompts, or (tokens, prompt_tokens, prompt_wav, prompt_sampling_rate); prompts at
     other rates are resampled on the device, one batched call per distinct rate.
     Each output equals what ``generate_sentence`` would produce for that item with
-    the same initial noise (per-utterance lengths and masks throughout).
+    the same initial noise (per-utterance lengths and masks throughout).  To rounding that holds
+    in ``model.padding == "row"``, where every row is integrated as it would be alone; in the
+    default ``"batch"`` mode it holds for the items whose total length is the batch's longest or a
+    multiple of 4 (the decoder's largest downsampling factor), and the others end as the
+    reference's batched ``sample`` leaves them (``DESIGN.md`` section 3, "Padding").
 
     ``seeds`` (one int in [0, 2^64) per item; not together with ``x0``) keys every item's
     initial noise to the item (``noise.seeded_normal``, stream 0): item i then starts from the

@@ -24,7 +24,7 @@ import torch
 
 from .common import make_pad_mask, pad_labels, predict_features_lens, speaker_turn_indices
 from .config import ModelConfig
-from .engine import HipEngine
+from .engine import HipEngine, padding_id
 from .noise import check_keys, seeded_normal
 from .solver import DistillEulerSolver, EulerSolver, RowSchedule
 from .weights import check_state_dict, load_checkpoint_state_dict, synthetic_state_dict
@@ -46,7 +46,7 @@ class ZipVoice:
                  time_embed_dim: int = 192, text_embed_dim: int = 192, query_head_dim: int = 32,
                  value_head_dim: int = 12, pos_head_dim: int = 4, pos_dim: int = 48,
                  feat_dim: int = 100, vocab_size: int = 26, pad_id: int = 0,
-                 precision: str = "fp32", **extra):
+                 precision: str = "fp32", padding: str = "batch", **extra):
         self.cfg = ModelConfig(
             fm_decoder_downsampling_factor=list(fm_decoder_downsampling_factor),
             fm_decoder_num_layers=list(fm_decoder_num_layers),
@@ -69,6 +69,8 @@ class ZipVoice:
         self.text_embed_dim = text_embed_dim
         self.pad_id = pad_id
         self.precision = precision
+        padding_id(padding)                    # (ValueError for anything but "batch" / "row")
+        self._padding = padding                # remembered until the engine exists, and across rebuilds
         self._state: Optional[Dict[str, np.ndarray]] = None
         self.engine: Optional[HipEngine] = None
         self.device = torch.device("cpu")
@@ -103,7 +105,25 @@ class ZipVoice:
         if self._state is None:
             raise RuntimeError("load_state_dict() must be called before moving to a GPU")
         self.engine = HipEngine(self.cfg, self._state, precision=self.precision, device=device)
+        self.engine.padding = self._padding
         self.device = self.engine.device
+
+    @property
+    def padding(self) -> str:
+        """The decoder's padding mode, engine-wide (``HipEngine.padding``).  ``"batch"`` (default):
+        the reference's behaviour on a padded batch, where a row whose length is no multiple of the
+        decoder's downsampling factors depends on the padded length and on what lies past its end.
+        ``"row"``: every row is integrated as it would be alone at its own length.  Every entry that
+        runs the decoder follows it (``sample``, ``sample_edit``, ``sample_intermediate``,
+        ``forward_fm_decoder``, the ``infer`` / ``longform`` / ``edit`` generators)."""
+        return self._padding
+
+    @padding.setter
+    def padding(self, mode: str) -> None:
+        padding_id(mode)
+        if self.engine is not None:
+            self.engine.padding = mode
+        self._padding = mode
 
     def to(self, device):
         device = torch.device(device)
@@ -418,7 +438,7 @@ MODEL_CLASSES = {"zipvoice": ZipVoice, "zipvoice_distill": ZipVoiceDistill,
                  "zipvoice_dialog_stereo": ZipVoiceDialogStereo}
 
 
-def build_model(cfg: ModelConfig, precision: str = "fp32"):
+def build_model(cfg: ModelConfig, precision: str = "fp32", padding: str = "batch"):
     cls = MODEL_CLASSES[cfg.variant]
     kw = cfg.model_kwargs()
-    return cls(**kw, precision=precision)
+    return cls(**kw, precision=precision, padding=padding)

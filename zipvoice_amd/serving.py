@@ -30,11 +30,20 @@ class ContinuousBatcher:
     """``submit`` queues a request and returns its ticket; ``step`` retires, admits and ticks, returning
     ``[(ticket, wav (1, N))]`` of the requests that have finished; ``drain`` steps until nothing is left.
     ``last_mel`` holds ``(ticket, mel (T_i, n_mels))`` of the rows the last retiring step returned, before
-    the vocoder.  ``max_frames`` bounds a request's prompt + generated frames."""
+    the vocoder.  ``max_frames`` bounds a request's prompt + generated frames.
+
+    ``padding`` (``None``: leave the model's mode; ``"batch"`` / ``"row"``: set ``model.padding``, which is
+    engine-wide, so it also holds for every other call on the model).  In ``"row"`` mode a request's
+    features depend on its own frames only: the same request and seed give the same result, to rounding,
+    whatever else is in flight.  In ``"batch"`` mode a row whose length is no multiple of 4 ends
+    differently depending on the tick's length (``DESIGN.md`` section 3, "Padding")."""
 
     def __init__(self, model, vocoder, feature_extractor, max_rows: int, max_frames: int,
-                 target_rms: float = 0.1, feat_scale: float = 0.1, feat_bias: float = 0.0):
+                 target_rms: float = 0.1, feat_scale: float = 0.1, feat_bias: float = 0.0,
+                 padding: Optional[str] = None):
         self.model, self.vocoder, self.fx = model, vocoder, feature_extractor
+        if padding is not None:               # engine-wide: every other user of the model follows it
+            model.padding = padding
         self.max_rows, self.max_frames = int(max_rows), int(max_frames)
         self.target_rms, self.feat_scale, self.feat_bias = target_rms, feat_scale, feat_bias
         self.session = model.solver.open_session(self.max_rows, self.max_frames)
