@@ -1076,6 +1076,67 @@ int zv_edit_splice(zv_edit_handle h, const float* orig, int64_t ld, const int32_
                    int64_t out_cols, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Voice store: a prompt prepared once and kept on the device (zipvoice_amd/voices.py VoiceStore;
+ * the (tokens, Voice) items of generate_batch and ContinuousBatcher.submit(voice=...)).  NO
+ * reference counterpart: the reference normalises the prompt of every sentence on the host
+ * (zipvoice/bin/infer_zipvoice.py:340-342) and restores the level on the host (:399-400), so
+ * the behaviour is defined here (tests/voice_ref.py restates it in numpy).  fp32 data, no
+ * atomics, every output element written exactly once: results are bitwise reproducible.
+ *
+ * zv_prompt_rms.  wav [B, ld] device fp32, lens [B] device int32, host_lens [B] the same
+ * lengths as a HOST array (checked before the launch: each in [1, ld]; the kernel reads the
+ * device copy, cut to [0, ld]).  Row b: one workgroup of 256 lanes; lane j adds
+ * (double)x[i] * (double)x[i] for i = j, j + 256, ... < len in rising i, starting from 0; the
+ * 256 partial sums p are folded in place, for w = 128, 64, ..., 1: p[j] += p[j + w] for every
+ * j < w; then
+ *   rms[b] = (float) sqrt(p[0] / (double)len)
+ * in float64 with one rounding to fp32 at the end.  The order depends on len alone: a row's
+ * bits do not depend on B, on ld, or on what columns [len, ld) hold (they are not read).  With
+ * t = target as fp32 and IEEE fp32 divisions,
+ *   gain_in[b]  = rms[b] < t ? t / rms[b] : 1      (the factor of :340-342)
+ *   gain_out[b] = rms[b] < t ? rms[b] / t : 1      (the factor of :399-400)
+ * rms, gain_in and gain_out are [B] device fp32; nothing comes back to the host.  Stateless, one
+ * launch on `stream`, no host-blocking runtime call.  Rejected: B outside [1, 65535], ld
+ * outside [1, 2^31), target <= 0, a null array, a length outside [1, ld] (so a row of length 0).
+ *
+ * zv_prompt_scale.  out [B, ld] device (may be wav itself), rms [B] device as written by
+ * zv_prompt_rms.  For rows with rms[b] < t: out[b, i] = (wav[b, i] * t) / rms[b] for i < len,
+ * two fp32 operations with an IEEE division: the expression infer._prompt_rms_normalise
+ * evaluates, so for the same fp32 rms the samples are bitwise the host path's.  Other rows are
+ * bitwise copies.  Columns [len, ld) are written as zeros (wav is not read there).  ld % 4 == 0
+ * with 16-byte aligned wav and out moves four samples per thread as 16-byte loads and stores,
+ * anything else one sample per thread.  Rejections as zv_prompt_rms.
+ *
+ * zv_voice_gather.  pool [pool_rows, F] device fp32 holds the stored features of the voices,
+ * each a range of whole rows; host_table [n, 2] int32 HOST rows {offset, frames}; out
+ * [n, T, F] device.  Row r of out receives pool rows [offset_r, offset_r + frames_r) as one
+ * flat bitwise copy of frames_r * F values, then zeros up to T * F: what zv_speech_condition
+ * produces from the padded prompt batch, without the padded batch.  The same range may be named
+ * by several rows.  With gains_pool [pool_rows] and gains_out [n] (both or neither),
+ * gains_out[r] = gains_pool[offset_r]: a voice's gain lives at the index of its first row.  F % 4
+ * == 0 with 16-byte aligned pool and out moves four values per thread (16-byte loads and
+ * stores), anything else one value per thread.  The table is validated completely before
+ * anything is queued (0 <= offset, 1 <= frames <= T, offset + frames <= pool_rows; the error
+ * names the row and launches nothing), then travels through the handle's pinned staging to the
+ * handle's device table on `stream`, as the tables of zv_edit_*: calls queued back to back
+ * each keep their own table until it has been read, calls on one handle are ordered by the
+ * caller, and a warm call neither allocates nor makes a host-blocking runtime call
+ * (zv_voice_device_bytes: the device table, 0 before the first call).  Rejected: a null handle,
+ * pool, table or out, n outside [1, 65535], pool_rows, F or T < 1, T * F >= 2^30, one of the
+ * gains arrays without the other, a table that breaks a rule above.
+ * ---------------------------------------------------------------------- */
+int zv_prompt_rms(const float* wav, int64_t ld, const int32_t* lens, const int32_t* host_lens, int B, float target,
+                  float* rms, float* gain_in, float* gain_out, void* stream);
+int zv_prompt_scale(const float* wav, int64_t ld, const int32_t* lens, const int32_t* host_lens, const float* rms, int B,
+                    float target, float* out, void* stream);
+typedef struct zv_voice* zv_voice_handle;
+zv_voice_handle zv_voice_create(void);
+void zv_voice_destroy(zv_voice_handle h);
+int64_t zv_voice_device_bytes(zv_voice_handle h);
+int zv_voice_gather(zv_voice_handle h, const float* pool, int pool_rows, int F, const int32_t* host_table, int n, int T,
+                    float* out, const float* gains_pool, float* gains_out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Seeded noise: standard normals that are a pure function of (seed, stream, element
  * index), drawn on the device (zipvoice_amd/noise.py seeded_normal; the seeds / seed
  * arguments of sample, generate_sentence, generate_batch, generate_long and

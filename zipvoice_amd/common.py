@@ -9,12 +9,21 @@ from typing import List
 import torch
 
 
+def to_device(t: torch.Tensor, device=None) -> torch.Tensor:
+    """A host tensor on ``device``.  To a GPU it goes through pinned memory as an asynchronous copy
+    on the current stream, so the host does not wait for the work queued there (a copy from
+    pageable memory does); the values are the same either way."""
+    if device is None or torch.device(device).type != "cuda" or t.is_cuda:
+        return t if device is None else t.to(device)
+    return t.pin_memory().to(device, non_blocking=True)
+
+
 def pad_labels(y: List[List[int]], pad_id: int, device=None) -> torch.Tensor:
     """common.py:255-268: append ONE pad to every row, then pad to the max length."""
     y = [list(t) + [pad_id] for t in y]
     n = max(len(t) for t in y)
     y = [t + [pad_id] * (n - len(t)) for t in y]
-    return torch.tensor(y, dtype=torch.int64, device=device)
+    return to_device(torch.tensor(y, dtype=torch.int64), device)
 
 
 def make_pad_mask(lengths: torch.Tensor, max_len: int = 0) -> torch.Tensor:

@@ -1637,6 +1637,7 @@ zv_session::~zv_session() {
 #include "zv_resample.inc"
 #include "zv_wavjoin.inc"
 #include "zv_edit.inc"
+#include "zv_voice.inc"
 
 // ===========================================================================
 // C ABI
@@ -2236,6 +2237,49 @@ int zv_edit_splice(zv_edit_handle h, const float* orig, int64_t ld, const int32_
   ZV_REQUIRE(host_table || host_row_ptr[B] == 0, "zv_edit_splice: null table");
   h->splice(orig, (long)ld, host_lens, gen, (long)ldg, host_gen_lens, B, C, host_table, host_row_ptr, host_gains,
             fade, out, (long)out_ld, (long)out_cols, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int zv_prompt_rms(const float* wav, int64_t ld, const int32_t* lens, const int32_t* host_lens, int B, float target,
+                  float* rms, float* gain_in, float* gain_out, void* stream) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(B >= 1 && B <= 65535 && ld >= 1 && ld <= 0x7fffffffLL, "zv_prompt_rms: B in [1, 65535], ld in [1, 2^31)");
+  ZV_REQUIRE(wav && lens && host_lens && rms && gain_in && gain_out, "zv_prompt_rms: null argument");
+  ZV_REQUIRE(target > 0.f, "zv_prompt_rms: target must be positive");
+  voice_check_lens(host_lens, B, (long)ld, "zv_prompt_rms");
+  launch_prompt_rms(wav, (long)ld, lens, B, target, rms, gain_in, gain_out, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int zv_prompt_scale(const float* wav, int64_t ld, const int32_t* lens, const int32_t* host_lens, const float* rms, int B,
+                    float target, float* out, void* stream) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(B >= 1 && B <= 65535 && ld >= 1 && ld <= 0x7fffffffLL, "zv_prompt_scale: B in [1, 65535], ld in [1, 2^31)");
+  ZV_REQUIRE(wav && lens && host_lens && rms && out, "zv_prompt_scale: null argument");
+  ZV_REQUIRE(target > 0.f, "zv_prompt_scale: target must be positive");
+  voice_check_lens(host_lens, B, (long)ld, "zv_prompt_scale");
+  launch_prompt_scale(wav, (long)ld, lens, rms, B, target, out, (hipStream_t)stream);
+  ZV_API_END
+}
+
+zv_voice_handle zv_voice_create(void) {
+  return api_create([&] { return new zv_voice(); });
+}
+
+void zv_voice_destroy(zv_voice_handle h) { delete h; }
+
+int64_t zv_voice_device_bytes(zv_voice_handle h) { return h ? (int64_t)h->stage.device_bytes() : 0; }
+
+int zv_voice_gather(zv_voice_handle h, const float* pool, int pool_rows, int F, const int32_t* host_table, int n, int T,
+                    float* out, const float* gains_pool, float* gains_out, void* stream) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(h != nullptr, "null voice handle");
+  ZV_REQUIRE(n >= 1 && n <= 65535, "voice table: n must be in [1, 65535]");
+  ZV_REQUIRE(pool_rows >= 1 && F >= 1 && T >= 1 && (int64_t)T * F < ((int64_t)1 << 30),
+             "zv_voice_gather: pool_rows, F and T at least 1, T * F under 2^30");
+  ZV_REQUIRE(pool && host_table && out, "zv_voice_gather: null argument");
+  ZV_REQUIRE((gains_pool != nullptr) == (gains_out != nullptr), "zv_voice_gather: gains_pool and gains_out go together");
+  h->gather(pool, pool_rows, F, host_table, n, T, out, gains_pool, gains_out, (hipStream_t)stream);
   ZV_API_END
 }
 

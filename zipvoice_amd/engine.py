@@ -290,6 +290,13 @@ SIGNATURES = {
     "zv_edit_gather": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     "zv_edit_splice": (_I, [_P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _I, _I, _P, _P, _P, _I,
                             _P, ctypes.c_int64, ctypes.c_int64, _P]),
+    # voice store (zipvoice_amd/voices.py)
+    "zv_prompt_rms": (_I, [_P, ctypes.c_int64, _P, _P, _I, _F, _P, _P, _P, _P]),
+    "zv_prompt_scale": (_I, [_P, ctypes.c_int64, _P, _P, _P, _I, _F, _P, _P]),
+    "zv_voice_create": (_P, []),
+    "zv_voice_destroy": (None, [_P]),
+    "zv_voice_device_bytes": (ctypes.c_int64, [_P]),
+    "zv_voice_gather": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P]),
     # seeded noise (zipvoice_amd/noise.py)
     "zv_noise_normal": (_I, [_P, _P, _I, ctypes.c_int64, ctypes.c_int64, _P, _P]),
     "zv_noise_check": (_I, [ctypes.POINTER(ZvNoiseCheckArgs)]),

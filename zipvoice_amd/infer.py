@@ -21,6 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .common import to_device
 from .models import per_row_schedule
 from .noise import check_keys
 
@@ -222,7 +223,12 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
     ``longform.WavJoiner.trim`` (``joiner``, default ``WavJoiner()``), which drops the
     silence at its edges and cuts over-long pauses inside, with the RMS restore folded in
     as the row's gain; each waveform is then (1, N_i) and ``wav_seconds`` / ``rtf`` use
-    the trimmed lengths."""
+    the trimmed lengths.
+
+    Items ``(tokens, Voice)`` (``voices.VoiceStore.register``; all of one store, not mixed with wav
+    items: a ValueError) take the prompt features from the store and its ``target_rms`` / ``feat_scale``
+    / ``feat_bias``: no prompt is resampled, measured or framed, and the RMS restore is one multiply by
+    the store's gains on the device (the row's gain of ``WavJoiner.trim`` under ``remove_long_sil``)."""
     dev = model.device
     B = len(items)
     if seeds is not None:
@@ -231,17 +237,31 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
         seeds, _ = check_keys(seeds, None, B)
     # (per-item settings are checked for their length here, before any GPU work)
     per_row_schedule(B, num_step=num_step, t_shift=t_shift, guidance_scale=guidance_scale, speed=speed)
-    feats, nfr, rms, _ = _prepare_prompts(items, feature_extractor, target_rms, dev)
-    prompt_features = (feats + feat_bias) * feat_scale
+    from .voices import Voice
+    by_voice = [len(it) == 2 and isinstance(it[1], Voice) for it in items]
+    if any(by_voice):
+        if not all(by_voice):
+            raise ValueError("a batch is all (tokens, Voice) items or all prompt wavs, not a mix")
+        store = items[0][1].store
+        voices = [store.check(it[1]) for it in items]
+        # the store holds (feats + feat_bias) * feat_scale of the normalised prompts: nothing to prepare
+        prompt_features, gains = store.gather(voices, max(v.frames for v in voices))
+        nfr = to_device(torch.tensor([v.frames for v in voices]), dev)
+        prompt_tokens, rms = [list(v.prompt_tokens) for v in voices], None
+    else:
+        feats, nfr, rms, _ = _prepare_prompts(items, feature_extractor, target_rms, dev)
+        prompt_features = (feats + feat_bias) * feat_scale
+        prompt_tokens, gains = [it[1] for it in items], None
     if remove_long_sil:
         from .longform import WavJoiner
         joiner = joiner if joiner is not None else WavJoiner()
-        gains = torch.tensor([r / target_rms if r < target_rms else 1.0 for r in rms],
-                             dtype=torch.float32).to(dev)
+        if gains is None:
+            gains = torch.tensor([r / target_rms if r < target_rms else 1.0 for r in rms],
+                                 dtype=torch.float32).to(dev)
     torch.cuda.synchronize(dev)
     t0 = dt.datetime.now()
     pred, pred_lens, _, _ = model.sample(
-        tokens=[it[0] for it in items], prompt_tokens=[it[1] for it in items],
+        tokens=[it[0] for it in items], prompt_tokens=prompt_tokens,
         prompt_features=prompt_features, prompt_features_lens=nfr, speed=speed,
         t_shift=t_shift, duration="predict", num_step=num_step, guidance_scale=guidance_scale,
         x0=x0, seeds=seeds)
@@ -250,6 +270,8 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
     if remove_long_sil:
         out, out_lens = joiner.trim(out, (pred_lens * vocoder.cfg.hop_length).to(torch.int32),
                                     gains)
+    elif rms is None:
+        out = out * gains[:, None]                  # the voices' RMS restore, on the device
     torch.cuda.synchronize(dev)
     t = (dt.datetime.now() - t0).total_seconds()
     if remove_long_sil:
@@ -261,7 +283,7 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
     res = []
     for i in range(B):
         w = out[i, :int(pred_lens[i]) * hop]
-        if rms[i] < target_rms:
+        if rms is not None and rms[i] < target_rms:
             w = w * rms[i] / target_rms
         res.append(w.unsqueeze(0))
     secs = float(pred_lens.sum()) * hop / 24000

@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .common import make_pad_mask, pad_labels, predict_features_lens, speaker_turn_indices
+from .common import make_pad_mask, pad_labels, predict_features_lens, speaker_turn_indices, to_device
 from .config import ModelConfig
 from .engine import HipEngine, padding_id
 from .noise import check_keys, seeded_normal
@@ -170,9 +170,10 @@ class ZipVoice:
         """zipvoice.py:187-212 (dialog: + speaker-turn embeddings, zipvoice_dialog.py:127-159)."""
         eng = self._need_engine()
         tokens_padded = pad_labels(tokens, pad_id=self.pad_id, device=self.device)
-        tokens_lens = torch.tensor([len(t) for t in tokens], dtype=torch.int64,
-                                   device=self.device)
-        pm = make_pad_mask(tokens_lens, tokens_padded.shape[1])
+        tokens_lens = to_device(torch.tensor([len(t) for t in tokens], dtype=torch.int64), self.device)
+        # (make_pad_mask's values at the padded width, which is past every length, without its read
+        # of the longest length back from the device)
+        pm = torch.arange(tokens_padded.shape[1], device=self.device)[None] >= tokens_lens[:, None]
         spk = None
         if self.cfg.dialog:
             spk = speaker_turn_indices(tokens_padded, self.cfg.spk_a_id, self.cfg.spk_b_id,
@@ -181,11 +182,17 @@ class ZipVoice:
         return embed, tokens_lens
 
     def forward_text_condition(self, embed: torch.Tensor, tokens_lens: torch.Tensor,
-                               features_lens: torch.Tensor):
-        """zipvoice.py:214-251."""
+                               features_lens: torch.Tensor, num_frames: Optional[int] = None):
+        """zipvoice.py:214-251.  ``num_frames`` (extra, optional): the longest of ``features_lens`` when
+        the caller knows it on the host; nothing is then read back from the device."""
         eng = self._need_engine()
-        num_frames = int(features_lens.max())
-        padding_mask = make_pad_mask(features_lens.to(self.device), max_len=num_frames)
+        if num_frames is None:
+            num_frames = int(features_lens.max())
+            padding_mask = make_pad_mask(features_lens.to(self.device), max_len=num_frames)
+        else:
+            num_frames = int(num_frames)
+            padding_mask = (torch.arange(num_frames, device=self.device)[None]
+                            >= features_lens.to(self.device)[:, None])
         tc = eng.text_condition(embed, tokens_lens, features_lens, num_frames)
         return tc, padding_mask
 
@@ -198,14 +205,14 @@ class ZipVoice:
         return self.forward_text_condition(embed, tokens_lens, features_lens)
 
     def forward_text_inference_ratio_duration(self, tokens, prompt_tokens, prompt_features_lens,
-                                              speed: float):
-        """zipvoice.py:290-330."""
+                                              speed: float, num_frames: Optional[int] = None):
+        """zipvoice.py:290-330.  ``num_frames``: as ``forward_text_condition``."""
         cat_tokens = [p + t for p, t in zip(prompt_tokens, tokens)]
-        ptl = torch.tensor([len(t) for t in prompt_tokens], dtype=torch.int64, device=self.device)
-        tl = torch.tensor([len(t) for t in tokens], dtype=torch.int64, device=self.device)
+        ptl = to_device(torch.tensor([len(t) for t in prompt_tokens], dtype=torch.int64), self.device)
+        tl = to_device(torch.tensor([len(t) for t in tokens], dtype=torch.int64), self.device)
         cat_embed, cat_tokens_lens = self.forward_text_embed(cat_tokens)
         features_lens = predict_features_lens(prompt_features_lens.to(self.device), ptl, tl, speed)
-        return self.forward_text_condition(cat_embed, cat_tokens_lens, features_lens)
+        return self.forward_text_condition(cat_embed, cat_tokens_lens, features_lens, num_frames)
 
     # ------------------------------------------------------------------ sampling
     def sample(self, tokens: List[List[int]], prompt_tokens: List[List[int]],

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import engine as _eng
+from .common import to_device
 
 
 def _ints(values, what: str, bits: int) -> List[int]:
@@ -77,10 +78,10 @@ def seeded_normal_into(out: torch.Tensor, seeds: Sequence[int],
         raise ValueError("every row of out must be contiguous and rows must not overlap")
     lib = _eng.load_library()
     dev = out.device
-    sd = torch.tensor([_twos(s, 64) for s in seeds], dtype=torch.int64).to(dev)
+    sd = to_device(torch.tensor([_twos(s, 64) for s in seeds], dtype=torch.int64), dev)
     st = None
     if streams is not None:
-        st = torch.tensor([_twos(s, 32) for s in streams], dtype=torch.int32).to(dev)
+        st = to_device(torch.tensor([_twos(s, 32) for s in streams], dtype=torch.int32), dev)
     with torch.cuda.device(dev):
         _eng._check(lib.zv_noise_normal(_eng._ptr(sd), _eng._ptr(st), B, n, ld, _eng._ptr(out),
                                         _eng._stream()), lib)
