@@ -174,6 +174,60 @@ int zv_attn_fallbacks(zv_handle h, int reset, int64_t* host_counts);
 int zv_attn2_check(int kernel, int form, int B, int L, int H, int nv, const float* qkp, const float* P,
                    const uint8_t* key_pad, const float* v, const float* y, int force_exact, float* out,
                    int64_t* counts);
+/* The same with columns [L, Lpad) of V^T (Lpad = L rounded up to 64, the engine's row stride) holding
+ * +stale / -stale (finite, alternating) instead of zeros: the engine's transposed value stores write
+ * frames below L only, so in a reused workspace those columns hold whatever an earlier, longer
+ * pass left there.  A key past L must weigh exactly 0 whatever its value. */
+int zv_attn2_check_stale(int kernel, int form, int B, int L, int H, int nv, const float* qkp, const float* P,
+                         const uint8_t* key_pad, const float* v, const float* y, int force_exact, float stale,
+                         float* out, int64_t* counts);
+
+/* One first-generation attention kernel (csrc/zv_flash.inc) or the materialising softmax
+ * (csrc/zv_attn.inc) alone, through the launch function the engine launches it through (test
+ * infrastructure: pins them against a float64 softmax in tests/test_gpu_attn_ref.py; synchronous).
+ * They are the fp32 mode's kernels (split 3), the fp16 parity mode's text encoder, the over-length /
+ * ZV_ATTN_MATERIALIZE fallback and the ZV_ATTN2=0 / ZV_SA_TP=0 arms.  qkp (B, L, 2*32*H + 4*H)
+ * fp32 rows [q | k | p] and P (2L-1, 4*H) in natural units (these kernels fold log2(e) themselves;
+ * SOFTMAX with b2 = 1 takes base-2 scores and exponentiates with exp2); qkp is rounded to the operand
+ * format (split 1) or split into its hi / lo pair (split 3) as the engine's producers do; key_pad
+ * (B, L) 1 = padded, or NULL.
+ *   ZV_ATTN_STATS    head 0's row statistics.  form 0: positional term on VALU (split 1 / 3), 1: the
+ *                    Toeplitz MFMA form (split 1).  stats (guard + B*L + guard, 2) fp32 = (m, r): the
+ *                    base-2 row maximum estimate and 1 / sum_j 2^(u_j - m).
+ *   ZV_ATTN_NA       NonlinAttention (head 0): the matching STATS launch into a private buffer, then
+ *                    the consumer chosen by width as the engine chooses it (nv <= 384, a multiple
+ *                    of 4).  v, y (B, L, nv); oh (/ ol with split 3) (guard + B*L + guard, ldo),
+ *                    ldo % 4 == 0: out = y * (W0 . v).
+ *   ZV_ATTN_SA       SelfAttention.  form 0: zv_attn_sa_kernel<split>, 1: zv_attn_sa_tp_kernel<0, 2>,
+ *                    2: <0, 1> (forms 1 / 2: split 1).  v (B, L, H*nv), nv <= 12; oh (/ ol with split
+ *                    3) (guard + B*L + guard, ldo), column h * nv + d.  Forms 1 / 2 also write the
+ *                    output's lo half to ol and a second hi copy to oh2 when both are given (the fp16
+ *                    parity mode's [o_hi | o_lo | o_hi] operand).
+ *   ZV_ATTN_SOFTMAX  the weights W = softmax(s) of every head: Wh (/ Wl with split 3)
+ *                    (guard + H*B*L + guard, ldw), ldw = L rounded up to 64, row (h * B + b) * L + i;
+ *                    columns [L, ldw) are written as zeros.
+ * V^T is laid out as the engine's transposed linears leave it: rows of L rounded up to 64 frames
+ * (SA: nv rows per head -- these kernels make the ones row of the softmax denominator in registers;
+ * NA: nv rows), frames below L written, columns past L holding +stale / -stale (finite).  Every
+ * output is canary-filled by the caller, goes to the device as it is and comes back whole.
+ * vrows (SA): V^T rows per head, 0 = nv, or up to 16: the layout of a value projection built padded for
+ * the second-generation kernels, which the engine's fallback and ZV_ATTN2=0 arms hand to these kernels
+ * with a 16-row head stride; rows nv..15 of a head then hold +-stale.
+ * launch (out), written by the kind's launch function itself: {kernel (0 stats, 1 NonlinAttention,
+ * 2 SelfAttention, 3 SelfAttention Toeplitz, 4 softmax), SPLIT, NA value tiles per wave (DTW) / Toeplitz
+ * SA PLO, NA query tiles per block / Toeplitz SA MINW, TPM, grid x, grid y, grid z}. */
+enum zv_attn_kind { ZV_ATTN_STATS = 0, ZV_ATTN_NA = 1, ZV_ATTN_SA = 2, ZV_ATTN_SOFTMAX = 3 };
+typedef struct {
+  int kind, B, L, H, nv, split, form, b2, guard, vrows;
+  float stale;
+  const float* qkp; const float* P; const uint8_t* key_pad;
+  const float* v; const float* y;
+  float* stats;
+  uint16_t* oh; uint16_t* ol; uint16_t* oh2; int64_t ldo;
+  uint16_t* Wh; uint16_t* Wl; int64_t ldw;
+  int launch[8];
+} zv_attn_check_args;
+int zv_attn_check(zv_attn_check_args* a);
 
 /* GEMM microbenchmark (random bf16 operands): average ms per launch of the 128x128 kernel for
  * C(M,N) = A(M,K) W(N,K)^T.  variant 0 = the general epilogue (any out_mode), 70 = the counted

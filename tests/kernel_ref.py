@@ -1265,3 +1265,310 @@ def speech_cond_ref(pf, plen, T, bug=None):
             if keep and (t < Tp or bug in ("no_tp", "le")):
                 out[b, t] = flat[b * Tp + t] if (t < Tp or bug == "no_tp") else 0.0
     return out.reshape(B * T, F)
+
+
+# --------------------------------------------------------------------------- attention
+# (csrc/zv_flash.inc's first-generation kernels and zv_attn.inc's materialising softmax, one launch at a
+# time through zv_attn_check; zv_flash2.inc's second generation through zv_attn2_check_stale;
+# tests/test_gpu_attn_ref.py, case lists and input classes in tests/attn_cases.py.)
+#
+# Definition (RelPositionMultiheadAttentionWeights, zipformer.py:1149-1306): per utterance and head
+#   s[i, j] = q_i . k_j + p_i . P[L-1-i+j];  s[i, j] = -1000 where key j is padded (masked_fill: the
+#   score is REPLACED);  W = softmax_j(s).
+# SelfAttention (:1359-1396): out[i] = sum_j W[i, j] v_j per head; NonlinAttention (:1499-1544):
+# out[i] = y_i * sum_j W0[i, j] v_j with head 0's weights.  base "2": the scores arrive in base-2 units
+# (the second generation, whose engine folds log2(e) into the k / p weights; the softmax kernel's b2):
+# the masked value is -1000 log2(e) and the exponential is 2^s.
+#
+# Operands are taken as the kernel multiplies them: q, k, p, v, y rounded to the operand format, or their
+# hi / lo pairs (split 3: hi hi + hi lo + lo hi for the MFMA products, hi + lo where the kernel adds the
+# halves in fp32, as ld_split does for p and y).
+#
+# What the engine guarantees about V^T columns [L, Lpad) (Lpad = L rounded up to 64): every workspace
+# buffer is zeroed when it is allocated (zv_engine.hip DBuf::get) and grows only; the transposed stores of
+# the value / NonlinAttention projections (zv_gemm.inc gemm_epilogue_trans*, store_trans8) write frames
+# below L only.  So those columns hold zero, or what an earlier pass of another length or batch wrote
+# there: a finite 16-bit activation as long as the model's activations are finite, never an uninitialised
+# pattern.  Every kernel reads them (a key step is 32 or 64 keys) and multiplies them by a weight that is
+# exactly zero (2^-inf), so finite stale data is harmless and a NaN or Inf would not be; nothing in the
+# engine can put one there without the activations themselves being non-finite.  The checks fill the
+# columns with +-1000.
+#
+# Tolerance of a consumer's output, per element (derived, nothing fitted).  Let the computed weights be
+# w_j (1 + e_j).  Where numerator and denominator are summed from the same computed p_j (SelfAttention:
+# the ones row of the value tile), out' - out = sum_j w_j e_j (v_j - out) / (1 + sum_j w_j e_j), so with
+# |e_j| <= E:  |out' - out| <= E / (1 - E) dev,  dev = sum_j w_j |v_j - out|, which vanishes on one-hot
+# rows and on constant v.  Where the denominator comes from elsewhere (first-generation NonlinAttention:
+# the statistics kernel, which scores with another instruction sequence; second-generation
+# NonlinAttention: the fp32 sum of p before p is rounded), the part of e_j that the denominator does not
+# share leaves  out' - out = (sum_j w_j a_j v_j - out sum_j w_j b_j) / (1 + sum_j w_j b_j), bounded by
+# (A + B) / (1 - B) mag with mag = sum_j w_j |v_j| >= |out|: such terms go against mag, not dev.
+# [Found while deriving, before any GPU run: a NonlinAttention row of equal weights 1/n has dev != 0 but
+# every p = 1/n takes the same 16-bit rounding error, which the fp32 denominator does not share --
+# zv_attn_na_kernel: ph[r] = (bf16)pr after cst = -m + log2(r) from the statistics; zv_attn_na2_kernel:
+# psum += pr before ph[r] = (bf16)pr.]
+# E is the sum of
+#   2 ds            numerator and denominator; ds = ((36 + 8) 2^-23 [+ 2^-16 split]) (sum|q||k| + sum|p||P|),
+#                   dot_tol's form with K = 32 + 4, maximum over the row's keys; in base 2 times ln 2
+#   p rounding      half an ulp of the rounded p.  Where the denominator is summed from the rounded p too:
+#                   2^-9 / 2^-12 (16-bit forms) or 2^-16 (hi / lo pair), once for the numerator and once
+#                   more for the denominator.  Where only the numerator has it (NonlinAttention): the
+#                   format's unit roundoff, 2^-8 / 2^-11 -- round-to-nearest to 8 (11) significant bits
+#                   moves a value just above a power of two, 2^e (1 + 2^-8), by 2^(e-8).  [After the first
+#                   GPU run: with 2^-9 the bf16 first-generation NonlinAttention exceeded the bound by up
+#                   to 1.47 x on elements that one +-1000 key dominates; the error there is that key's
+#                   p rounding alone, zv_attn_na_kernel "ph[r] = (bf16)pr".  The SelfAttention figure
+#                   2 * 2^-9 is the same number.]
+#   exponentials    TRANS_FACTOR ERR_EXP2, numerator and denominator
+# The Toeplitz forms (stage_tp) round the positional table to the operand format before the MFMA
+# ("hv[d] = (bf16)a[i][d]": natural units in the first generation, where log2(e) multiplies the fp32 score;
+# the second generation's table arrives log2(e)-scaled).  The reference takes the table as those kernels
+# multiply it, round16(P), like every other operand, so no term stands for that rounding.  [After the first
+# GPU run: a bound term of half an ulp of 2^-9 sum|p||P| in its place was exceeded by up to 1.33 x by
+# zv_attn_stats_kernel<1, 1>, for the same reason as above: the unit roundoff is 2^-8.]
+# plus, absolute, fp16 only: p below the smallest normal 2^-14 is rounded to a multiple of 2^-24 (error at
+# most 2^-25, and never more than p itself).  The largest p of a row is at least 1/2 in every form (first
+# generation: the running maximum's own p is 1; second generation, FA2_OFS: the offset is the integer
+# ceiling of a maximum over some of the row's keys, so the row maximum's p is above 1/2; it stays finite
+# while no score rises 16 above the offset, else the exact path with the maximum subtracted), so the
+# denominator is at least 1/2 and a weight is off by at most min(2^-24, w_j): sub = sum_j min(2^-24, w_j)
+# (|v_j| + |out|) (and the same sum without v on the shared denominator).
+# plus (L + 8) 2^-23 mag for the fp32 accumulation of L products (the online rescales included) and
+# 4 2^-24 |out| for the final reciprocal and multiplies (NonlinAttention's y among them).
+LOG2E = 1.4426950408889634
+LN2 = 0.6931471805599453
+ATT_QD, ATT_PD = 32, 4
+ATT_SUB = 2.0 ** -24                   # fp16: absolute error of a weight from p's subnormal range
+# relative error of numpy's fp32 exp2 against float64 (measured; tests/test_kernel_ref.py recomputes it)
+ERR_EXP2 = 1.8 * U32
+
+# form -> what its bound needs: split; tp: the positional table rounded to the operand format; den: where
+# the denominator comes from ("ones": summed from the rounded p; "stats": another pass; "psum": the fp32 p)
+ATTN_FORMS = {
+    # first generation (natural units)
+    "stats1": dict(kind="stats", split=1, tp=False, base="e"),
+    "stats1_tp": dict(kind="stats", split=1, tp=True, base="e"),
+    "stats3": dict(kind="stats", split=3, tp=False, base="e"),
+    "na1": dict(kind="na", split=1, tp=False, den="stats", base="e"),
+    "na1_tp": dict(kind="na", split=1, tp=True, den="stats", base="e"),
+    "na3": dict(kind="na", split=3, tp=False, den="stats", base="e"),
+    "sa1": dict(kind="sa", split=1, tp=False, den="ones", base="e"),
+    "sa3": dict(kind="sa", split=3, tp=False, den="ones", base="e"),
+    "sa_tp2": dict(kind="sa", split=1, tp=True, den="ones", base="e"),
+    "sa_tp1": dict(kind="sa", split=1, tp=True, den="ones", base="e"),
+    "softmax1": dict(kind="softmax", split=1, tp=False, base="e"),
+    "softmax3": dict(kind="softmax", split=3, tp=False, base="e"),
+    "softmax1_b2": dict(kind="softmax", split=1, tp=False, base="2"),
+    "softmax3_b2": dict(kind="softmax", split=3, tp=False, base="2"),
+    # second generation (base 2)
+    "sa2": dict(kind="sa", split=1, tp=True, den="ones", base="2"),
+    "na2": dict(kind="na", split=1, tp=True, den="psum", base="2"),
+}
+
+
+def attn_parts(x, split, fmt):
+    """The operand halves the kernel holds: [round16(x)] or the hi / lo pair."""
+    return [round16(x, fmt)] if split == 1 else list(split16(x, fmt))
+
+
+def attn_table(P, f, fmt):
+    """The positional table as the form multiplies it: fp32, or rounded to the operand format (stage_tp)."""
+    return round16(P, fmt) if f["tp"] else P
+
+
+def attn_heads(qkp, H):
+    """(L, 2 * 32 H + 4 H) rows [q | k | p] -> q (H, L, 32), k (H, L, 32), p (H, L, 4)."""
+    L = qkp.shape[0]
+    q = qkp[:, :H * ATT_QD].reshape(L, H, ATT_QD).transpose(1, 0, 2)
+    k = qkp[:, H * ATT_QD:2 * H * ATT_QD].reshape(L, H, ATT_QD).transpose(1, 0, 2)
+    p = qkp[:, 2 * H * ATT_QD:].reshape(L, H, ATT_PD).transpose(1, 0, 2)
+    return q, k, p
+
+
+def attn_weights_ref(q, k, p, P, pad, base, bug=None):
+    """One utterance, one head.  q, k: lists of operand halves (L, 32) ([hi] or [hi, lo]: hi hi + hi lo +
+    lo hi); p (L, 4) the value the kernel multiplies; P (2L - 1, 4); pad (L,) 1 = padded, or None.
+    Returns (w (L, L), qmass, pmass): the weights and, per score, sum|q||k| and sum|p||P|.
+    bug: "n_off" n = L - i + j; "mask_kept" the first padded key not masked; "mask_added" -1000 added to a
+    padded key's score instead of replacing it."""
+    L = p.shape[0]
+    i = np.arange(L)[:, None]
+    j = np.arange(L)[None, :]
+    n = L - 1 - i + j
+    if bug == "n_off":
+        n = np.minimum(n + 1, 2 * L - 2)
+    s = dot_kernel(q, k) + (p @ P.T)[i, n]
+    qmass = sum(np.abs(a) for a in q) @ sum(np.abs(a) for a in k).T
+    pmass = (np.abs(p) @ np.abs(P).T)[i, n]
+    mval = -1000.0 * (LOG2E if base == "2" else 1.0)
+    if pad is not None and np.any(pad):
+        m = np.asarray(pad).astype(bool).copy()
+        if bug == "mask_kept":
+            m[np.flatnonzero(m)[0]] = False
+        s = np.where(m[None, :], s + mval if bug == "mask_added" else mval, s)
+    s = s - s.max(1, keepdims=True)
+    e = np.exp2(s) if base == "2" else np.exp(s)
+    return e / e.sum(1, keepdims=True), qmass, pmass
+
+
+def attn_score_ref(q, k, p, P, pad, base):
+    """The masked scores themselves (for the statistics), in the units given."""
+    L = p.shape[0]
+    i = np.arange(L)[:, None]
+    j = np.arange(L)[None, :]
+    s = dot_kernel(q, k) + (p @ P.T)[i, L - 1 - i + j]
+    if pad is not None:
+        s = np.where(np.asarray(pad).astype(bool)[None, :], -1000.0 * (LOG2E if base == "2" else 1.0), s)
+    return s
+
+
+def attn_E(form, fmt, qmass, pmass, L):
+    """Per query row: (Es, En, Esm): the relative weight error that numerator and denominator share, the
+    part only the numerator has, and the weights' own (for the softmax kernel)."""
+    f = ATTN_FORMS[form]
+    unit = LN2 if f["base"] == "2" else 1.0
+    ds = ((36 + 8) * 2.0 ** -23 + (2.0 ** -16 if f["split"] == 3 else 0.0)) * (qmass + pmass)
+    ds = ds.max(1) * unit
+    prnd = 2.0 ** -(PREC[fmt] + 1) if f["split"] == 1 else 2.0 ** -16          # half an ulp at the top of a binade
+    pone = 2.0 ** -PREC[fmt] if f["split"] == 1 else 2.0 ** -16                # ... at its bottom: the unit roundoff
+    ex = TRANS_FACTOR * ERR_EXP2
+    acc = (L + 8) * 2.0 ** -23
+    den = f.get("den")
+    if den == "ones":
+        return 2 * ds + 2 * prnd + 2 * ex, np.zeros_like(ds), None
+    if den == "psum":
+        return 2 * ds + 2 * ex + acc, pone + np.zeros_like(ds), None
+    if den == "stats":
+        return np.zeros_like(ds), 2 * ds + pone + 2 * ex + acc, None
+    return None, None, 2 * ds + 2 * ex + acc
+
+
+def attn_dev(w, v, out):
+    """dev = sum_j w_j |v_j - out| per (query, channel), in channel blocks."""
+    dev = np.zeros_like(out)
+    for c0 in range(0, v.shape[1], 16):
+        d = np.abs(v[None, :, c0:c0 + 16] - out[:, None, c0:c0 + 16])        # (i, j, c)
+        dev[:, c0:c0 + 16] = np.einsum("ij,ijc->ic", w, d)
+    return dev
+
+
+def attn_out_tol(form, fmt, w, v, out, qmass, pmass):
+    """The consumer bound of the section comment for one utterance and head: (L, C).  NonlinAttention
+    (hundreds of channels) takes dev <= mag + |out| instead of the sum itself: its shared part Es is the
+    fp32-level part of E only (the p rounding goes against mag there anyway), so nothing visible is lost;
+    sub is bounded the same way in every form, sum_j min(2^-24, w_j) (|v_j| + |out|)."""
+    L = w.shape[0]
+    f = ATTN_FORMS[form]
+    Es, En, _ = attn_E(form, fmt, qmass, pmass, L)
+    mag = w @ np.abs(v)
+    dev = attn_dev(w, v, out) if f["kind"] == "sa" else mag + np.abs(out)
+    sb = 0.0
+    if fmt == "f16":
+        ws = np.minimum(w, ATT_SUB)
+        sb = ws @ np.abs(v) + ws.sum(1)[:, None] * np.abs(out)
+        if f["den"] == "ones":
+            Es = Es + ws.sum(1)
+    Es = Es[:, None]
+    assert Es.max() < 0.5
+    return (Es * dev + En[:, None] * mag) / (1.0 - Es) + sb + (L + 8) * 2.0 ** -23 * mag + 4 * U32 * np.abs(out)
+
+
+def attn_consumer_ref(form, fmt, qkp, P, pad, v, y, H, nv, bug=None, tol=True):
+    """SelfAttention / NonlinAttention of a batch.  qkp (B, L, .), P (2L - 1, 4 H), pad (B, L) or None,
+    v (B, L, H nv) / (B, L, nv), y (B, L, nv) or None: fp32 values (float64 arrays), rounded / split here.
+    Returns (ref, tol) of shape v's.
+    bug: attn_weights_ref's, or "past_L" a key L (zero k, no table row: score 0) whose value is +1000
+    included; "utt_prev" utterance b reads utterance b - 1's values; "head_next" head h reads head h + 1's
+    positional slice."""
+    f = ATTN_FORMS[form]
+    sa = f["kind"] == "sa"
+    B, L, _ = qkp.shape
+    ref = np.zeros(v.shape)
+    tl = np.zeros(v.shape)
+    vs = sum(attn_parts(v, f["split"], fmt))
+    for b in range(B):
+        q, k, p = attn_heads(qkp[b], H)
+        vb = vs[b - 1 if bug == "utt_prev" else b]
+        for h in (range(H) if sa else [0]):
+            hp = (h + 1) % H if bug == "head_next" else h
+            qq, kk = attn_parts(q[h], f["split"], fmt), attn_parts(k[h], f["split"], fmt)
+            pp = sum(attn_parts(p[h], f["split"], fmt))
+            Ph = attn_table(P[:, hp * ATT_PD:(hp + 1) * ATT_PD], f, fmt)
+            w, qm, pm = attn_weights_ref(qq, kk, pp, Ph, None if pad is None else pad[b], f["base"], bug)
+            vh = vb[:, h * nv:(h + 1) * nv] if sa else vb
+            if bug == "past_L":
+                s0 = attn_score_ref(qq, kk, pp, Ph, None if pad is None else pad[b], f["base"]).max(1)
+                e = (np.exp2(-s0) if f["base"] == "2" else np.exp(-s0))[:, None]      # the extra key's weight
+                o = (w @ vh + e * 1000.0) / (1.0 + e)
+            else:
+                o = w @ vh
+            t = attn_out_tol(form, fmt, w, vh, o, qm, pm) if tol else 0.0
+            if sa:
+                ref[b, :, h * nv:(h + 1) * nv] = o
+                tl[b, :, h * nv:(h + 1) * nv] = t
+            else:
+                yy = sum(attn_parts(y[b], f["split"], fmt))
+                ref[b] = o * yy
+                tl[b] = t * np.abs(yy) + U32 * np.abs(ref[b])
+    return ref, tl
+
+
+def attn_stats_ref(form, fmt, qkp, P, pad, H):
+    """Head 0's row statistics in base 2: (lse2, mx2, tol) each (B, L): log2 sum_j 2^u_j and max_j u_j with
+    u = log2(e) s.  tol: ds log2(e) for the scores, the accumulation and the exponentials of the sum, and
+    fp32 roundings of m, log2 r and their difference."""
+    f = ATTN_FORMS[form]
+    B, L, _ = qkp.shape
+    lse = np.zeros((B, L))
+    mx = np.zeros((B, L))
+    tl = np.zeros((B, L))
+    for b in range(B):
+        q, k, p = attn_heads(qkp[b], H)
+        qq, kk = attn_parts(q[0], f["split"], fmt), attn_parts(k[0], f["split"], fmt)
+        pp = sum(attn_parts(p[0], f["split"], fmt))
+        pb = None if pad is None else pad[b]
+        P0 = attn_table(P[:, :ATT_PD], f, fmt)
+        u = attn_score_ref(qq, kk, pp, P0, pb, "e") * LOG2E
+        _, qm, pm = attn_weights_ref(qq, kk, pp, P0, pb, "e")
+        mx[b] = u.max(1)
+        lse[b] = mx[b] + np.log2(np.exp2(u - mx[b][:, None]).sum(1))
+        # (the bound of the scores as attn_E forms it, without the factor 2 and in base 2)
+        ds = ((36 + 8) * 2.0 ** -23 + (2.0 ** -16 if f["split"] == 3 else 0.0)) * (qm + pm)
+        tl[b] = ds.max(1) * LOG2E + ((L + 8) * 2.0 ** -23 + 2 * TRANS_FACTOR * ERR_EXP2 + 2.0 ** -22) / LN2 \
+            + 2.0 ** -22 * (np.abs(mx[b]) + np.abs(lse[b]) + 1.0)
+    return lse, mx, tl
+
+
+def attn_softmax_ref(form, fmt, qkp, P, pad, H, bug=None):
+    """The materialised weights (H, B, L, L) and their relative tolerance (H, B, L)."""
+    f = ATTN_FORMS[form]
+    B, L, _ = qkp.shape
+    W = np.zeros((H, B, L, L))
+    E = np.zeros((H, B, L))
+    for b in range(B):
+        q, k, p = attn_heads(qkp[b], H)
+        for h in range(H):
+            qq, kk = attn_parts(q[h], f["split"], fmt), attn_parts(k[h], f["split"], fmt)
+            pp = sum(attn_parts(p[h], f["split"], fmt))
+            W[h, b], qm, pm = attn_weights_ref(qq, kk, pp, P[:, h * ATT_PD:(h + 1) * ATT_PD],
+                                               None if pad is None else pad[b], f["base"], bug)
+            E[h, b] = attn_E(form, fmt, qm, pm, L)[2]
+    return W, E
+
+
+def attn_accept(got, ref, tol, fmt, split=1):
+    """The interval rule: round16(ref - tol) <= got <= round16(ref + tol) per element; split 3: got = hi +
+    lo within tol + 2^-16 |ref| (+ the pair's underflow).  Returns (bad mask, max |got - ref| / (tol + the format's half ulp))."""
+    ref = np.asarray(ref, np.float64)
+    if split == 3:
+        # (+ what the pair cannot hold: half the format's smallest spacing, and fp32's smallest normal)
+        t = tol + 2.0 ** -16 * np.abs(ref) + 0.5 * ulp16(0.0, fmt) + 2.0 ** -126
+        lo, hi = ref - t, ref + t
+        allow = t
+    else:
+        lo, hi = round16(ref - tol, fmt), round16(ref + tol, fmt)
+        allow = tol + 0.5 * ulp16(ref, fmt)
+    with np.errstate(invalid="ignore"):
+        bad = ~((got >= lo) & (got <= hi)) | ~np.isfinite(got)
+        err = np.where(got == ref, 0.0, np.abs(got - ref) / np.maximum(allow, 1e-300))
+    return bad, float(np.nanmax(err)) if err.size else 0.0

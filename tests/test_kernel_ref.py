@@ -621,3 +621,118 @@ def test_solve_text_side_mutants_visible():
             _differs(ref, kr.speech_cond_ref(pf, plen, T, bug="le"), 0.0, "speech t <= plen")
             if T > Tp:
                 _differs(ref, kr.speech_cond_ref(pf, plen, T, bug="no_tp"), 0.0, "speech t < Tp missing")
+
+
+# ---------------------------------------------------------------------------------------------
+# attention (kernel_ref's section "attention", tests/attn_cases.py, tests/test_gpu_attn_ref.py)
+# ---------------------------------------------------------------------------------------------
+import attn_cases as ac  # noqa: E402
+
+
+def test_attn_exp2_error_table():
+    """numpy's fp32 exp2 against float64 over the softmax's range (the yardstick ERR_EXP2 that the
+    attention tolerances take TRANS_FACTOR times)."""
+    x = np.linspace(-140.0, 24.0, 400001).astype(np.float32)
+    got = np.exp2(x).astype(np.float64)
+    ref = np.exp2(x.astype(np.float64))
+    ok = ref >= 2.0 ** -126
+    r = (np.abs(got - ref)[ok] / ref[ok]).max() / kr.U32
+    print(f"exp2: {r:.2f} * 2^-24 relative")
+    assert r <= kr.ERR_EXP2 / kr.U32
+
+
+def _sa_weights(inp, fmt, base="e"):
+    for b in range(ac.B):
+        q, k, p = kr.attn_heads(inp["qkp"][b], ac.H)
+        for h in range(ac.H):
+            w, _, _ = kr.attn_weights_ref([kr.round16(q[h], fmt)], [kr.round16(k[h], fmt)], kr.round16(p[h], fmt),
+                                          inp["P"][:, h * ac.PD:(h + 1) * ac.PD],
+                                          None if inp["pad"] is None else inp["pad"][b], base)
+            yield b, h, w
+
+
+@pytest.mark.parametrize("mask", [True, False])
+@pytest.mark.parametrize("L", ac.LENGTHS)
+def test_attn_onehot_construction(L, mask):
+    """Every case of the list: the match's weight is at least 1 - 2^-50 (in both units, with and without
+    the padded keys' raised scores), pi stays inside the kept keys, and every operand of the one-hot and
+    shift classes is a value of both 16-bit formats."""
+    for hot in (False, True):
+        inp = ac.attn_inputs("onehot", L, "sa", ac.SA_NV, "bf16", mask=mask, hot_masked=hot)
+        for fmt in ("bf16", "f16"):
+            for name in ("qkp", "v"):
+                assert np.array_equal(kr.round16(inp[name], fmt), inp[name]), (name, fmt)
+        for base in ("e", "2"):
+            for b, h, w in _sa_weights(inp, "bf16", base):
+                pi = inp["pi"][b, h]
+                assert pi.max() < (inp["lens"][b] if mask else L)
+                assert w[np.arange(L), pi].min() >= 1.0 - 2.0 ** -50, (b, h)
+    na = ac.attn_inputs("onehot", L, "na", 40, "bf16", mask=mask)
+    prod = na["v"] * na["y"]
+    sh = ac.attn_inputs("shift", L, "sa", ac.SA_NV, "bf16", mask=mask)
+    kr.assert_fp32_exact(prod)       # NonlinAttention's y v is one exact fp32 product, then rounded once
+    for fmt in ("bf16", "f16"):
+        for name in ("qkp", "P", "v"):
+            assert np.array_equal(kr.round16(sh[name], fmt), sh[name]), (name, fmt)
+    # the shift class's rows: one-hot on j = i + d where that key exists and is kept, else uniform
+    for b, h, w in _sa_weights(sh, "bf16"):
+        d = ac.shift_of(L, h)
+        nk = sh["lens"][b] if mask else L
+        for i in range(L):
+            if 0 <= i + d < nk:
+                assert w[i, i + d] >= 1.0 - 2.0 ** -50
+            else:
+                assert np.allclose(w[i, :nk], 1.0 / nk, rtol=1e-12)
+
+
+def test_attn_dev_bound_against_perturbation():
+    """The bounds of the section comment against brute force: weights perturbed by relative errors up to
+    E, at random and at the worst signs; a shared denominator is bounded through dev, a denominator with
+    errors of its own through mag."""
+    rng = np.random.default_rng(5)
+    worst = [0.0, 0.0]
+    for trial in range(200):
+        n, E = int(rng.integers(1, 40)), float(rng.choice([1e-6, 2.0 ** -9, 0.05, 0.3]))
+        w = rng.random(n) ** 4
+        w /= w.sum()
+        v = rng.standard_normal(n) * rng.choice([1.0, 1000.0], n)
+        out = w @ v
+        dev, mag = w @ np.abs(v - out), w @ np.abs(v)
+        for k in range(6):
+            e = E * (np.sign(v - out) * (1 if k == 0 else -1) if k < 2 else rng.uniform(-1, 1, n))
+            got = (w * (1 + e)) @ v / (w * (1 + e)).sum()
+            bound = E / (1 - E) * dev
+            assert abs(got - out) <= bound + 1e-13 * mag       # (+ this test's own float64 noise)
+            if bound > 1e-9 * mag:
+                worst[0] = max(worst[0], abs(got - out) / bound)
+            e2 = E * (np.sign(v) * np.sign(out) * -1 if k == 0 else rng.uniform(-1, 1, n))
+            got = (w * (1 + e)) @ v / (w * (1 + e2)).sum()
+            bound = 2 * E / (1 - E) * mag
+            assert abs(got - out) <= bound + 1e-13 * mag       # (+ this test's own float64 noise)
+            if bound > 1e-9 * mag:
+                worst[1] = max(worst[1], abs(got - out) / bound)
+    print(f"worst |out' - out| / bound: shared {worst[0]:.3f}, separate {worst[1]:.3f}")
+    assert worst[0] > 0.9            # the dev bound is attained (not slack the kernels could hide in)
+
+
+@pytest.mark.parametrize("case", ac.BUG_CASES, ids=lambda c: "-".join(str(x) for x in c))
+def test_attn_classes_see_each_bug(case):
+    """Each deliberate mistake of the reference falls outside the right reference's tolerance on at least
+    one element of its smallest case, in both operand formats (first-generation 16-bit forms; the one-hot
+    class at tolerance 0)."""
+    bug, klass, L, kernel = case
+    nv = ac.SA_NV if kernel == "sa" else 40
+    form = "sa1" if kernel == "sa" else "na1"
+    for fmt in ("bf16", "f16"):
+        inp = ac.attn_inputs(klass, L, kernel, nv, fmt, hot_masked=True)
+        args = (form, fmt, inp["qkp"], inp["P"], inp["pad"], inp["v"], inp["y"], ac.H, nv)
+        ref, tol = kr.attn_consumer_ref(*args)
+        if klass == "onehot":
+            assert np.array_equal(ref, ac.onehot_expected(inp, kernel, nv))
+            tol = np.zeros_like(tol)
+        wrong, _ = kr.attn_consumer_ref(*args, bug=bug, tol=False)
+        bad, worst = kr.attn_accept(kr.round16(wrong, fmt), ref, tol, fmt)
+        print(f"{case} [{fmt}]: {int(bad.sum())} of {bad.size} elements outside, worst {worst:.3g} x the allowance")
+        assert bad.any()
+        ok, _ = kr.attn_accept(kr.round16(ref, fmt), ref, tol, fmt)
+        assert not ok.any()

@@ -31,6 +31,13 @@ struct AttnParams {
 
 constexpr int ATT_QD = 32, ATT_PD = 4;
 
+// What the last attention launch of this file or zv_flash.inc was, written by its launch function (test
+// infrastructure: zv_attn_check reports it, so a test sees which instantiation ran): kernel 0 stats,
+// 1 NonlinAttention, 2 SelfAttention, 3 SelfAttention Toeplitz, 4 materialising softmax; a = value tiles per
+// wave (NonlinAttention) or PLO (Toeplitz SelfAttention), b = query tiles per block or MINW
+struct AttnLaunchRec { int kernel, split, a, b, tpm, gx, gy, gz; };
+static thread_local AttnLaunchRec g_zv_last_attn = {-1, 0, 0, 0, 0, 0, 0, 0};
+
 template <int SPLIT>
 __device__ __forceinline__ void load_qk_frag(const bf16* qh, const bf16* ql, long off, bool valid,
                                              bf16x8& hi, bf16x8& lo) {
@@ -179,6 +186,7 @@ static void launch_attn_softmax(const AttnParams& p, hipStream_t s) {
   ZvProfScope prof(SPLIT == 3 ? "attn_softmax_fp32" : "attn_softmax_bf16",
                    72.0 * p.H * p.B * (double)p.L * p.L,
                    (double)p.H * p.B * p.L * (double)p.ldw * 2 * (SPLIT == 3 ? 2 : 1), s);
+  g_zv_last_attn = {4, SPLIT, 0, 0, 0, (int)grid.x, (int)grid.y, (int)grid.z};
   hipLaunchKernelGGL((zv_attn_softmax_kernel<SPLIT>), grid, dim3(256), lds, s, p);
   ZV_LAUNCH_CHECK();
 }

@@ -1,5 +1,5 @@
 // Test-infrastructure and microbenchmark entry points of the C ABI: zv_bench_gemm, zv_bench_fused_linear,
-// zv_gemm_selftest, zv_attn_plan, zv_attn2_check, zv_mx8_quantize, zv_mx8_gemm_check, zv_linear_check, zv_ffn_check,
+// zv_gemm_selftest, zv_attn_plan, zv_attn2_check, zv_attn2_check_stale, zv_attn_check, zv_mx8_quantize, zv_mx8_gemm_check, zv_linear_check, zv_ffn_check,
 // zv_dwconv_check, zv_stackedge_check, zv_bigvgan_check, zv_solve_check (and the host-only zv_time_steps,
 // zv_cfg_plan).
 // None of them builds an engine: each runs one launch (or a timed loop of one launch) of a kernel the
@@ -322,10 +322,10 @@ int zv_attn_plan(int split, int sa_plo, int tpm, int L, int nv_na, int64_t* lds_
 // form 0: the engine's choice for L; SelfAttention 1 / 2: sa2 with 2 / 3 query tiles per wave,
 // 3 / 4 / 5: sa3 with 2 / 3 / 4; NonlinAttention 1 / 2: 4 / 8 query tiles per block.
 // force_exact: every wave / block on its exact path.  counts (or null): zv_attn_fallbacks's three.
-int zv_attn2_check(int kernel, int form, int B, int L, int H, int nv, const float* qkp, const float* P,
-                   const uint8_t* key_pad, const float* v, const float* y, int force_exact, float* out,
-                   int64_t* counts) {
-  ZV_API_BEGIN
+// stale: V^T columns [L, Lpad) hold +-stale (zv_attn2_check_stale) instead of zeros
+static void attn2_check_run(int kernel, int form, int B, int L, int H, int nv, const float* qkp, const float* P,
+                            const uint8_t* key_pad, const float* v, const float* y, int force_exact, float stale,
+                            float* out, int64_t* counts) {
   ZV_REQUIRE((kernel == 0 || kernel == 1) && B > 0 && L > 0 && H > 0 && qkp && P && v && out &&
                  (kernel == 0 ? (nv > 0 && nv <= 12) : (nv > 0 && nv <= 384 && y)),
              "zv_attn2_check: bad arguments");
@@ -345,6 +345,9 @@ int zv_attn2_check(int kernel, int form, int B, int L, int H, int nv, const floa
         else if (d == 12) x = 1.f;                       // the ones row (softmax denominator)
         hv[((size_t)b * vrows + r) * Lpad + j] = (bf16)x;
       }
+      if (stale != 0.f)
+        for (long j = L; j < Lpad; ++j)
+          hv[((size_t)b * vrows + r) * Lpad + j] = (bf16)(((r + j) & 1) ? -stale : stale);
     }
   std::vector<bf16> hy;
   if (kernel == 1) {
@@ -382,6 +385,154 @@ int zv_attn2_check(int kernel, int form, int B, int L, int H, int nv, const floa
     dev.down(c, dcnt, 4);
     for (int i = 0; i < 3; ++i) counts[i] = c[i];
   }
+}
+
+int zv_attn2_check(int kernel, int form, int B, int L, int H, int nv, const float* qkp, const float* P,
+                   const uint8_t* key_pad, const float* v, const float* y, int force_exact, float* out,
+                   int64_t* counts) {
+  ZV_API_BEGIN
+  attn2_check_run(kernel, form, B, L, H, nv, qkp, P, key_pad, v, y, force_exact, 0.f, out, counts);
+  ZV_API_END
+}
+
+// zv_attn2_check with V^T columns [L, Lpad) filled with +-stale: finite values a reused workspace
+// may hold there (the transposed stores write frames below L only)
+int zv_attn2_check_stale(int kernel, int form, int B, int L, int H, int nv, const float* qkp, const float* P,
+                         const uint8_t* key_pad, const float* v, const float* y, int force_exact, float stale,
+                         float* out, int64_t* counts) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(stale == stale && fabsf(stale) <= 60000.f, "zv_attn2_check_stale: a finite fill (within fp16's range)");
+  attn2_check_run(kernel, form, B, L, H, nv, qkp, P, key_pad, v, y, force_exact, stale, out, counts);
+  ZV_API_END
+}
+
+// ---------------------------------------------------------------------------
+// zv_attn_check: one first-generation attention kernel (zv_flash.inc) or the materialising softmax
+// (zv_attn.inc) alone, through its launch function, on host arrays with canary-guarded outputs
+// ---------------------------------------------------------------------------
+int zv_attn_check(zv_attn_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && a->kind >= ZV_ATTN_STATS && a->kind <= ZV_ATTN_SOFTMAX && a->B > 0 && a->L > 0 && a->H > 0 &&
+                 (a->split == 1 || a->split == 3) && a->guard >= 0 && a->qkp && a->P,
+             "zv_attn_check: bad arguments");
+  const int kind = a->kind, B = a->B, L = a->L, H = a->H, nv = a->nv, G = a->guard;
+  const bool split3 = a->split == 3;
+  ZV_REQUIRE(kind == ZV_ATTN_SA ? (a->form >= 0 && a->form <= 2) : kind == ZV_ATTN_SOFTMAX ? a->form == 0
+                                                                                           : (a->form == 0 || a->form == 1),
+             "zv_attn_check: form (STATS / NA 0 VALU, 1 Toeplitz; SA 0 sa, 1 sa_tp<0, 2>, 2 sa_tp<0, 1>)");
+  ZV_REQUIRE(a->form == 0 || !split3, "zv_attn_check: the Toeplitz forms are 16-bit forms");
+  ZV_REQUIRE(kind == ZV_ATTN_SOFTMAX || a->b2 == 0, "zv_attn_check: b2 belongs to SOFTMAX");
+  ZV_REQUIRE(a->stale == a->stale && fabsf(a->stale) <= 60000.f, "zv_attn_check: a finite fill (within fp16's range)");
+  const long ldq = 2L * H * ATT_QD + H * ATT_PD, M = (long)B * L, Lpad = round_up(L, 64), rows = M + 2 * G;
+  ChkDev dev;
+  hipStream_t s = nullptr;
+  std::vector<bf16> h, l;
+  chk_act(a->qkp, M, (int)ldq, ldq, split3, h, l);
+  const bf16* qh = dev.up(h.data(), h.size());
+  const bf16* ql = split3 ? dev.up(l.data(), l.size()) : nullptr;
+  const float* P = dev.up(a->P, (size_t)(2 * L - 1) * H * ATT_PD);
+  const uint8_t* pad = a->key_pad ? dev.up(a->key_pad, (size_t)M) : nullptr;
+  auto up16 = [&](uint16_t* p, long n, long ld) {
+    return p ? reinterpret_cast<bf16*>(dev.up(p, (size_t)(n + 2 * G) * ld)) : nullptr;
+  };
+  auto down16 = [&](uint16_t* p, bf16* d, long n, long ld) {
+    if (p) dev.down(p, reinterpret_cast<uint16_t*>(d), (size_t)(n + 2 * G) * ld);
+  };
+  if (kind == ZV_ATTN_SOFTMAX) {
+    ZV_REQUIRE(a->Wh && (a->Wl != nullptr) == split3 && a->ldw == Lpad,
+               "zv_attn_check: SOFTMAX writes Wh (Wl with split 3) in rows of L rounded up to 64");
+    const long n = (long)H * M;
+    bf16 *Wh = up16(a->Wh, n, Lpad), *Wl = up16(a->Wl, n, Lpad);
+    AttnParams ap{qh, ql, ldq, P, pad, Wh + (size_t)G * Lpad, Wl ? Wl + (size_t)G * Lpad : nullptr, Lpad, B, L, H,
+                  a->b2 ? 1 : 0};
+    if (split3) launch_attn_softmax<3>(ap, s);
+    else launch_attn_softmax<1>(ap, s);
+    ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+    down16(a->Wh, Wh, n, Lpad); down16(a->Wl, Wl, n, Lpad);
+  } else {
+    FlashParams f{};
+    f.qh = qh; f.ql = ql; f.ldq = ldq; f.P = P; f.key_pad = pad;
+    f.B = B; f.L = L; f.H = H;
+    float2* st = nullptr;
+    float* stg = nullptr;
+    if (kind == ZV_ATTN_STATS) {
+      ZV_REQUIRE(a->stats, "zv_attn_check: STATS writes stats");
+      stg = dev.up(a->stats, (size_t)rows * 2);
+      st = reinterpret_cast<float2*>(stg) + G;
+    } else if (kind == ZV_ATTN_NA) {
+      st = dev.zero<float2>((size_t)M);
+    }
+    f.stats = st;
+    if (kind != ZV_ATTN_SA) {   // head-0 statistics, in the form the NonlinAttention launch scores in
+      if (split3) launch_attn_stats<3>(f, s);
+      else if (a->form == 1) launch_attn_stats<1, 1>(f, s);
+      else launch_attn_stats<1>(f, s);
+    }
+    if (kind == ZV_ATTN_STATS) {
+      ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+      dev.down(a->stats, stg, (size_t)rows * 2);
+    } else {
+      const bool na = kind == ZV_ATTN_NA;
+      ZV_REQUIRE(a->v && a->oh && nv > 0 && (na ? (nv <= 384 && nv % 4 == 0 && a->y && a->ldo % 4 == 0 && a->ldo >= nv)
+                                                : (nv <= 12 && a->ldo >= (long)H * nv)),
+                 "zv_attn_check: v, out and the value width (SA <= 12 per head; NA <= 384, a multiple of 4, with y)");
+      ZV_REQUIRE(split3 ? (a->ol && !a->oh2) : (!na && a->form > 0) ? ((a->ol != nullptr) == (a->oh2 != nullptr))
+                                                                     : (!a->ol && !a->oh2),
+                 "zv_attn_check: ol with split 3; ol and oh2 together with the Toeplitz SelfAttention form only");
+      // V^T as the engine's transposed linears leave it: rows of Lpad frames, frames below L written,
+      // the rest whatever the workspace held (+-stale here).  SA: nv rows per head (the first-generation
+      // kernels make their ones row in registers: vconst / vfix), NA: nv rows
+      // (vrows = 16: the layout of a value projection built padded for the second generation, which the
+      // engine's fallback / ZV_ATTN2=0 arms hand to these kernels with a 16-row head stride; rows nv..15 of
+      // a head -- the ones row and zero rows there -- are not read: stale values here)
+      ZV_REQUIRE(a->vrows == 0 || (!na && a->vrows >= nv && a->vrows <= 16),
+                 "zv_attn_check: vrows (SA V^T rows per head): 0 = nv, or nv..16");
+      const long vph = na ? nv : (a->vrows ? a->vrows : nv);
+      const long vrows = na ? nv : (long)H * vph, vcols = na ? nv : (long)H * nv;
+      std::vector<bf16> vh((size_t)B * vrows * Lpad), vl;
+      if (split3) vl.resize(vh.size());
+      for (int b = 0; b < B; ++b)
+        for (long r = 0; r < vrows; ++r) {
+          bf16* dh = &vh[((size_t)b * vrows + r) * Lpad];
+          bf16* dl = split3 ? &vl[((size_t)b * vrows + r) * Lpad] : nullptr;
+          for (long j = 0; j < Lpad; ++j) {
+            const long hh = r / vph, d = r % vph;      // (NonlinAttention: hh = 0, d = r)
+            const float x = j < L && d < nv ? a->v[((long)b * L + j) * vcols + hh * nv + d]
+                                            : (((r + j) & 1) ? -a->stale : a->stale);
+            dh[j] = (bf16)x;
+            if (dl) dl[j] = j < L && d < nv ? (bf16)(x - (float)dh[j]) : (bf16)x;
+          }
+        }
+      f.vh = dev.up(vh.data(), vh.size());
+      f.vl = split3 ? dev.up(vl.data(), vl.size()) : nullptr;
+      f.ldv = Lpad; f.sv_b = vrows * Lpad; f.nv = nv;
+      bf16 *oh = up16(a->oh, M, a->ldo), *ol = up16(a->ol, M, a->ldo), *oh2 = up16(a->oh2, M, a->ldo);
+      f.oh = oh + (size_t)G * a->ldo; f.ol = ol ? ol + (size_t)G * a->ldo : nullptr;
+      f.oh2 = oh2 ? oh2 + (size_t)G * a->ldo : nullptr; f.ldo = a->ldo;
+      if (na) {
+        const long ldy = round_up(nv, 8);
+        std::vector<bf16> yh, yl;
+        chk_act(a->y, M, nv, ldy, split3, yh, yl);
+        f.mulh = dev.up(yh.data(), yh.size());
+        f.mull = split3 ? dev.up(yl.data(), yl.size()) : nullptr;
+        f.ldmul = ldy; f.vrows_per_head = 0; f.ocol_per_head = 0;
+        if (split3) attn_na_v1<3, 0>(f, nv, s);
+        else if (a->form == 1) attn_na_v1<1, 1>(f, nv, s);
+        else attn_na_v1<1, 0>(f, nv, s);
+      } else {
+        f.vrows_per_head = (int)vph; f.ocol_per_head = nv;
+        if (split3) launch_attn_sa<3>(f, s);
+        else if (a->form == 1) launch_attn_sa_tp<0>(f, s);
+        else if (a->form == 2) launch_attn_sa_tp<0, 1>(f, s);
+        else launch_attn_sa<1>(f, s);
+      }
+      ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize()));
+      down16(a->oh, oh, M, a->ldo); down16(a->ol, ol, M, a->ldo); down16(a->oh2, oh2, M, a->ldo);
+    }
+  }
+  const AttnLaunchRec& r = g_zv_last_attn;       // the last launch: the kind's own kernel
+  const int rec[8] = {r.kernel, r.split, r.a, r.b, r.tpm, r.gx, r.gy, r.gz};
+  memcpy(a->launch, rec, sizeof(rec));
   ZV_API_END
 }
 

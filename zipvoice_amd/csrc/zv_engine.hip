@@ -742,14 +742,7 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
 
   // ---------------------------------------------------------------- fused attention consumers
   // NonlinAttention's head-0 consumer: the second-generation kernel (a2), the Toeplitz MFMA scoring
-  // (tp_na) or the VALU form
-  template <int SPLIT, int TPM>
-  static void attn_na_v1(const FlashParams& f, int hid, hipStream_t s) {   // by the hidden width
-    constexpr int QTILES = SPLIT == 3 ? 4 : 8;
-    if (hid <= 128) launch_attn_na<SPLIT, 1, QTILES, TPM>(f, s);
-    else if (hid <= 256) launch_attn_na<SPLIT, 2, QTILES, TPM>(f, s);
-    else launch_attn_na<SPLIT, 3, QTILES, TPM>(f, s);
-  }
+  // (tp_na) or the VALU form (attn_na_v1, zv_flash.inc)
   template <int SPLIT>
   void attn_na(const FlashParams& f, int hid, bool a2, bool tp_na, hipStream_t s) {
     if constexpr (SPLIT == 1) {

@@ -1022,6 +1022,7 @@ static void launch_attn_stats(const FlashParams& p, hipStream_t s) {
   }
   ZvProfScope prof(SPLIT == 3 ? "attn_stats_fp32" : "attn_stats_bf16",
                    72.0 * p.B * (double)p.L * p.L, 0.0, s);
+  g_zv_last_attn = {0, SPLIT, 0, 0, TPM, (int)grid.x, (int)grid.y, (int)grid.z};
   hipLaunchKernelGGL((zv_attn_stats_kernel<SPLIT, TPM>), grid, dim3(256), lds, s, p);
   ZV_LAUNCH_CHECK();
 }
@@ -1042,8 +1043,19 @@ static void launch_attn_na(const FlashParams& p, hipStream_t s) {
   // algorithmic work: scores (72 flop) + P.V (2 nv flop) per (query, key)
   ZvProfScope prof(SPLIT == 3 ? "attn_na_fp32" : "attn_na_bf16",
                    (72.0 + 2.0 * p.nv) * p.B * (double)p.L * p.L, 0.0, s);
+  g_zv_last_attn = {1, SPLIT, DTW, QTILES, TPM, (int)grid.x, (int)grid.y, (int)grid.z};
   hipLaunchKernelGGL((zv_attn_na_kernel<SPLIT, DTW, QTILES, TPM>), grid, dim3(128 * QTILES), lds, s, p);
   ZV_LAUNCH_CHECK();
+}
+
+// the first-generation NonlinAttention consumer by the hidden width (the engine's layers and
+// zv_attn_check launch it through here)
+template <int SPLIT, int TPM>
+static void attn_na_v1(const FlashParams& f, int hid, hipStream_t s) {
+  constexpr int QTILES = SPLIT == 3 ? 4 : 8;
+  if (hid <= 128) launch_attn_na<SPLIT, 1, QTILES, TPM>(f, s);
+  else if (hid <= 256) launch_attn_na<SPLIT, 2, QTILES, TPM>(f, s);
+  else launch_attn_na<SPLIT, 3, QTILES, TPM>(f, s);
 }
 
 template <int SPLIT>
@@ -1060,6 +1072,7 @@ static void launch_attn_sa(const FlashParams& p, hipStream_t s) {
   dim3 grid(cdiv(p.L, SA_QT), p.H, p.B);
   ZvProfScope prof(SPLIT == 3 ? "attn_sa_fp32" : "attn_sa_bf16",
                    (72.0 + 2.0 * p.nv) * p.H * p.B * (double)p.L * p.L, 0.0, s);
+  g_zv_last_attn = {2, SPLIT, 0, 0, 0, (int)grid.x, (int)grid.y, (int)grid.z};
   hipLaunchKernelGGL((zv_attn_sa_kernel<SPLIT>), grid, dim3(256), lds, s, p);
   ZV_LAUNCH_CHECK();
 }
@@ -1077,6 +1090,7 @@ static void launch_attn_sa_tp(const FlashParams& p, hipStream_t s) {
   }
   dim3 grid(cdiv(p.L, SA_QT), p.H, p.B);
   ZvProfScope prof("attn_sa_bf16", (72.0 + 2.0 * p.nv) * p.H * p.B * (double)p.L * p.L, 0.0, s);
+  g_zv_last_attn = {3, 1, PLO, MINW, 1, (int)grid.x, (int)grid.y, (int)grid.z};
   hipLaunchKernelGGL((zv_attn_sa_tp_kernel<PLO, MINW>), grid, dim3(256), lds, s, p);
   ZV_LAUNCH_CHECK();
 }

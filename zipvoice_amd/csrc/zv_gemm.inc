@@ -89,7 +89,22 @@ constexpr int gemm_stage_bytes() {
                     : ((SPLIT == 3 ? 2 : 1) * BM + (SPLIT == 3 || SPLIT == 2 ? 2 : 1) * BN) * BK * 2;
 }
 
+// The fp32 value a hi / lo pair is split from, pinned to one register in the fp16-operand build.  There
+// the compiler may fold the multiply that produced the value into the hi conversion for one use of hi
+// (v_fma_mixlo_f16: the exact product rounded once) and convert the fp32-rounded product for the other
+// (rounded twice).  Where the fp32 product lies on an fp16 tie and the exact one beside it, the stored hi
+// and the hi that lo was taken against differ by an ulp, and hi + lo is off by that ulp (2^-10 relative):
+// zv_attn_na_kernel<3>'s out = acc * y, about one element in 10^5 (tests/test_gpu_attn_ref.py).  The
+// empty asm costs no instruction.
+__device__ __forceinline__ float split_pin(float v) {
+#ifdef ZV_OPERAND_F16
+  asm("" : "+v"(v));
+#endif
+  return v;
+}
+
 __device__ __forceinline__ void split_store(bf16* hi, bf16* lo, long i, float v) {
+  v = split_pin(v);
   const bf16 h = (bf16)v;
   hi[i] = h;
   if (lo) lo[i] = (bf16)(v - (float)h);
@@ -171,8 +186,9 @@ __device__ __forceinline__ void store_split4(bf16* hi, bf16* lo, long i, const f
   bf16x4 h, l;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    h[j] = (bf16)v[j];
-    l[j] = (bf16)(v[j] - (float)h[j]);
+    const float x = split_pin(v[j]);
+    h[j] = (bf16)x;
+    l[j] = (bf16)(x - (float)h[j]);
   }
   *reinterpret_cast<bf16x4*>(hi + i) = h;
   if (lo) *reinterpret_cast<bf16x4*>(lo + i) = l;
@@ -181,8 +197,9 @@ __device__ __forceinline__ void store_split8(bf16* hi, bf16* lo, long i, const f
   bf16x8 h, l;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    h[j] = (bf16)v[j];
-    l[j] = (bf16)(v[j] - (float)h[j]);
+    const float x = split_pin(v[j]);
+    h[j] = (bf16)x;
+    l[j] = (bf16)(x - (float)h[j]);
   }
   *reinterpret_cast<bf16x8*>(hi + i) = h;
   if (lo) *reinterpret_cast<bf16x8*>(lo + i) = l;

@@ -91,6 +91,16 @@ class ZvDwconvCheckArgs(ctypes.Structure):
         ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
 
 
+class ZvAttnCheckArgs(ctypes.Structure):
+    """zv_attn_check_args (test infrastructure; tests/test_gpu_attn_ref.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kind", "B", "L", "H", "nv", "split", "form", "b2", "guard", "vrows")] + [
+        ("stale", ctypes.c_float)] + [
+        (n, ctypes.c_void_p) for n in ("qkp", "P", "key_pad", "v", "y", "stats")] + [
+        ("oh", ctypes.c_void_p), ("ol", ctypes.c_void_p), ("oh2", ctypes.c_void_p), ("ldo", ctypes.c_int64),
+        ("Wh", ctypes.c_void_p), ("Wl", ctypes.c_void_p), ("ldw", ctypes.c_int64),
+        ("launch", ctypes.c_int * 8)]
+
+
 class ZvStackedgeCheckArgs(ctypes.Structure):
     """zv_stackedge_check_args (test infrastructure; tests/test_gpu_stackedge_ref.py)."""
     _fields_ = [(n, ctypes.c_int) for n in ("kind", "B", "L", "C", "ds", "guard", "rows_per_group")] + [
@@ -221,6 +231,8 @@ SIGNATURES = {
     "zv_host_block_count": (ctypes.c_int64, []),
     "zv_attn_fallbacks": (_I, [_P, _I, _P]),
     "zv_attn2_check": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P]),
+    "zv_attn2_check_stale": (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _F, _P, _P]),
+    "zv_attn_check": (_I, [ctypes.POINTER(ZvAttnCheckArgs)]),
     "zv_attn_plan": (_I, [_I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "zv_mx8_quantize": (_I, [_P, _I, _I, _P, _P]),
     "zv_mx8_gemm_check": (_I, [_I, _I, _I, _P, _P, _P, _P, _P]),
