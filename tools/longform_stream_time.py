@@ -227,8 +227,12 @@ def order():
     voc.decode_features = stamped("decode returned", real_decode)
 
     def push(js, idx, final):
-        wav, pl = lf._long_group(m, voc, [chunks[i] for i in idx], idx[0], pt, pf, 7, None, 1.0,
-                                 0.5, 16, 1.0, 0.1, 0.0)
+        nb = len(idx)
+        wav, pl = lf._long_group(m, voc, [chunks[i] for i in idx], [pt] * nb,
+                                 pf.expand(nb, -1, -1).contiguous(),
+                                 torch.full((nb,), pf.size(1), dtype=torch.int64, device=dev),
+                                 [7] * nb, idx, None, 0.1, 0.0, speed=1.0, t_shift=0.5, num_step=16,
+                                 guidance_scale=1.0)
         p = js.push_async(wav, pl.to(dev, torch.int32) * 256, None, final=final)
         marks.append((f"group {idx[0]}..{idx[-1]} pushed", time.perf_counter()))
         return p

@@ -93,8 +93,8 @@ def front(m, fx):
     dev = m.device
 
     def wav():
-        feats, nfr, _, _ = _prepare_prompts(items, fx, 0.1, dev)
-        return m.engine.speech_condition((feats + 0.0) * 0.1, nfr, MAX_FRAMES)
+        feats, nfr, _, _ = _prepare_prompts(items, fx, 0.1, 0.1, 0.0, dev)
+        return m.engine.speech_condition(feats, nfr, MAX_FRAMES)
 
     def voice():
         return store.gather(voices, MAX_FRAMES)[0]

@@ -24,7 +24,7 @@ from __future__ import annotations
 import datetime as dt
 import math
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -191,7 +191,7 @@ def edit_batch(items: Sequence[tuple], model, vocoder, feature_extractor, num_st
     frames -> ``edit_splice`` against the un-normalised resampled recording: everything outside
     the edits and the ``fade``-sample cross-fades around them is the recording's own samples,
     bit for bit, and a recording that was quieter than ``target_rms`` gets its level back on the
-    generated side (gain ``rms / target_rms``).  ``keep_original_audio=False`` returns the
+    generated side (gain ``infer.output_gain``).  ``keep_original_audio=False`` returns the
     vocoder's rendering of the whole row (one generated segment through the same splice).
 
     An item without spans comes back as its resampled input, bitwise, and is not sent to the
@@ -200,7 +200,7 @@ def edit_batch(items: Sequence[tuple], model, vocoder, feature_extractor, num_st
     one-channel Dialog models; the stereo model raises NotImplementedError."""
     import torch
 
-    from .infer import _prompt_rms_normalise, _resampler
+    from .infer import _prompt_rms_normalise, _prompts_at_rate, output_gain
     from .noise import check_keys
 
     if getattr(model.cfg, "stereo", False):
@@ -212,19 +212,8 @@ def edit_batch(items: Sequence[tuple], model, vocoder, feature_extractor, num_st
     sampling_rate = feature_extractor.config.sampling_rate
     hop = vocoder.cfg.hop_length
     with torch.inference_mode():
-        wavs = [torch.as_tensor(np.asarray(it[1]), dtype=torch.float32).reshape(-1) for it in items]
-        by_rate: Dict[int, List[int]] = {}
-        for i, it in enumerate(items):
-            if len(it) > 3 and int(it[3]) != sampling_rate:
-                by_rate.setdefault(int(it[3]), []).append(i)
-        for rate, idx in by_rate.items():
-            lens = [len(wavs[i]) for i in idx]
-            rb = torch.zeros((len(idx), max(lens)), dtype=torch.float32)
-            for r, i in enumerate(idx):
-                rb[r, :lens[r]] = wavs[i]
-            out, olens = _resampler(rate, sampling_rate).resample_batch(rb.to(dev), lens)
-            for r, i in enumerate(idx):
-                wavs[i] = out[r, :int(olens[r])].cpu()
+        wavs = [w.cpu() for w in _prompts_at_rate(
+            [it[1] for it in items], [it[3] if len(it) > 3 else None for it in items], sampling_rate, dev)]
         res: List[Optional[torch.Tensor]] = [None] * B
         todo = [i for i, it in enumerate(items) if len(it[2]) > 0]
         for i in range(B):
@@ -262,7 +251,7 @@ def edit_batch(items: Sequence[tuple], model, vocoder, feature_extractor, num_st
             else:
                 table, row_ptr = _stack([np.asarray([(0, 0, g, GENERATED)] if g else [],
                                                     np.int32).reshape(-1, 4) for g in gen_lens], 4)
-            gains = [v / target_rms if v < target_rms else 1.0 for v in rms]
+            gains = [output_gain(v, target_rms) for v in rms]
             out = model.engine.edit_splice(orig, Ns, gen, gen_lens, table, row_ptr, gains, fade)
             torch.cuda.synchronize(dev)
             t = (dt.datetime.now() - t0).total_seconds()

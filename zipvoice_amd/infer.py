@@ -23,7 +23,7 @@ import torch
 
 from .common import to_device
 from .models import per_row_schedule
-from .noise import check_keys
+from .noise import check_noise
 
 
 def get_feature_extractor(feature_type: str, num_channels: int = 1):
@@ -42,6 +42,24 @@ def _prompt_rms_normalise(wav: torch.Tensor, target_rms: float) -> Tuple[torch.T
     if rms < target_rms:
         wav = wav * target_rms / rms
     return wav, rms
+
+
+def restore_level(wav: torch.Tensor, rms: float, target_rms: float) -> torch.Tensor:
+    """The RMS restore (:399-400) on a waveform: two roundings per sample; ``wav`` itself at rms >= target."""
+    return wav * rms / target_rms if rms < target_rms else wav
+
+
+def output_gain(rms: float, target_rms: float) -> float:
+    """The restore as one factor, rounded before the joiner or the splice multiplies by it: not
+    ``restore_level``'s arithmetic."""
+    return rms / target_rms if rms < target_rms else 1.0
+
+
+def _finish_row(wav_row: torch.Tensor, n: int, level, target_rms: float) -> torch.Tensor:
+    """A decoded row as its request gets it: its first ``n`` samples at the prompt's level, (1, n).
+    ``level`` is the prompt's RMS on the host (a prompt wav) or its output gain on the device (a voice)."""
+    w = wav_row[:n]
+    return (w * level if torch.is_tensor(level) else restore_level(w, level, target_rms)).unsqueeze(0)
 
 
 _resamplers: Dict[Tuple[int, int], object] = {}
@@ -122,15 +140,9 @@ def generate_sentence(tokens: List[int], prompt_tokens: List[int], prompt_wav, m
     (``noise.seeded_normal``, stream 0): the same seed in a ``generate_batch`` row starts from
     the same noise.  Without it the noise comes from torch.randn, as before."""
     dev = model.device
-    w = torch.as_tensor(np.asarray(prompt_wav) if not torch.is_tensor(prompt_wav) else prompt_wav,
-                        dtype=torch.float32)
-    if w.dim() == 1:
-        w = w.unsqueeze(0)
-    if prompt_sampling_rate != sampling_rate:                      # :335-338, before the RMS
-        w = _resampler(prompt_sampling_rate, sampling_rate)(w.to(dev))
-    w, prompt_rms = _prompt_rms_normalise(w, target_rms)
-    feats = feature_extractor.extract(w.to(dev), sampling_rate=sampling_rate)
-    prompt_features = ((feats.unsqueeze(0) + feat_bias) * feat_scale).to(dev)
+    prompt_features, prompt_rms, _ = _prepare_prompt(
+        prompt_wav, prompt_sampling_rate, feature_extractor, dev, target_rms, feat_scale, feat_bias,
+        sampling_rate)
     prompt_features_lens = torch.tensor([prompt_features.size(1)], device=dev)
     torch.cuda.synchronize(dev)
     start_t = dt.datetime.now()
@@ -151,45 +163,67 @@ def generate_sentence(tokens: List[int], prompt_tokens: List[int], prompt_wav, m
     metrics = {"t": t, "t_no_vocoder": t_no_vocoder, "t_vocoder": t_vocoder,
                "wav_seconds": wav_seconds, "rtf": t / wav_seconds,
                "rtf_no_vocoder": t_no_vocoder / wav_seconds, "rtf_vocoder": t_vocoder / wav_seconds}
-    if prompt_rms < target_rms:
-        wav = wav * prompt_rms / target_rms
-    return wav, metrics
+    return restore_level(wav, prompt_rms, target_rms), metrics
 
 
-def _prepare_prompts(items: Sequence[tuple], feature_extractor, target_rms: float, dev):
-    """The prompts of items = [(tokens, prompt_tokens, prompt_wav[, prompt_sampling_rate]), ...]
-    as ``generate_batch`` prepares them: one batched resample per distinct rate, host RMS
-    normalisation, one ``extract_batch``.  Returns (features (B, T, n_mels) before scale and
-    bias, frame counts (B,) on the device, the prompts' RMS before normalisation, their
-    sample counts at the model's rate)."""
-    B = len(items)
-    sampling_rate = feature_extractor.config.sampling_rate
-    prompts = [torch.as_tensor(np.asarray(it[2]), dtype=torch.float32).reshape(-1) for it in items]
+def _prepare_prompt(prompt_wav, prompt_sampling_rate: int, feature_extractor, dev, target_rms: float,
+                    feat_scale: float, feat_bias: float, sampling_rate: int):
+    """One prompt as ``generate_sentence`` prepares it: resampled on the device when its rate is not
+    the model's (:335-338, before the RMS, which is then taken on the device too), RMS-normalised,
+    framed (a two-channel prompt keeps its channels for the extractor), scaled.  Returns
+    (prompt_features (1, P, F) on the device, the RMS before normalisation, the samples per channel
+    at the model's rate)."""
+    w = torch.as_tensor(np.asarray(prompt_wav) if not torch.is_tensor(prompt_wav) else prompt_wav,
+                        dtype=torch.float32)
+    if w.dim() == 1:
+        w = w.unsqueeze(0)
+    if prompt_sampling_rate != sampling_rate:
+        w = _resampler(prompt_sampling_rate, sampling_rate)(w.to(dev))
+    w, rms = _prompt_rms_normalise(w, target_rms)
+    feats = feature_extractor.extract(w.to(dev), sampling_rate=sampling_rate)
+    return ((feats.unsqueeze(0) + feat_bias) * feat_scale).to(dev), rms, w.shape[-1]
+
+
+def _prompts_at_rate(wavs: Sequence, rates: Sequence[Optional[int]], sampling_rate: int, dev
+                     ) -> List[torch.Tensor]:
+    """Host prompts (mono samples; ``rates[i]`` None: at ``sampling_rate``) -> one 1-D float32 row each
+    at ``sampling_rate``, where it already is: a prompt at the model's rate stays on the host (no GPU is
+    touched if all are), the others go up padded, one ``resample_batch`` per distinct rate, and are
+    returned as views of its output on ``dev``, cut to their lengths."""
+    rows = [torch.as_tensor(np.asarray(w), dtype=torch.float32).reshape(-1) for w in wavs]
     by_rate: Dict[int, List[int]] = {}
-    for i, it in enumerate(items):
-        if len(it) > 3 and int(it[3]) != sampling_rate:
-            by_rate.setdefault(int(it[3]), []).append(i)
+    for i, rate in enumerate(rates):
+        if rate is not None and int(rate) != sampling_rate:
+            by_rate.setdefault(int(rate), []).append(i)
     for rate, idx in by_rate.items():
-        lens = [len(prompts[i]) for i in idx]
+        lens = [len(rows[i]) for i in idx]
         rb = torch.zeros((len(idx), max(lens)), dtype=torch.float32)
         for r, i in enumerate(idx):
-            rb[r, :lens[r]] = prompts[i]
+            rb[r, :lens[r]] = rows[i]
         out, olens = _resampler(rate, sampling_rate).resample_batch(rb.to(dev), lens)
-        out = out.cpu()             # RMS + padding below are the 24 kHz items' host path
-        for r, i in enumerate(idx):
-            prompts[i] = out[r, :int(olens[r])]
-    wavs, rms = [], []
-    for w in prompts:
-        w, r = _prompt_rms_normalise(w, target_rms)
-        wavs.append(w)
-        rms.append(r)
+        for r, (i, n) in enumerate(zip(idx, olens.tolist())):
+            rows[i] = out[r, :n]
+    return rows
+
+
+def _prepare_prompts(items: Sequence[tuple], feature_extractor, target_rms: float, feat_scale: float,
+                     feat_bias: float, dev):
+    """The prompts of items = [(tokens, prompt_tokens, prompt_wav[, prompt_sampling_rate]), ...]
+    as ``generate_batch`` prepares them: one batched resample per distinct rate, host RMS
+    normalisation, one ``extract_batch``, scale and bias.  Returns (prompt features (B, T, n_mels),
+    frame counts (B,) on the device, the prompts' RMS before normalisation, their sample counts at
+    the model's rate)."""
+    rows = _prompts_at_rate([it[2] for it in items], [it[3] if len(it) > 3 else None for it in items],
+                            feature_extractor.config.sampling_rate, dev)
+    # (resampled rows come back: RMS + padding are the 24 kHz items' host path)
+    wavs, rms = zip(*[_prompt_rms_normalise(w.cpu(), target_rms) for w in rows])
     n = max(len(w) for w in wavs)
-    wb = torch.zeros((B, n), dtype=torch.float32)
+    wb = torch.zeros((len(wavs), n), dtype=torch.float32)
     for i, w in enumerate(wavs):
         wb[i, :len(w)] = w
     lens = torch.tensor([len(w) for w in wavs])
     feats, nfr = feature_extractor.extract_batch(wb.to(dev), lens)
-    return feats, nfr, rms, [len(w) for w in wavs]
+    return (feats + feat_bias) * feat_scale, nfr, list(rms), [len(w) for w in wavs]
 
 
 @torch.inference_mode()
@@ -231,10 +265,7 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
     the store's gains on the device (the row's gain of ``WavJoiner.trim`` under ``remove_long_sil``)."""
     dev = model.device
     B = len(items)
-    if seeds is not None:
-        if x0 is not None:
-            raise ValueError("give x0 or seeds, not both")
-        seeds, _ = check_keys(seeds, None, B)
+    seeds, _ = check_noise(B, x0, seeds)
     # (per-item settings are checked for their length here, before any GPU work)
     per_row_schedule(B, num_step=num_step, t_shift=t_shift, guidance_scale=guidance_scale, speed=speed)
     from .voices import Voice
@@ -245,19 +276,19 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
         store = items[0][1].store
         voices = [store.check(it[1]) for it in items]
         # the store holds (feats + feat_bias) * feat_scale of the normalised prompts: nothing to prepare
-        prompt_features, gains = store.gather(voices, max(v.frames for v in voices))
+        # (level: the output gains on the device; the wav items' is their prompts' RMS on the host)
+        prompt_features, level = store.gather(voices, max(v.frames for v in voices))
         nfr = to_device(torch.tensor([v.frames for v in voices]), dev)
-        prompt_tokens, rms = [list(v.prompt_tokens) for v in voices], None
+        prompt_tokens = [list(v.prompt_tokens) for v in voices]
     else:
-        feats, nfr, rms, _ = _prepare_prompts(items, feature_extractor, target_rms, dev)
-        prompt_features = (feats + feat_bias) * feat_scale
-        prompt_tokens, gains = [it[1] for it in items], None
+        prompt_features, nfr, level, _ = _prepare_prompts(items, feature_extractor, target_rms, feat_scale,
+                                                          feat_bias, dev)
+        prompt_tokens = [it[1] for it in items]
     if remove_long_sil:
         from .longform import WavJoiner
         joiner = joiner if joiner is not None else WavJoiner()
-        if gains is None:
-            gains = torch.tensor([r / target_rms if r < target_rms else 1.0 for r in rms],
-                                 dtype=torch.float32).to(dev)
+        gains = level if torch.is_tensor(level) else torch.tensor(
+            [output_gain(r, target_rms) for r in level], dtype=torch.float32).to(dev)
     torch.cuda.synchronize(dev)
     t0 = dt.datetime.now()
     pred, pred_lens, _, _ = model.sample(
@@ -270,8 +301,6 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
     if remove_long_sil:
         out, out_lens = joiner.trim(out, (pred_lens * vocoder.cfg.hop_length).to(torch.int32),
                                     gains)
-    elif rms is None:
-        out = out * gains[:, None]                  # the voices' RMS restore, on the device
     torch.cuda.synchronize(dev)
     t = (dt.datetime.now() - t0).total_seconds()
     if remove_long_sil:
@@ -280,11 +309,6 @@ def generate_batch(items: Sequence[tuple], model, vocoder,
         return ([out[i, :ns[i]].unsqueeze(0) for i in range(B)],
                 {"t": t, "wav_seconds": secs, "rtf": t / secs if secs else float("inf")})
     hop = vocoder.cfg.hop_length
-    res = []
-    for i in range(B):
-        w = out[i, :int(pred_lens[i]) * hop]
-        if rms is not None and rms[i] < target_rms:
-            w = w * rms[i] / target_rms
-        res.append(w.unsqueeze(0))
+    res = [_finish_row(out[i], n * hop, level[i], target_rms) for i, n in enumerate(pred_lens.tolist())]
     secs = float(pred_lens.sum()) * hop / 24000
     return res, {"t": t, "wav_seconds": secs, "rtf": t / secs}

@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import engine as _eng
-from .noise import check_keys
+from .noise import check_keys, check_noise
 
 
 # ------------------------------------------------------------------------------ chunker
@@ -406,41 +406,64 @@ def _long_prepare(tokens, prompt_tokens, prompt_wav, model, feature_extractor, b
     the prompt, prepared once as ``infer.generate_sentence`` does, and the text cut by
     ``chunk_budget`` and ``chunk_tokens``.  Returns (prompt_features (1, P, F) on the device,
     the prompt's RMS before normalisation, the chunks)."""
-    from .infer import _prompt_rms_normalise, _resampler
-    dev = model.device
-    w = torch.as_tensor(np.asarray(prompt_wav) if not torch.is_tensor(prompt_wav) else prompt_wav,
-                        dtype=torch.float32)
-    if w.dim() == 1:
-        w = w.unsqueeze(0)
-    if prompt_sampling_rate != sampling_rate:
-        w = _resampler(prompt_sampling_rate, sampling_rate)(w.to(dev))
-    w, prompt_rms = _prompt_rms_normalise(w, target_rms)
-    feats = feature_extractor.extract(w.to(dev), sampling_rate=sampling_rate)
-    prompt_features = ((feats.unsqueeze(0) + feat_bias) * feat_scale).to(dev)
-    budget = chunk_budget(len(prompt_tokens), w.shape[-1] / sampling_rate, max_seconds, speed)
+    from .infer import _prepare_prompt
+    prompt_features, prompt_rms, samples = _prepare_prompt(
+        prompt_wav, prompt_sampling_rate, feature_extractor, model.device, target_rms, feat_scale,
+        feat_bias, sampling_rate)
+    budget = chunk_budget(len(prompt_tokens), samples / sampling_rate, max_seconds, speed)
     chunks = chunk_tokens(tokens, break_ids, budget, soft_break_ids)
     if not chunks:
         raise ValueError("no tokens to synthesise")
     return prompt_features, prompt_rms, chunks
 
 
-def _long_group(model, vocoder, grp, first, prompt_tokens, prompt_features, seed, x0, speed,
-                t_shift, num_step, guidance_scale, feat_scale, feat_bias):
-    """One group of consecutive chunks, ``grp[i]`` being chunk ``first + i`` of the text:
-    ``model.sample`` on rows that repeat the prompt (with a seed, row i draws from
-    (seed, stream = first + i)), then the vocoder.  Returns (wavs (nb, n), frames (nb,))."""
-    nb, dev, P = len(grp), model.device, prompt_features.size(1)
+def _long_group(model, vocoder, tokens, prompt_tokens, prompt_features, prompt_frames, seeds,
+                streams, x0, feat_scale, feat_bias, **settings):
+    """One group of chunks, whose rows may belong to different requests: row i speaks ``tokens[i]``
+    after the prompt ``prompt_tokens[i]`` / ``prompt_features[i, :prompt_frames[i]]`` (frames on the
+    device) and, with ``seeds``, draws from (seeds[i], streams[i]).  One ``model.sample`` with ``settings``
+    (speed, t_shift, num_step, guidance_scale), then the vocoder.  Returns (wavs (nb, n), frames (nb,))."""
     pred, pred_lens, _, _ = model.sample(
-        tokens=grp, prompt_tokens=[prompt_tokens] * nb,
-        prompt_features=prompt_features.expand(nb, -1, -1).contiguous(),
-        prompt_features_lens=torch.full((nb,), P, dtype=torch.int64, device=dev),
-        speed=speed, t_shift=t_shift, duration="predict", num_step=num_step,
-        guidance_scale=guidance_scale, x0=x0,
-        seeds=None if seed is None else [seed] * nb,
-        seed_streams=None if seed is None else list(range(first, first + nb)))
+        tokens=tokens, prompt_tokens=prompt_tokens, prompt_features=prompt_features,
+        prompt_features_lens=prompt_frames, duration="predict", x0=x0, seeds=seeds,
+        seed_streams=streams, **settings)
     wav = vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale, feat_bias=feat_bias,
                                   clamp=True)
     return wav, pred_lens
+
+
+def _long_run(model, vocoder, plan, prompt_tokens, prompt_features, prompt_frames, seeds, x0,
+              feat_scale, feat_bias, **settings):
+    """The groups of ``plan`` through ``_long_group``.  Request d has the prompt ``prompt_tokens[d]`` /
+    ``prompt_features[d]`` of ``prompt_frames[d]`` frames (host ints) and the seed ``seeds[d]`` (``seeds``
+    None: torch.randn); chunk k of a request, in text order, draws from stream k; ``x0`` is None or one
+    tensor per group.  Returns (the decoded rows as one (K, n) batch in join order, their host lengths)."""
+    if x0 is not None and len(x0) != len(plan.groups):
+        raise ValueError(f"x0 must hold one tensor per sample() call ({len(plan.groups)}), got {len(x0)}")
+    dev = model.device
+    nfr = torch.tensor(prompt_frames, dtype=torch.int64, device=dev)
+    # chunk i is chunk i - first[doc_of[i]] of its request (join order is text by text)
+    first = [sum(plan.doc_sizes[:d]) for d in range(len(plan.doc_sizes))]
+    wavs, lens, rows = [], [], []
+    for gi, grp in enumerate(plan.groups):
+        docs = [plan.doc_of[i] for i in grp]
+        di = torch.tensor(docs, dtype=torch.int64, device=dev)
+        wav, pred_lens = _long_group(
+            model, vocoder, [plan.chunks[i] for i in grp], [prompt_tokens[d] for d in docs],
+            prompt_features.index_select(0, di)[:, :max(prompt_frames[d] for d in docs)].contiguous(),
+            nfr.index_select(0, di), None if seeds is None else [seeds[d] for d in docs],
+            None if seeds is None else [i - first[plan.doc_of[i]] for i in grp],
+            None if x0 is None else x0[gi], feat_scale, feat_bias, **settings)
+        wavs.append(wav)
+        lens.append(pred_lens)
+        rows.append(torch.tensor(grp, dtype=torch.int64, device=dev))
+    K, n = len(plan.chunks), max(x.shape[1] for x in wavs)
+    batch = torch.zeros((K, n), dtype=torch.float32, device=dev)
+    for x, r in zip(wavs, rows):                      # group order -> join order
+        batch[:, :x.shape[1]].index_copy_(0, r, x)
+    lens_dev = torch.empty(K, dtype=torch.int64, device=dev).index_copy_(
+        0, torch.cat(rows), torch.cat(lens).to(torch.int64))
+    return batch, [int(v) * vocoder.cfg.hop_length for v in lens_dev.tolist()]
 
 
 @torch.inference_mode()
@@ -467,6 +490,7 @@ def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model
     per-chunk gain.  Returns (wav (1, N) on the device, metrics with t, wav_seconds, rtf,
     num_chunks, num_batches); with ``return_chunks`` also the list of per-chunk waveforms
     (untrimmed, before the gain) and the joiner's spans."""
+    from .infer import output_gain
     if seed is not None:
         if x0 is not None:
             raise ValueError("give x0 or seed, not both")
@@ -475,39 +499,24 @@ def generate_long(tokens: List[int], prompt_tokens: List[int], prompt_wav, model
     prompt_features, prompt_rms, chunks = _long_prepare(
         tokens, prompt_tokens, prompt_wav, model, feature_extractor, break_ids, soft_break_ids,
         max_seconds, speed, target_rms, feat_scale, feat_bias, sampling_rate, prompt_sampling_rate)
-    groups = [chunks[i:i + batch_size] for i in range(0, len(chunks), int(batch_size))]
-    if x0 is not None and len(x0) != len(groups):
-        raise ValueError(f"x0 must hold one tensor per sample() call ({len(groups)}), got {len(x0)}")
+    # the one-text plan: ``plan_long_batch``'s without sorting (frames are not needed: nothing is sorted)
+    K, bs = len(chunks), int(batch_size)
+    plan = LongPlan(chunks, [K], [0] * K, None, [list(range(i, min(i + bs, K))) for i in range(0, K, bs)])
     joiner = joiner if joiner is not None else WavJoiner()
-    hop = vocoder.cfg.hop_length
 
     torch.cuda.synchronize(dev)
     t0 = dt.datetime.now()
-    wavs, lens = [], []
-    for gi, grp in enumerate(groups):
-        wav, pred_lens = _long_group(
-            model, vocoder, grp, gi * int(batch_size), prompt_tokens, prompt_features, seed,
-            None if x0 is None else x0[gi], speed, t_shift, num_step, guidance_scale, feat_scale,
-            feat_bias)
-        wavs.append(wav)
-        lens.append(pred_lens)
-    lens_host = [int(v) * hop for v in torch.cat(lens).tolist()]
-    K, n = len(chunks), max(x.shape[1] for x in wavs)
-    if len(wavs) == 1:
-        batch = wavs[0]
-    else:
-        batch = torch.zeros((K, n), dtype=torch.float32, device=dev)
-        r = 0
-        for x in wavs:
-            batch[r:r + x.shape[0], :x.shape[1]] = x
-            r += x.shape[0]
-    gains = [prompt_rms / target_rms] * K if prompt_rms < target_rms else None
+    batch, lens_host = _long_run(
+        model, vocoder, plan, [prompt_tokens], prompt_features, [prompt_features.size(1)],
+        None if seed is None else [seed], x0, feat_scale, feat_bias, speed=speed, t_shift=t_shift,
+        num_step=num_step, guidance_scale=guidance_scale)
+    gains = [output_gain(prompt_rms, target_rms)] * K if prompt_rms < target_rms else None
     out, spans = joiner(batch, lens_host, gains)
     torch.cuda.synchronize(dev)
     t = (dt.datetime.now() - t0).total_seconds()
     secs = out.shape[1] / sampling_rate
     metrics = {"t": t, "wav_seconds": secs, "rtf": t / secs if secs else float("inf"),
-               "num_chunks": K, "num_batches": len(groups)}
+               "num_chunks": K, "num_batches": len(plan.groups)}
     if return_chunks:
         return out, metrics, [batch[i, :lens_host[i]] for i in range(K)], spans
     return out, metrics
@@ -559,6 +568,7 @@ def generate_long_stream(tokens: List[int], prompt_tokens: List[int], prompt_wav
     ``generate_long`` takes its ``t``, to this piece's completion: the first yield's ``t`` is
     the time to first audio); with ``return_chunks`` also chunks (the group's waveforms,
     untrimmed, before the gain) and spans (m_b, off_b relative to the piece, F_b)."""
+    from .infer import output_gain
     if seed is not None:
         seed = check_keys([seed])[0][0]
     dev = model.device
@@ -569,7 +579,8 @@ def generate_long_stream(tokens: List[int], prompt_tokens: List[int], prompt_wav
     groups = stream_groups(K, first_batch, batch_size)
     joiner = joiner if joiner is not None else WavJoiner()
     hop = vocoder.cfg.hop_length
-    gain = prompt_rms / target_rms if prompt_rms < target_rms else None
+    gain = output_gain(prompt_rms, target_rms) if prompt_rms < target_rms else None
+    P = prompt_features.size(1)
 
     js = joiner.stream(1, device=dev)
     torch.cuda.synchronize(dev)
@@ -577,9 +588,14 @@ def generate_long_stream(tokens: List[int], prompt_tokens: List[int], prompt_wav
 
     def queue(gi):
         idx = groups[gi]
+        nb = len(idx)                                        # rows that repeat the one prompt
         wav, pred_lens = _long_group(
-            model, vocoder, [chunks[i] for i in idx], idx[0], prompt_tokens, prompt_features,
-            seed, None, speed, t_shift, num_step, guidance_scale, feat_scale, feat_bias)
+            model, vocoder, [chunks[i] for i in idx], [prompt_tokens] * nb,
+            prompt_features.expand(nb, -1, -1).contiguous(),
+            torch.full((nb,), P, dtype=torch.int64, device=dev),
+            None if seed is None else [seed] * nb, None if seed is None else idx, None,
+            feat_scale, feat_bias, speed=speed, t_shift=t_shift, num_step=num_step,
+            guidance_scale=guidance_scale)
         lens = pred_lens.to(dev, torch.int32) * hop          # stays on the device: no wait here
         return wav, lens, js.push_async(wav, lens, None if gain is None else [gain] * len(idx),
                                         final=gi == len(groups) - 1)
@@ -686,60 +702,30 @@ def generate_long_batch(requests: Sequence[tuple], model, vocoder, feature_extra
     Returns (a list of R waveforms (1, N_d) on the device, metrics with t, wav_seconds, rtf,
     num_chunks, num_batches, num_requests); with ``return_chunks`` also the per-chunk
     waveforms in join order (untrimmed, before the gain), the joiner's spans and the plan."""
-    from .infer import _prepare_prompts
+    from .infer import _prepare_prompts, output_gain
     dev = model.device
     R = len(requests)
     if R == 0:
         raise ValueError("no requests to synthesise")
-    if seeds is not None:
-        if x0 is not None:
-            raise ValueError("give x0 or seeds, not both")
-        seeds, _ = check_keys(seeds, None, R)
+    seeds, _ = check_noise(R, x0, seeds)
     sampling_rate = feature_extractor.config.sampling_rate
-    feats, nfr, rms, nsamp = _prepare_prompts(requests, feature_extractor, target_rms, dev)
-    prompt_features = (feats + feat_bias) * feat_scale
+    prompt_features, nfr, rms, nsamp = _prepare_prompts(requests, feature_extractor, target_rms,
+                                                        feat_scale, feat_bias, dev)
     plan = plan_long_batch([r[0] for r in requests], [len(r[1]) for r in requests], nsamp,
                            break_ids, soft_break_ids, max_seconds, batch_size, speed,
                            sort_by_length, sampling_rate, feature_extractor.config.hop_length)
-    if x0 is not None and len(x0) != len(plan.groups):
-        raise ValueError(f"x0 must hold one tensor per sample() call ({len(plan.groups)}), got "
-                         f"{len(x0)}")
     joiner = joiner if joiner is not None else WavJoiner()
-    hop = vocoder.cfg.hop_length
     K = len(plan.chunks)
     P = [int(v) for v in nfr.tolist()]
-    # chunk i is chunk i - first[doc_of[i]] of its request (join order is text by text)
-    first = [sum(plan.doc_sizes[:d]) for d in range(R)]
 
     torch.cuda.synchronize(dev)
     t0 = dt.datetime.now()
-    wavs, lens, rows = [], [], []
-    for gi, grp in enumerate(plan.groups):
-        docs = [plan.doc_of[i] for i in grp]
-        di = torch.tensor(docs, dtype=torch.int64, device=dev)
-        pred, pred_lens, _, _ = model.sample(
-            tokens=[plan.chunks[i] for i in grp], prompt_tokens=[requests[d][1] for d in docs],
-            prompt_features=prompt_features.index_select(0, di)[:, :max(P[d] for d in docs)]
-            .contiguous(),
-            prompt_features_lens=nfr.index_select(0, di), speed=speed, t_shift=t_shift,
-            duration="predict", num_step=num_step, guidance_scale=guidance_scale,
-            x0=None if x0 is None else x0[gi],
-            seeds=None if seeds is None else [seeds[d] for d in docs],
-            seed_streams=None if seeds is None else [i - first[plan.doc_of[i]] for i in grp])
-        wavs.append(vocoder.decode_features(pred, pred_lens, feat_scale=feat_scale,
-                                            feat_bias=feat_bias, clamp=True))
-        lens.append(pred_lens)
-        rows.append(torch.tensor(grp, dtype=torch.int64, device=dev))
-    n = max(x.shape[1] for x in wavs)
-    batch = torch.zeros((K, n), dtype=torch.float32, device=dev)
-    for x, r in zip(wavs, rows):                      # group order -> join order
-        batch[:, :x.shape[1]].index_copy_(0, r, x)
-    lens_dev = torch.empty(K, dtype=torch.int64, device=dev).index_copy_(
-        0, torch.cat(rows), torch.cat(lens).to(torch.int64))
-    lens_host = [int(v) * hop for v in lens_dev.tolist()]
+    batch, lens_host = _long_run(
+        model, vocoder, plan, [r[1] for r in requests], prompt_features, P, seeds, x0, feat_scale,
+        feat_bias, speed=speed, t_shift=t_shift, num_step=num_step, guidance_scale=guidance_scale)
     gains = None
     if any(r < target_rms for r in rms):
-        gains = [rms[d] / target_rms if rms[d] < target_rms else 1.0 for d in plan.doc_of]
+        gains = [output_gain(rms[d], target_rms) for d in plan.doc_of]
     outs, spans = joiner.join_docs(batch, lens_host, plan.doc_sizes, gains)
     torch.cuda.synchronize(dev)
     t = (dt.datetime.now() - t0).total_seconds()

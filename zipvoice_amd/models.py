@@ -25,7 +25,7 @@ import torch
 from .common import make_pad_mask, pad_labels, predict_features_lens, speaker_turn_indices, to_device
 from .config import ModelConfig
 from .engine import HipEngine, padding_id
-from .noise import check_keys, seeded_normal
+from .noise import check_noise, initial_noise
 from .solver import DistillEulerSolver, EulerSolver, RowSchedule
 from .weights import check_state_dict, load_checkpoint_state_dict, synthetic_state_dict
 
@@ -233,12 +233,7 @@ class ZipVoice:
         sequence of one value per row: the batch then runs as one scheduled solve
         (``solver.sample_rows``), every row with its own settings.  Scalars, and the
         reference's (batch, 1, 1) guidance tensor, take the unscheduled path."""
-        if seeds is not None and x0 is not None:
-            raise ValueError("give x0 or seeds, not both")
-        if seed_streams is not None and seeds is None:
-            raise ValueError("seed_streams needs seeds")
-        if seeds is not None:
-            seeds, seed_streams = check_keys(seeds, seed_streams, len(tokens))
+        check_noise(len(tokens), x0, seeds, seed_streams)
         eng = self._need_engine()
         # per-request settings: a sequence of one value per row for any of these four sends the
         # batch through the scheduled solve (solver.sample_rows), the others broadcast
@@ -260,31 +255,31 @@ class ZipVoice:
                 prompt_features_lens=prompt_features_lens)
         batch_size, num_frames, _ = text_condition.shape
         speech_condition = eng.speech_condition(prompt_features, prompt_features_lens, num_frames)
-        F = prompt_features.size(-1)
-        if seeds is not None:
-            x0 = seeded_normal(seeds, (num_frames, F), seed_streams, device=self.device)
-        elif x0 is None:
-            x0 = torch.randn(batch_size, num_frames, F, device=self.device)
-        elif tuple(x0.shape) != (batch_size, num_frames, F):
-            raise ValueError(f"x0 must have shape {(batch_size, num_frames, F)}, got "
-                             f"{tuple(x0.shape)}")
+        x0 = initial_noise(batch_size, num_frames, prompt_features.size(-1), self.device, x0, seeds,
+                           seed_streams)
         # the output shapes are known before sampling: reading them here (the text path has
         # already synchronised for num_frames) keeps the host from waiting on the Euler loop,
         # so the prompt split and the vocoder are queued behind it without an idle gap
         x1_wo_prompt_lens = (~padding_mask).sum(-1) - prompt_features_lens
         Tg, Tp = (int(v) for v in torch.stack([x1_wo_prompt_lens.max(),
                                                 prompt_features_lens.max()]).tolist())
-        if schedule is not None:
-            x1 = self.solver.sample_rows(x=x0, text_condition=text_condition,
-                                         speech_condition=speech_condition,
-                                         padding_mask=padding_mask, schedule=schedule)
-        else:
-            x1 = self.solver.sample(x=x0, text_condition=text_condition,
-                                    speech_condition=speech_condition, padding_mask=padding_mask,
-                                    num_step=num_step, guidance_scale=guidance_scale,
-                                    t_shift=t_shift)
+        x1 = self._solve(x0, text_condition, speech_condition, padding_mask, schedule, num_step,
+                         guidance_scale, t_shift)
         return split_prompt(x1, prompt_features_lens, x1_wo_prompt_lens, Tg, Tp) + (
             prompt_features_lens,)
+
+    def _solve(self, x0, text_condition, speech_condition, padding_mask, schedule, num_step,
+               guidance_scale, t_shift, t_start: float = 0.0, t_end: float = 1.0):
+        """The solve of ``sample`` and ``sample_edit``: the scheduled one when ``schedule`` holds one
+        ``RowSchedule`` per row, the plain one with the scalar settings when it is None."""
+        if schedule is not None:
+            return self.solver.sample_rows(x=x0, text_condition=text_condition,
+                                           speech_condition=speech_condition,
+                                           padding_mask=padding_mask, schedule=schedule)
+        return self.solver.sample(x=x0, text_condition=text_condition,
+                                  speech_condition=speech_condition, padding_mask=padding_mask,
+                                  num_step=num_step, guidance_scale=guidance_scale,
+                                  t_start=t_start, t_end=t_end, t_shift=t_shift)
 
     # ------------------------------------------------------------------ editing
     def sample_edit(self, tokens: List[List[int]], features: torch.Tensor,
@@ -309,14 +304,9 @@ class ZipVoice:
         Returns (x1 (B, T, F), the new lengths (B,), mask (B, T) bool: True on generated
         frames)."""
         from .edit import plan_edit_batch
-        if seeds is not None and x0 is not None:
-            raise ValueError("give x0 or seeds, not both")
-        if seed_streams is not None and seeds is None:
-            raise ValueError("seed_streams needs seeds")
-        if seeds is not None:
-            seeds, seed_streams = check_keys(seeds, seed_streams, len(tokens))
-        eng = self._need_engine()
         B = len(tokens)
+        check_noise(B, x0, seeds, seed_streams)
+        eng = self._need_engine()
         schedule = per_row_schedule(B, num_step=num_step, t_shift=t_shift,
                                     guidance_scale=guidance_scale, speed=1.0)
         if features.dim() != 3 or features.size(0) != B:
@@ -331,24 +321,13 @@ class ZipVoice:
         num_frames, F = text_condition.size(1), features.size(-1)
         speech_condition, mask = eng.edit_gather(features, plan.lens, plan.table, plan.row_ptr,
                                                  num_frames)
-        if seeds is not None:
-            x0 = seeded_normal(seeds, (num_frames, F), seed_streams, device=self.device)
-        elif x0 is None:
-            x0 = torch.randn(B, num_frames, F, device=self.device)
-        elif tuple(x0.shape) != (B, num_frames, F):
-            raise ValueError(f"x0 must have shape {(B, num_frames, F)}, got {tuple(x0.shape)}")
-        if schedule is not None:
-            rows = [RowSchedule(num_step=r.num_step, guidance_scale=r.guidance_scale,
-                                t_start=float(t_start), t_end=float(t_end), t_shift=r.t_shift)
-                    for r in schedule[0]]
-            x1 = self.solver.sample_rows(x=x0, text_condition=text_condition,
-                                         speech_condition=speech_condition,
-                                         padding_mask=padding_mask, schedule=rows)
-        else:
-            x1 = self.solver.sample(x=x0, text_condition=text_condition,
-                                    speech_condition=speech_condition, padding_mask=padding_mask,
-                                    num_step=num_step, guidance_scale=guidance_scale,
-                                    t_start=float(t_start), t_end=float(t_end), t_shift=t_shift)
+        x0 = initial_noise(B, num_frames, F, self.device, x0, seeds, seed_streams)
+        if schedule is not None:                # (speed plays no part: the lengths are the plan's)
+            schedule = [RowSchedule(num_step=r.num_step, guidance_scale=r.guidance_scale,
+                                    t_start=float(t_start), t_end=float(t_end), t_shift=r.t_shift)
+                        for r in schedule[0]]
+        x1 = self._solve(x0, text_condition, speech_condition, padding_mask, schedule, num_step,
+                         guidance_scale, t_shift, float(t_start), float(t_end))
         if keep_original:
             x1, _ = eng.edit_gather(features, plan.lens, plan.table, plan.row_ptr, num_frames,
                                     fill=x1)

@@ -53,6 +53,21 @@ def check_keys(seeds, streams=None, rows: Optional[int] = None
     return seeds, streams
 
 
+def check_noise(rows: int, x0=None, seeds=None, streams=None):
+    """The checks every entry that takes ``x0`` / ``seeds`` / ``seed_streams`` makes before it touches
+    the GPU: ``x0`` or ``seeds``, not both; ``streams`` only with ``seeds``; then ``check_keys``.
+    ``seeds`` may hold None for rows without a key.  Returns (seeds, streams) as checked lists."""
+    if seeds is not None and x0 is not None:
+        raise ValueError("give x0 or seeds, not both")
+    if streams is not None and seeds is None:
+        raise ValueError("seed_streams needs seeds")
+    if seeds is None:
+        return None, None
+    holes = isinstance(seeds, (list, tuple)) and None in seeds
+    keys, streams = check_keys([0 if s is None else s for s in seeds] if holes else seeds, streams, rows)
+    return ([None if s is None else k for s, k in zip(seeds, keys)] if holes else keys), streams
+
+
 def _twos(v: int, bits: int) -> int:
     return v - (1 << bits) if v >= 1 << (bits - 1) else v
 
@@ -110,3 +125,22 @@ def seeded_normal(seeds: Sequence[int], shape, streams: Optional[Sequence[int]] 
         dev = torch.device("cuda", torch.cuda.current_device())
     out = torch.empty((len(seeds),) + shape, dtype=torch.float32, device=dev)
     return seeded_normal_into(out, seeds, streams)
+
+
+def initial_noise(B: int, T: int, F: int, device, x0=None, seeds=None, streams=None) -> torch.Tensor:
+    """The (B, T, F) initial noise of a solve, after ``check_noise``: ``x0`` itself (a ValueError at
+    another shape); every row keyed: ``seeded_normal``; none keyed: ``torch.randn`` on ``device``, as the
+    reference draws it; some keyed (``seeds`` holds None for the others): ``torch.randn`` for the whole
+    batch, then each keyed row overwritten in place (no index tensor goes up; a key's noise is its own)."""
+    seeds, streams = check_noise(B, x0, seeds, streams)
+    if x0 is not None:
+        if tuple(x0.shape) != (B, T, F):
+            raise ValueError(f"x0 must have shape {(B, T, F)}, got {tuple(x0.shape)}")
+        return x0
+    keyed = [b for b, s in enumerate(seeds or ()) if s is not None]
+    if keyed and len(keyed) == B:
+        return seeded_normal(seeds, (T, F), streams, device=device)
+    x = torch.randn(B, T, F, device=device)
+    for b in keyed:
+        seeded_normal_into(x[b:b + 1], [seeds[b]], None if streams is None else [streams[b]])
+    return x

@@ -14,17 +14,37 @@ with per-item settings.  The reference has no counterpart.
 from __future__ import annotations
 
 import collections
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
 from .common import predict_features_lens, to_device
 from .feature import compute_num_frames
-from .infer import _prepare_prompts, _resampler
+from .infer import _finish_row, _prepare_prompts, _resampler
 from .models import per_row_schedule, split_prompt
-from .noise import check_keys, seeded_normal, seeded_normal_into
+from .noise import check_keys, initial_noise
 from .voices import Voice
+
+
+class _Request(NamedTuple):
+    """Queued.  ``item``: (tokens, prompt_tokens, prompt_wav[, rate]) or (tokens, Voice); ``total``: ``_frames``'s."""
+    ticket: int
+    item: tuple
+    num_step: int
+    guidance_scale: float
+    speed: float
+    t_shift: float
+    seed: Optional[int]
+    total: int
+
+
+class _Row(NamedTuple):
+    """In flight.  ``level`` (``infer._finish_row``): the prompt's RMS on the host, or a voice's gain on the device."""
+    ticket: int
+    frames: int
+    prompt_frames: int
+    level: Union[float, torch.Tensor]
 
 
 class ContinuousBatcher:
@@ -59,8 +79,7 @@ class ContinuousBatcher:
         self.voices = voices
         self.session = model.solver.open_session(self.max_rows, self.max_frames)
         self._queue = collections.deque()
-        # slot -> (ticket, frames, prompt frames, prompt rms: a host float, or the output gain on the device)
-        self._rows = {}
+        self._rows = {}                                      # slot -> _Row
         self._next_ticket = 0
         self._done: List[Tuple[int, torch.Tensor]] = []      # retired, not yet returned by step()
         self.last_mel: List[Tuple[int, torch.Tensor]] = []   # (ticket, mel (T_i, n_mels)) of the last retire
@@ -68,9 +87,9 @@ class ContinuousBatcher:
     def close(self) -> None:
         """Close the session; the requests still queued are given up (their voices are free to be dropped)."""
         while self._queue:
-            item = self._queue.popleft()[1]
-            if isinstance(item[1], Voice):
-                self.voices.release(item[1])
+            voice = self._queue.popleft().item[1]
+            if isinstance(voice, Voice):
+                self.voices.release(voice)
         self.session.close()
 
     def _frames(self, tokens, prompt_tokens, prompt_wav, prompt_sampling_rate, speed, voice=None) -> Tuple[int, int]:
@@ -117,8 +136,8 @@ class ContinuousBatcher:
         else:
             item = (list(tokens), list(prompt_tokens), prompt_wav) + (
                 () if prompt_sampling_rate is None else (int(prompt_sampling_rate),))
-        self._queue.append((ticket, item, int(num_step), float(guidance_scale), float(speed), float(t_shift), seed,
-                            total))
+        self._queue.append(_Request(ticket, item, int(num_step), float(guidance_scale), float(speed), float(t_shift),
+                                    seed, total))
         return ticket
 
     def pending(self) -> Tuple[int, int]:
@@ -134,22 +153,15 @@ class ContinuousBatcher:
         dev = self.model.device
         rows = [self._rows.pop(s) for s in slots]
         x1 = self.session.retire(slots)
-        plens = to_device(torch.tensor([r[2] for r in rows]), dev)
-        glens = to_device(torch.tensor([r[1] - r[2] for r in rows]), dev)
-        pred, pred_lens, _ = split_prompt(x1, plens, glens, max(r[1] - r[2] for r in rows), max(r[2] for r in rows))
+        plens = to_device(torch.tensor([r.prompt_frames for r in rows]), dev)
+        gen = [r.frames - r.prompt_frames for r in rows]
+        pred, pred_lens, _ = split_prompt(x1, plens, to_device(torch.tensor(gen), dev), max(gen),
+                                          max(r.prompt_frames for r in rows))
         wav = self.vocoder.decode_features(pred, pred_lens, feat_scale=self.feat_scale, feat_bias=self.feat_bias,
                                            clamp=True)
-        hop = self.vocoder.cfg.hop_length
-        out, self.last_mel = [], []
-        for i, (ticket, frames, p, rms) in enumerate(rows):
-            w = wav[i, :(frames - p) * hop]
-            if torch.is_tensor(rms):                      # a voice's row: its gain, already on the device
-                w = w * rms
-            elif rms < self.target_rms:
-                w = w * rms / self.target_rms
-            out.append((ticket, w.unsqueeze(0)))
-            self.last_mel.append((ticket, pred[i, :frames - p]))
-        return out
+        self.last_mel = [(r.ticket, pred[i, :n]) for i, (r, n) in enumerate(zip(rows, gen))]
+        return [(r.ticket, _finish_row(wav[i], n * self.vocoder.cfg.hop_length, r.level, self.target_rms))
+                for i, (r, n) in enumerate(zip(rows, gen))]
 
     @torch.inference_mode()
     def _admit(self) -> None:
@@ -159,74 +171,58 @@ class ContinuousBatcher:
         if n == 0:
             return
         # (a group is all voices or all wavs: the leading run of the kind at the head of the queue)
-        by_voice = isinstance(self._queue[0][1][1], Voice)
-        n = next((i for i in range(n) if isinstance(self._queue[i][1][1], Voice) != by_voice), n)
+        by_voice = isinstance(self._queue[0].item[1], Voice)
+        n = next((i for i in range(n) if isinstance(self._queue[i].item[1], Voice) != by_voice), n)
         # (the requests stay queued until the session has taken them: a failure below loses none)
         reqs = [self._queue[i] for i in range(n)]
-        if by_voice:
-            return self._admit_voices(reqs, free[:n])
         m, dev = self.model, self.model.device
-        items = [r[1] for r in reqs]
-        feats, nfr, rms, _ = _prepare_prompts(items, self.fx, self.target_rms, dev)
-        prompt_features = (feats + self.feat_bias) * self.feat_scale
-        schedule, speeds = per_row_schedule(n, num_step=[r[2] for r in reqs], guidance_scale=[r[3] for r in reqs],
-                                            speed=[r[4] for r in reqs], t_shift=[r[5] for r in reqs])
-        tc, pm = m.forward_text_inference_ratio_duration(
-            tokens=[it[0] for it in items], prompt_tokens=[it[1] for it in items], prompt_features_lens=nfr,
-            speed=torch.tensor(speeds, dtype=torch.float32, device=dev))
-        T_in = tc.shape[1]
-        sc = m.engine.speech_condition(prompt_features, nfr, T_in)
+        schedule, speeds = per_row_schedule(n, num_step=[r.num_step for r in reqs],
+                                            guidance_scale=[r.guidance_scale for r in reqs],
+                                            speed=[r.speed for r in reqs], t_shift=[r.t_shift for r in reqs])
+
+        def text(prompt_tokens, prompt_frames, num_frames=None):
+            return m.forward_text_inference_ratio_duration(
+                tokens=[r.item[0] for r in reqs], prompt_tokens=prompt_tokens, prompt_features_lens=prompt_frames,
+                speed=to_device(torch.tensor(speeds, dtype=torch.float32), dev), num_frames=num_frames)
+
+        tc, sc, lens, prompt_frames, level = (self._voice_group if by_voice else self._wav_group)(reqs, text)
+        x0 = initial_noise(n, tc.shape[1], sc.size(-1), dev, seeds=[r.seed for r in reqs])
+        self.session.admit(free[:n], x0, tc, sc, lens, schedule)
+        for i, (s, r) in enumerate(zip(free, reqs)):
+            self._queue.popleft()
+            if by_voice:
+                self.voices.release(r.item[1])
+            self._rows[s] = _Row(r.ticket, lens[i], prompt_frames[i], level[i])
+
+    def _wav_group(self, reqs, text):
+        """(text condition, speech condition, frames, prompt frames, the prompts' RMS) of a group whose
+        requests carry prompt wavs: the prompts prepared as ``infer.generate_batch`` prepares them, the lengths
+        read back from the text condition's mask."""
+        items = [r.item for r in reqs]
+        prompt_features, nfr, rms, _ = _prepare_prompts(items, self.fx, self.target_rms, self.feat_scale,
+                                                        self.feat_bias, self.model.device)
+        tc, pm = text([it[1] for it in items], nfr)
+        sc = self.model.engine.speech_condition(prompt_features, nfr, tc.shape[1])
         lens = (~pm).sum(-1).tolist()
         long = [i for i, v in enumerate(lens) if v > self.max_frames]
         if long:                                          # submit's host count was short: drop it, keep the rest queued
             del self._queue[long[0]]
-            raise ValueError(f"request {reqs[long[0]][0]} has {lens[long[0]]} frames, more than max_frames "
+            raise ValueError(f"request {reqs[long[0]].ticket} has {lens[long[0]]} frames, more than max_frames "
                              f"({self.max_frames}); it was dropped")
-        F = prompt_features.size(-1)
-        seeds = [r[6] for r in reqs]
-        if all(s is not None for s in seeds):
-            x0 = seeded_normal(seeds, (T_in, F), device=dev)
-        else:
-            x0 = torch.randn(n, T_in, F, device=dev)
-            keyed = [i for i, s in enumerate(seeds) if s is not None]
-            if keyed:
-                x0[keyed] = seeded_normal([seeds[i] for i in keyed], (T_in, F), device=dev)
-        slots = free[:n]
-        self.session.admit(slots, x0, tc, sc, lens, schedule)
-        for _ in range(n):
-            self._queue.popleft()
-        for s, r, frames, p, q in zip(slots, reqs, lens, nfr.tolist(), rms):
-            self._rows[s] = (r[0], frames, int(p), q)
+        return tc, sc, lens, nfr.tolist(), rms
 
-    def _admit_voices(self, reqs, slots) -> None:
-        """Admission of a group whose requests all carry voices.  Nothing is read back from the device:
-        the lengths are ``submit``'s host counts (the device evaluates the same fp32 expression for the text
-        condition), the speech condition and the gains come from the store, and every host value goes up
-        through pinned memory."""
-        m, dev, n = self.model, self.model.device, len(reqs)
-        voices = [r[1][1] for r in reqs]
-        lens = [r[7] for r in reqs]
-        T_in = max(lens)
-        schedule, speeds = per_row_schedule(n, num_step=[r[2] for r in reqs], guidance_scale=[r[3] for r in reqs],
-                                            speed=[r[4] for r in reqs], t_shift=[r[5] for r in reqs])
-        tc, _ = m.forward_text_inference_ratio_duration(
-            tokens=[r[1][0] for r in reqs], prompt_tokens=[list(v.prompt_tokens) for v in voices],
-            prompt_features_lens=to_device(torch.tensor([v.frames for v in voices]), dev),
-            speed=to_device(torch.tensor(speeds, dtype=torch.float32), dev), num_frames=T_in)
-        sc, gains = self.voices.gather(voices, T_in)
-        seeds = [r[6] for r in reqs]
-        if all(s is not None for s in seeds):
-            x0 = seeded_normal(seeds, (T_in, sc.size(-1)), device=dev)
-        else:
-            x0 = torch.randn(n, T_in, sc.size(-1), device=dev)
-            for i, s in enumerate(seeds):
-                if s is not None:
-                    seeded_normal_into(x0[i:i + 1], [s])
-        self.session.admit(slots, x0, tc, sc, lens, schedule)
-        for s, r, v, frames, i in zip(slots, reqs, voices, lens, range(n)):
-            self._queue.popleft()
-            self.voices.release(v)
-            self._rows[s] = (r[0], frames, v.frames, gains[i])
+    def _voice_group(self, reqs, text):
+        """The same of a group whose requests all carry voices, their output gains on the device as the level.
+        Nothing is read back: the lengths are ``submit``'s host counts (the device evaluates the same fp32
+        expression for the text condition), the speech condition and the gains come from the store, and every
+        host value goes up through pinned memory."""
+        voices = [r.item[1] for r in reqs]
+        lens = [r.total for r in reqs]
+        frames = [v.frames for v in voices]
+        tc, _ = text([list(v.prompt_tokens) for v in voices], to_device(torch.tensor(frames), self.model.device),
+                     max(lens))
+        sc, gains = self.voices.gather(voices, max(lens))
+        return tc, sc, lens, frames, gains
 
     def step(self) -> List[Tuple[int, torch.Tensor]]:
         """Retire the finished rows, admit queued requests into the free slots, run one tick.

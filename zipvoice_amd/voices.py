@@ -208,7 +208,7 @@ class VoiceStore:
     def register_batch(self, prompts: Sequence[tuple]) -> List[Voice]:
         """``prompts`` = [(prompt_wav, prompt_tokens[, prompt_sampling_rate]), ...] -> their voices.
         A prompt the fbank cannot frame or a full arena is a ValueError and registers none."""
-        from .infer import _resampler
+        from .infer import _prompts_at_rate
         dev, B = self.device, len(prompts)
         if B == 0:
             return []
@@ -230,19 +230,9 @@ class VoiceStore:
         try:
             ld = (max(lens) + 3) // 4 * 4                 # (a multiple of 4: the 16-byte form of the scale pass)
             wb = torch.zeros((B, ld), dtype=torch.float32, device=dev)
-            by_rate = {}
-            for i, r in enumerate(rates):
-                by_rate.setdefault(r, []).append(i)
-            for rate, idx in by_rate.items():             # one upload (and one resample) per distinct rate
-                n_in = [len(wavs[i]) for i in idx]
-                hb = torch.zeros((len(idx), max(n_in)), dtype=torch.float32)
-                for r, i in enumerate(idx):
-                    hb[r, :n_in[r]] = wavs[i]
-                db = hb.to(dev)
-                if rate != self.sampling_rate:
-                    db, _ = _resampler(rate, self.sampling_rate).resample_batch(db, n_in)
-                for r, i in enumerate(idx):
-                    wb[i, :lens[i]] = db[r, :lens[i]]
+            # (one upload and one resample per other rate; a prompt at the model's rate goes up here)
+            for i, w in enumerate(_prompts_at_rate(wavs, rates, self.sampling_rate, dev)):
+                wb[i, :lens[i]] = w
             rms, _, gain_out, ln = prompt_rms(wb, lens, self.target_rms)
             prompt_scale(wb, lens, ln, rms, self.target_rms, out=wb)
             feats, _ = self.fx.extract_batch(wb, torch.tensor(lens))
