@@ -636,6 +636,34 @@ typedef struct {
 } zv_session_check_args;
 int zv_session_check(zv_session_check_args* a);
 
+/* The edit rows' two kernels (zv_session_admit_edit / zv_session_retire_edit below), one launch at a
+ * time through the rules, the table layout and the launch functions the engine runs (test
+ * infrastructure: tests/test_gpu_session_edit_kernels.py; builds no engine; synchronous).  Outputs are
+ * canary-filled by the caller with `guard` guard elements at both ends.  The session's host state is
+ * the caller's: state_left [slots] the steps each slot has left (-1: free), state_len [slots] its row's
+ * length; a call that succeeds updates both as the engine would (admit: num_step and T_i, retire: -1
+ * and 0), a rejected call (return 1) leaves them and every output as they were and launches nothing.
+ * slot / offsets / lens (n), table, row_ptr (n + 1) and pool (pool_rows, Fx) as in the entries.
+ *   ZV_SE_ADMIT   x, tc: the request rows (n, T_io, Fx / Ft); rows (n) the schedules -> out, out_tc,
+ *                 out_sc (guard + slots * max_frames * F + guard) and mout (guard + slots * max_frames
+ *                 + guard): the named slots written whole, the others left
+ *   ZV_SE_RETIRE  x: the slot buffer (slots, max_frames, Fx); keep_original -> out (guard + n * T_io *
+ *                 Fx + guard) and mout (guard + n * T_io + guard, or NULL)
+ * launch: {kind, kernel form (1: the quad kernel), grid.x, block threads, grid.y, 0...}. */
+enum zv_session_edit_kind { ZV_SE_ADMIT = 0, ZV_SE_RETIRE = 1 };
+typedef struct {
+  int kind, guard;
+  int slots, max_frames, n, T_io, Fx, Ft, pool_rows, keep_original;
+  const int32_t* slot; const int32_t* offsets; const int32_t* lens; const int32_t* table; const int32_t* row_ptr;
+  const zv_row_sched* rows;
+  int32_t* state_left; int32_t* state_len;
+  const float* x; const float* tc; const float* pool;
+  float* out; float* out_tc; float* out_sc; uint8_t* mout;
+  int launch[8];
+  int num_cus;
+} zv_session_edit_check_args;
+int zv_session_edit_check(zv_session_edit_check_args* a);
+
 /* Attention plan (host only, no GPU; test infrastructure): the LDS bytes of the fused
  * attention consumers a layer of sequence length L would launch — SelfAttention (sa_plo < 0:
  * the plain kernel, 0 / 1: the Toeplitz kernel without / with the table's lo half),
@@ -759,6 +787,49 @@ int zv_session_step(zv_session_handle s, void* stream);
 int zv_session_retire(zv_session_handle s, int n, const int32_t* host_slots, float* out, int T_out,
                       void* stream);
 int zv_session_state(zv_session_handle s, int32_t* host_steps_left, int64_t* stats);
+
+/* Edit rows: a row of a speech edit (zv_edit_gather's frame tables) enters and leaves a slot straight
+ * from a pool of stored feature frames, pool [pool_rows, Fx] device fp32 (the voice store's arena); no
+ * (n, T, Fx) speech condition is built and nothing is read back.  NO reference counterpart.  Row i is
+ * described by host_offsets[i] and host_lens[i] = L_i: its original frame f is pool row
+ * host_offsets[i] + f (a plain (B, Lmax, Fx) tensor is the case offset_i = i * Lmax), and by segments
+ * [host_row_ptr[i], host_row_ptr[i + 1]) of host_table, rows (dst, src, len) int32 with src == -1 a
+ * generated segment, exactly as zv_edit_gather defines them; T_i is the length they tile.  The same
+ * pool range may be named by several rows.  All of it is validated on the host before anything is
+ * queued, the error names the row, and a rejected call changes no state and launches nothing:
+ *   the table   row_ptr[0] == 0 and not falling; len > 0; the segments of a row tile [0, T_i) in
+ *               order; a kept segment lies in [0, L_i); L_i >= 0, offset_i >= 0 and offset_i + L_i <=
+ *               pool_rows (so the pool is never read outside [offset_i, offset_i + L_i));
+ *   admit       zv_session_admit's rules with len = T_i: n < 1, a slot outside [0, slots), not free or
+ *               named twice, T_i < 1, T_i > T_in or T_i > max_frames, a schedule zv_sched_plan rejects;
+ *   retire      zv_session_retire's rules: n < 1, a slot outside [0, slots), free, with steps left or
+ *               named twice, T_out shorter than a row; and a table whose T_i is not the slot's length.
+ * The checked table then goes up through the engine's pinned staging as the other tables of a session
+ * (one upload per call; the warm-path promise of zv_session_admit holds).
+ *   admit_edit  one launch, one row per blockIdx.y, into the free slot host_slots[i] with the schedule
+ *               host_rows[i] (t_start / t_end as zv_session_admit): x <- x0[i, :T_i], text <- text_c[i,
+ *               :T_i], both zero up to max_frames (x0 (n, T_in, Fx), text_c (n, T_in, feat_dim) device);
+ *               speech[t] = the pool frame on a kept segment, 0 on a generated one and for t >= T_i;
+ *               pad[t] = t >= T_i.  The slot is then as zv_session_admit leaves it after
+ *               zv_edit_gather(fill = NULL) built its speech condition, bit for bit.
+ *   retire_edit one launch: out[i, t] (n, T_out, Fx) = the pool frame on a kept segment (bitwise the
+ *               original), the slot's x on a generated one, 0 for T_i <= t < T_out; keep_original == 0
+ *               takes the slot's x on every frame below T_i (sample_edit(keep_original=False));
+ *               mask_out (n, T_out) uint8 or NULL: 1 exactly on generated frames.  The slot is free
+ *               afterwards.  What zv_session_retire followed by zv_edit_gather(fill = the retired rows)
+ *               leaves, bit for bit.
+ * Both find a frame's segment by bisection in the row's table once per frame, move four features per
+ * thread (16-byte loads and stores) when Fx % 4 == 0 (admit: and feat_dim % 4 == 0) and every base is
+ * 16-byte aligned, one otherwise; no atomics, every output element is written exactly once by one
+ * thread, and the results do not depend on the launch geometry. */
+int zv_session_admit_edit(zv_session_handle s, int n, const int32_t* host_slots, const zv_row_sched* host_rows,
+                          const float* x0, const float* text_c, int T_in, const float* pool, int pool_rows,
+                          const int32_t* host_offsets, const int32_t* host_lens, const int32_t* host_table,
+                          const int32_t* host_row_ptr, void* stream);
+int zv_session_retire_edit(zv_session_handle s, int n, const int32_t* host_slots, const float* pool, int pool_rows,
+                           const int32_t* host_offsets, const int32_t* host_lens, const int32_t* host_table,
+                           const int32_t* host_row_ptr, int keep_original, float* out, uint8_t* mask_out, int T_out,
+                           void* stream);
 
 /* Text encoder (+ dialog speaker-turn embeddings).
  *  tokens: [B, S] int64 (already padded with pad_id, one extra pad per row);

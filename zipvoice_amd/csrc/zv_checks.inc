@@ -1462,6 +1462,88 @@ int zv_session_check(zv_session_check_args* a) {
   ZV_API_END
 }
 
+// ---------------------------------------------------------------------------
+// zv_session_edit_check: the edit rows' two kernels through the rules, the table and the launch functions
+// zv_engine::session_admit_edit / session_retire_edit run, on host arrays with canary-guarded outputs and
+// the session's host state (state_left / state_len) given and updated by the caller's arrays.
+// ---------------------------------------------------------------------------
+int zv_session_edit_check(zv_session_edit_check_args* a) {
+  ZV_API_BEGIN
+  ZV_REQUIRE(a && (a->kind == ZV_SE_ADMIT || a->kind == ZV_SE_RETIRE) && a->guard >= 0,
+             "zv_session_edit_check: bad arguments");
+  const int kind = a->kind, S = a->slots, maxT = a->max_frames, Fx = a->Fx, Ft = a->Ft, n = a->n, Tio = a->T_io;
+  const size_t G = (size_t)a->guard, Gd = (G + 3) / 4 * 4;   // (device guards: a multiple of 4 values, as zv_session_check)
+  ZV_REQUIRE(S > 0 && S <= SESSION_MAX_SLOTS && maxT > 0 && Fx > 0 && (kind == ZV_SE_RETIRE || Ft > 0),
+             "zv_session_edit_check: slots in [1, 32767], max_frames, Fx (and Ft) > 0");
+  ZV_REQUIRE((long)S * maxT * std::max(Fx, std::max(Ft, 1)) < (1L << 30), "zv_session_edit_check: slot buffers under 2^30 values");
+  ZV_REQUIRE(a->pool_rows > 0 && (long)a->pool_rows * Fx < (1L << 30) && a->pool && a->state_left && a->state_len && a->x &&
+                 a->out,
+             "zv_session_edit_check: needs the pool (under 2^30 values), state_left, state_len, x and out");
+  for (int b = 0; b < S; ++b)
+    ZV_REQUIRE(a->state_left[b] >= -1 && a->state_len[b] >= 0 && a->state_len[b] <= maxT,
+               "zv_session_edit_check: state_left >= -1 and state_len in [0, max_frames]");
+  const size_t st = (size_t)S * maxT;
+  const SessView view{S, maxT, a->state_left, a->state_len};
+  const SessEditReq e{n, a->slot, a->offsets, a->lens, a->table, a->row_ptr, a->pool_rows};
+  std::vector<int> T;
+  hipStream_t s = nullptr;
+  EdgeLaunch ran{};
+  if (kind == ZV_SE_ADMIT) {
+    ZV_REQUIRE(a->tc && a->out_tc && a->out_sc && a->mout, "zv_session_edit_check: ADMIT needs tc, out_tc, out_sc and mout");
+    sess_edit_check_admit(view, e, reinterpret_cast<const SchedRow*>(a->rows), Tio, T);
+  } else {
+    sess_edit_check_retire(view, e, Tio, T);
+  }
+  ZV_REQUIRE((long)n * Tio * std::max(Fx, Ft) < (1L << 30), "zv_session_edit_check: request rows under 2^30 values");
+  ChkDev dev;
+  std::vector<unsigned> words(sess_edit_words(e));
+  sess_edit_fill(words.data(), e, T);
+  const unsigned* dtab = dev.up(words.data(), words.size());
+  const float* pool = dev.up(a->pool, (size_t)a->pool_rows * Fx);
+  auto sync = [&] { ZV_CHECK(ZV_BLOCKING(hipDeviceSynchronize())); };
+  auto guarded = [&](const float* host, size_t count) {   // host (guard + count + guard) -> device, interior 16-byte aligned
+    std::vector<float> h(Gd - G + count + 2 * G);
+    memcpy(&h[Gd - G], host, (count + 2 * G) * sizeof(float));
+    return dev.up(h.data(), h.size());
+  };
+  if (kind == ZV_SE_ADMIT) {
+    const float* x0 = dev.up(a->x, (size_t)n * Tio * Fx);
+    const float* tc0 = dev.up(a->tc, (size_t)n * Tio * Ft);
+    float* ox = guarded(a->out, st * Fx);
+    float* ot = guarded(a->out_tc, st * Ft);
+    float* os = guarded(a->out_sc, st * Fx);
+    uint8_t* om = dev.up(a->mout, st + 2 * G);
+    ran = launch_session_admit_edit(x0, tc0, n, Tio, pool, ox + Gd, ot + Gd, os + Gd, om + G, dtab, maxT, Fx, Ft, s);
+    sync();
+    dev.down(a->out, ox + (Gd - G), st * Fx + 2 * G);
+    dev.down(a->out_tc, ot + (Gd - G), st * Ft + 2 * G);
+    dev.down(a->out_sc, os + (Gd - G), st * Fx + 2 * G);
+    dev.down(a->mout, om, st + 2 * G);
+    for (int i = 0; i < n; ++i) {
+      a->state_left[a->slot[i]] = a->rows[i].num_step;
+      a->state_len[a->slot[i]] = T[i];
+    }
+  } else {
+    const float* x = dev.up(a->x, st * Fx);
+    const size_t no = (size_t)n * Tio * Fx, nm = (size_t)n * Tio;
+    float* o = guarded(a->out, no);
+    uint8_t* om = a->mout ? dev.up(a->mout, nm + 2 * G) : nullptr;
+    ran = launch_session_retire_edit(x, pool, o + Gd, om ? om + G : nullptr, n, Tio, dtab, maxT, Fx,
+                                     a->keep_original != 0, s);
+    sync();
+    dev.down(a->out, o + (Gd - G), no + 2 * G);
+    if (om) dev.down(a->mout, om, nm + 2 * G);
+    for (int i = 0; i < n; ++i) {
+      a->state_left[a->slot[i]] = -1;
+      a->state_len[a->slot[i]] = 0;
+    }
+  }
+  const int rec[8] = {kind, ran.form, ran.blocks, ran.threads, n, 0, 0, 0};
+  memcpy(a->launch, rec, sizeof(rec));
+  a->num_cus = zv_num_cus();
+  ZV_API_END
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------

@@ -1599,6 +1599,62 @@ struct zv_engine : LinearPolicy {   // (zv_linear.inc: linear<SPLIT> and the fus
     }
   }
 
+  // zv_session_admit_edit / zv_session_retire_edit bodies: a row of a speech edit enters and leaves its
+  // slot straight from a pool of stored frames under the edit's frame table (zv_session.inc, "Edit
+  // rows").  The rules run on the host before anything is queued; the table (rows | segments) goes up
+  // through the same staging as every other table of the session.
+  struct SessState {
+    std::vector<int> left;
+    SessView view;
+  };
+  static void session_view(const zv_session& q, SessState& st) {
+    st.left.resize(q.slots);
+    for (int b = 0; b < q.slots; ++b) st.left[b] = q.rows[b].num_step > 0 ? q.rows[b].num_step - q.done[b] : -1;
+    st.view = SessView{q.slots, q.maxT, st.left.data(), q.lens.data()};
+  }
+  const unsigned* session_edit_send(const SessEditReq& e, const std::vector<int>& T, hipStream_t s) {
+    const size_t words = sess_edit_words(e);
+    SchedSlot& sl = sched_slot(words * 4);
+    sess_edit_fill(sl.base + 16, e, T);
+    return sched_send(sl, words, s);
+  }
+
+  void session_admit_edit(zv_session& q, const SessEditReq& e, const SchedRow* rows, const float* x0,
+                          const float* tc0, int T_in, const float* pool, hipStream_t s) {
+    ZV_REQUIRE(x0 && tc0 && pool, "session: admit_edit: null argument");
+    SessState st;
+    session_view(q, st);
+    std::vector<int> T;
+    sess_edit_check_admit(st.view, e, rows, T_in, T);
+    const int Fx = stereo() ? 2 * cfg.feat_dim : cfg.feat_dim, Ft = cfg.feat_dim;
+    const unsigned* dtab = session_edit_send(e, T, s);
+    launch_session_admit_edit(x0, tc0, e.n, T_in, pool, q.dx, q.dtc, q.dsc, q.dpad, dtab, q.maxT, Fx, Ft, s);
+    for (int i = 0; i < e.n; ++i) {
+      const int b = e.slot[i];
+      q.rows[b] = rows[i];
+      q.ts[b] = solve_time_steps(rows[i].t_start, rows[i].t_end, rows[i].num_step, rows[i].t_shift);
+      q.lens[b] = T[i];
+      q.done[b] = 0;
+    }
+  }
+
+  void session_retire_edit(zv_session& q, const SessEditReq& e, const float* pool, bool keep, float* out,
+                           uint8_t* mask, int T_out, hipStream_t s) {
+    ZV_REQUIRE(pool && out, "session: retire_edit: null argument");
+    SessState st;
+    session_view(q, st);
+    std::vector<int> T;
+    sess_edit_check_retire(st.view, e, T_out, T);
+    const int Fx = stereo() ? 2 * cfg.feat_dim : cfg.feat_dim;
+    const unsigned* dtab = session_edit_send(e, T, s);
+    launch_session_retire_edit(q.dx, pool, out, mask, e.n, T_out, dtab, q.maxT, Fx, keep, s);
+    for (int i = 0; i < e.n; ++i) {
+      q.rows[e.slot[i]].num_step = 0;
+      q.done[e.slot[i]] = 0;
+      q.lens[e.slot[i]] = 0;
+    }
+  }
+
   void text_encode(const int64_t* tok, const uint8_t* pad, const int8_t* spk, int B, int S,
                    float* out, hipStream_t s) {
     const long n = (long)B * S;
@@ -1942,6 +1998,27 @@ int zv_session_step(zv_session_handle q, void* stream) {
 int zv_session_retire(zv_session_handle q, int n, const int32_t* host_slots, float* out, int T_out, void* stream) {
   ZV_API_BEGIN
   session_engine(q)->session_retire(*q, n, host_slots, out, T_out, (hipStream_t)stream);
+  ZV_API_END
+}
+
+int zv_session_admit_edit(zv_session_handle q, int n, const int32_t* host_slots, const zv_row_sched* host_rows,
+                          const float* x0, const float* text_c, int T_in, const float* pool, int pool_rows,
+                          const int32_t* host_offsets, const int32_t* host_lens, const int32_t* host_table,
+                          const int32_t* host_row_ptr, void* stream) {
+  ZV_API_BEGIN
+  const SessEditReq e{n, host_slots, host_offsets, host_lens, host_table, host_row_ptr, pool_rows};
+  session_engine(q)->session_admit_edit(*q, e, reinterpret_cast<const SchedRow*>(host_rows), x0, text_c, T_in, pool,
+                                        (hipStream_t)stream);
+  ZV_API_END
+}
+
+int zv_session_retire_edit(zv_session_handle q, int n, const int32_t* host_slots, const float* pool, int pool_rows,
+                           const int32_t* host_offsets, const int32_t* host_lens, const int32_t* host_table,
+                           const int32_t* host_row_ptr, int keep_original, float* out, uint8_t* mask_out, int T_out,
+                           void* stream) {
+  ZV_API_BEGIN
+  const SessEditReq e{n, host_slots, host_offsets, host_lens, host_table, host_row_ptr, pool_rows};
+  session_engine(q)->session_retire_edit(*q, e, pool, keep_original != 0, out, mask_out, T_out, (hipStream_t)stream);
   ZV_API_END
 }
 

@@ -214,3 +214,226 @@ static SessTick session_tick(const SchedRow* rows, const int* done, const int* l
   return tk;
 }
 constexpr int SESSION_MAX_SLOTS = 32767;   // 2 * slots decoder rows stay inside one grid.y
+
+// ---------------------------------------------------------------------------------------------------
+// Edit rows (zv_session_admit_edit / zv_session_retire_edit): a row of a speech edit enters and leaves
+// its slot straight from a pool of stored feature frames (the voice store's arena), driven by the
+// edit's frame table as zv_edit_gather defines it: rows (dst, src, len), src == -1 a generated segment.
+// No (n, T, F) speech condition is built.  Row i's original frame f is pool row off_i + f.
+//   admit    x and the text condition as zv_session_admit_kernel (sess_copy_zero); the speech condition
+//            by tiles of SE_TILE frames: the first SE_TILE threads find their frame's segment by
+//            bisection in the row's table, once per frame, and leave the source frame in LDS (>= 0 a
+//            frame of the row's pool range, SE_GEN generated, SE_PAD at or past T_i); then every thread
+//            moves 4 features per item (16-byte loads and stores) or one.  The tiles of a row are
+//            strided over the grid's x-blocks, so any grid writes the same bytes.
+//   retire   the same tiles over [0, T_out): the pool frame on a kept segment, the slot's x on a
+//            generated one (everywhere without keep), zero from T_i on; mask = 1 on generated frames.
+// No atomics; every output element is written once, by one thread; the pool is read only at the frames
+// the host has checked to lie inside [off_i, off_i + L_i).
+constexpr int SE_TILE = 16;               // frames per tile
+constexpr int SE_GEN = -1, SE_PAD = -2;   // LDS marks: generated frame, frame at or past T_i
+
+// one row of an admit_edit / retire_edit table: T_i = len, the row's segments are seg[3 lo, 3 hi)
+struct SessEditRow { int slot, len, off, lo, hi; };
+
+// the source of new frame t of a row: the last segment in [lo, hi) whose dst is <= t (hi > lo: len >= 1)
+__device__ __forceinline__ int sess_edit_src(const SessEditRow& r, const int* seg, int t) {
+  if (t >= r.len) return SE_PAD;
+  int lo = r.lo, hi = r.hi;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (seg[3L * mid] <= t) lo = mid; else hi = mid;
+  }
+  const int* sg = seg + 3L * lo;
+  return sg[1] < 0 ? SE_GEN : sg[1] + (t - sg[0]);
+}
+
+// request rows x0 (n, T_in, Fx), tc0 (n, T_in, Ft) and the pool (pool_rows, Fx) -> the slots of tab
+template <bool QUAD>
+__global__ __launch_bounds__(256) void zv_session_admit_edit_kernel(
+    const float* x0, const float* tc0, int T_in, const float* pool, float* x, float* tc, float* sc, uint8_t* pad,
+    const SessEditRow* tab, const int* seg, int maxT, int Fx, int Ft) {
+  __shared__ int s_src[SE_TILE];
+  const SessEditRow r = tab[blockIdx.y];
+  const long src = (long)blockIdx.y * T_in, dst = (long)r.slot * maxT;
+  sess_copy_zero<QUAD>(x + dst * Fx, x0 + src * Fx, r.len * Fx, maxT * Fx);
+  sess_copy_zero<QUAD>(tc + dst * Ft, tc0 + src * Ft, r.len * Ft, maxT * Ft);
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < maxT; t += gridDim.x * blockDim.x)
+    pad[dst + t] = t >= r.len;
+  const int per = QUAD ? Fx >> 2 : Fx, W = QUAD ? 4 : 1;   // items per frame, features per item
+  const float* pr = pool + (long)r.off * Fx;
+  float* so = sc + dst * Fx;
+  for (int t0 = blockIdx.x * SE_TILE; t0 < maxT; t0 += gridDim.x * SE_TILE) {   // (uniform over the block)
+    if (threadIdx.x < SE_TILE) s_src[threadIdx.x] = sess_edit_src(r, seg, t0 + threadIdx.x);
+    __syncthreads();
+    for (int i = threadIdx.x; i < SE_TILE * per; i += blockDim.x) {
+      const int fr = i / per, c = (i - fr * per) * W;
+      const int t = t0 + fr;
+      if (t >= maxT) break;                                // fr rises with i
+      const int v = s_src[fr];
+      const long o = (long)t * Fx + c;
+      if (QUAD) {
+        f32x4 q = {0.f, 0.f, 0.f, 0.f};
+        if (v >= 0) q = *reinterpret_cast<const f32x4*>(pr + (long)v * Fx + c);
+        *reinterpret_cast<f32x4*>(so + o) = q;
+      } else {
+        so[o] = v >= 0 ? pr[(long)v * Fx + c] : 0.f;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the slots of tab -> out rows (n, T_out, Fx) and mask rows (n, T_out) (mask may be null)
+template <bool QUAD>
+__global__ __launch_bounds__(256) void zv_session_retire_edit_kernel(
+    const float* x, const float* pool, float* out, uint8_t* mask, const SessEditRow* tab, const int* seg, int maxT,
+    int T_out, int Fx, int keep) {
+  __shared__ int s_src[SE_TILE];
+  const SessEditRow r = tab[blockIdx.y];
+  const int per = QUAD ? Fx >> 2 : Fx, W = QUAD ? 4 : 1;
+  const float* pr = pool + (long)r.off * Fx;
+  const float* xr = x + (long)r.slot * maxT * Fx;
+  float* orow = out + (long)blockIdx.y * T_out * Fx;
+  for (int t0 = blockIdx.x * SE_TILE; t0 < T_out; t0 += gridDim.x * SE_TILE) {
+    if (threadIdx.x < SE_TILE) {
+      const int t = t0 + threadIdx.x;
+      const int v = sess_edit_src(r, seg, t);
+      s_src[threadIdx.x] = v;
+      if (mask && t < T_out) mask[(long)blockIdx.y * T_out + t] = v == SE_GEN;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < SE_TILE * per; i += blockDim.x) {
+      const int fr = i / per, c = (i - fr * per) * W;
+      const int t = t0 + fr;
+      if (t >= T_out) break;
+      const int v = s_src[fr];
+      const long o = (long)t * Fx + c;
+      // (t < T_i <= max_frames wherever the slot is read)
+      const float* from = v == SE_PAD ? nullptr : (v >= 0 && keep ? pr + (long)v * Fx + c : xr + o);
+      if (QUAD) {
+        f32x4 q = {0.f, 0.f, 0.f, 0.f};
+        if (from) q = *reinterpret_cast<const f32x4*>(from);
+        *reinterpret_cast<f32x4*>(orow + o) = q;
+      } else {
+        orow[o] = from ? *from : 0.f;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- the host side of the edit rows: the rules, the table and the launches (zv_engine::session_admit_edit
+// / session_retire_edit and zv_session_edit_check run these same functions) ----
+// What the rules need of a session: per slot the steps left (-1: free) and the row's length.
+struct SessView { int slots, maxT; const int* left; const int* len; };
+struct SessEditReq {
+  int n;
+  const int32_t *slot, *off, *L, *table, *row_ptr;
+  int pool_rows;
+};
+// The table's own rules (zv_edit_gather's, and the pool range); T[i] = the new length of row i.
+static void sess_edit_check_tables(const std::string& who, const SessEditReq& e, std::vector<int>& T) {
+  ZV_REQUIRE(e.n >= 1, who + " takes at least one row");
+  ZV_REQUIRE(e.slot && e.off && e.L && e.row_ptr, who + ": null argument");
+  ZV_REQUIRE(e.pool_rows >= 1, who + ": pool_rows must be at least 1");
+  ZV_REQUIRE(e.row_ptr[0] == 0, who + ": row_ptr[0] must be 0");
+  for (int i = 0; i < e.n; ++i)
+    ZV_REQUIRE(e.row_ptr[i + 1] >= e.row_ptr[i], who + " row " + std::to_string(i) + ": row_ptr must not fall");
+  ZV_REQUIRE(e.table || e.row_ptr[e.n] == 0, who + ": null table");
+  T.assign(e.n, 0);
+  for (int i = 0; i < e.n; ++i) {
+    const std::string at = who + " row " + std::to_string(i) + ": ";
+    const long off = e.off[i], L = e.L[i];
+    ZV_REQUIRE(L >= 0 && off >= 0 && off + L <= e.pool_rows, at + "pool range outside [0, pool_rows)");
+    long pos = 0;
+    for (int k = e.row_ptr[i]; k < e.row_ptr[i + 1]; ++k) {
+      const long dst = e.table[3L * k], src = e.table[3L * k + 1], len = e.table[3L * k + 2];
+      ZV_REQUIRE(len > 0, at + "segment lengths must be positive");
+      ZV_REQUIRE(dst == pos, at + "segments must tile [0, T_i) in order");
+      ZV_REQUIRE(src == -1 || (src >= 0 && src + len <= L), at + "kept segment outside [0, L_i)");
+      pos += len;
+      ZV_REQUIRE(pos < (1L << 30), at + "row longer than 2^30 frames");
+    }
+    T[i] = (int)pos;
+  }
+}
+static void sess_edit_check_admit(const SessView& q, const SessEditReq& e, const SchedRow* rows, int T_in,
+                                  std::vector<int>& T) {
+  const std::string who = "session: admit_edit";
+  ZV_REQUIRE(rows != nullptr, who + ": null argument");
+  ZV_REQUIRE(T_in >= 1, who + ": T_in must be at least 1");
+  sess_edit_check_tables(who, e, T);
+  std::vector<char> seen(q.slots, 0);
+  for (int i = 0; i < e.n; ++i) {
+    const std::string at = who + " row " + std::to_string(i) + ": ";
+    ZV_REQUIRE(e.slot[i] >= 0 && e.slot[i] < q.slots, at + "slot outside [0, slots)");
+    ZV_REQUIRE(q.left[e.slot[i]] < 0, at + "slot is not free");
+    ZV_REQUIRE(!seen[e.slot[i]], at + "slot named twice");
+    seen[e.slot[i]] = 1;
+    ZV_REQUIRE(T[i] >= 1 && T[i] <= T_in && T[i] <= q.maxT, at + "length must be in [1, min(T_in, max_frames)]");
+    sched_check_row(rows[i], at);
+  }
+}
+static void sess_edit_check_retire(const SessView& q, const SessEditReq& e, int T_out, std::vector<int>& T) {
+  const std::string who = "session: retire_edit";
+  sess_edit_check_tables(who, e, T);
+  std::vector<char> seen(q.slots, 0);
+  for (int i = 0; i < e.n; ++i) {
+    const std::string at = who + " row " + std::to_string(i) + ": ";
+    ZV_REQUIRE(e.slot[i] >= 0 && e.slot[i] < q.slots, at + "slot outside [0, slots)");
+    ZV_REQUIRE(q.left[e.slot[i]] >= 0, at + "slot is free");
+    ZV_REQUIRE(q.left[e.slot[i]] == 0, at + "slot has steps left");
+    ZV_REQUIRE(!seen[e.slot[i]], at + "slot named twice");
+    seen[e.slot[i]] = 1;
+    ZV_REQUIRE(T[i] == q.len[e.slot[i]], at + "the table's length is not the slot's");
+    ZV_REQUIRE(T_out >= T[i], at + "T_out is shorter than the row");
+  }
+}
+// the device table of a checked request: rows [n] (SessEditRow) | segments [3 nseg]
+static size_t sess_edit_words(const SessEditReq& e) { return 5 * (size_t)e.n + 3 * (size_t)e.row_ptr[e.n]; }
+static void sess_edit_fill(unsigned* words, const SessEditReq& e, const std::vector<int>& T) {
+  static_assert(sizeof(SessEditRow) == 20, "SessEditRow is five 4-byte words");
+  SessEditRow* rows = reinterpret_cast<SessEditRow*>(words);
+  for (int i = 0; i < e.n; ++i) rows[i] = SessEditRow{e.slot[i], T[i], e.off[i], e.row_ptr[i], e.row_ptr[i + 1]};
+  if (e.row_ptr[e.n] > 0) memcpy(words + 5 * (size_t)e.n, e.table, 3 * (size_t)e.row_ptr[e.n] * sizeof(int));
+}
+// dtab: the device copy of that table.  Forms as launch_session_admit / launch_session_retire.
+static EdgeLaunch launch_session_admit_edit(const float* x0, const float* tc0, int n, int T_in, const float* pool,
+                                            float* x, float* tc, float* sc, uint8_t* pad, const unsigned* dtab,
+                                            int maxT, int Fx, int Ft, hipStream_t s) {
+  sess_check_sizes(maxT, Fx, Ft);
+  ZV_REQUIRE(T_in > 0 && (long)T_in * std::max(Fx, Ft) < (1L << 30), "session: T_in times width must stay under 2^30");
+  const bool quad = Fx % 4 == 0 && Ft % 4 == 0 && sess_aligned16(x0, tc0, pool) && sess_aligned16(x, tc, sc);
+  const long per = (long)maxT * std::max(Fx, Ft);
+  const dim3 grid = sched_grid(quad ? per / 4 : per, n);
+  const SessEditRow* tab = reinterpret_cast<const SessEditRow*>(dtab);
+  const int* seg = reinterpret_cast<const int*>(dtab + 5 * (size_t)n);
+  if (quad)
+    hipLaunchKernelGGL(zv_session_admit_edit_kernel<true>, grid, dim3(256), 0, s, x0, tc0, T_in, pool, x, tc, sc, pad,
+                       tab, seg, maxT, Fx, Ft);
+  else
+    hipLaunchKernelGGL(zv_session_admit_edit_kernel<false>, grid, dim3(256), 0, s, x0, tc0, T_in, pool, x, tc, sc, pad,
+                       tab, seg, maxT, Fx, Ft);
+  ZV_LAUNCH_CHECK();
+  return {quad ? 1 : 0, (int)grid.x, 256};
+}
+static EdgeLaunch launch_session_retire_edit(const float* x, const float* pool, float* out, uint8_t* mask, int n,
+                                             int T_out, const unsigned* dtab, int maxT, int Fx, bool keep,
+                                             hipStream_t s) {
+  sess_check_sizes(maxT, Fx, 1);
+  ZV_REQUIRE(T_out > 0 && (long)T_out * Fx < (1L << 30), "session: T_out times width must stay under 2^30");
+  const bool quad = Fx % 4 == 0 && sess_aligned16(x, pool, out);
+  const long per = (long)T_out * Fx;
+  const dim3 grid = sched_grid(quad ? per / 4 : per, n);
+  const SessEditRow* tab = reinterpret_cast<const SessEditRow*>(dtab);
+  const int* seg = reinterpret_cast<const int*>(dtab + 5 * (size_t)n);
+  if (quad)
+    hipLaunchKernelGGL(zv_session_retire_edit_kernel<true>, grid, dim3(256), 0, s, x, pool, out, mask, tab, seg, maxT,
+                       T_out, Fx, keep ? 1 : 0);
+  else
+    hipLaunchKernelGGL(zv_session_retire_edit_kernel<false>, grid, dim3(256), 0, s, x, pool, out, mask, tab, seg, maxT,
+                       T_out, Fx, keep ? 1 : 0);
+  ZV_LAUNCH_CHECK();
+  return {quad ? 1 : 0, (int)grid.x, 256};
+}

@@ -197,11 +197,18 @@ def edit_batch(items: Sequence[tuple], model, vocoder, feature_extractor, num_st
     An item without spans comes back as its resampled input, bitwise, and is not sent to the
     decoder.  Returns ([(1, N_i)] waveforms on the device, {"t", "wav_seconds", "gen_seconds",
     "rtf"}), ``gen_seconds`` the generated audio and ``rtf = t / gen_seconds``.  Mono and
-    one-channel Dialog models; the stereo model raises NotImplementedError."""
+    one-channel Dialog models; the stereo model raises NotImplementedError.
+
+    Items ``(tokens, Recording, spans)`` (``voices.VoiceStore.register_recording``; all of one store, not
+    mixed with wav items: a ValueError) skip the front: the features come from one ``VoiceStore.gather`` of
+    the recordings, the originals for the splice from the stored waveforms, the gains and ``target_rms`` /
+    ``feat_scale`` / ``feat_bias`` from the store."""
     import torch
 
     from .infer import _prompt_rms_normalise, _prompts_at_rate, output_gain
     from .noise import check_keys
+
+    from .voices import Recording
 
     if getattr(model.cfg, "stereo", False):
         raise NotImplementedError("edit_batch: the stereo dialog model is not supported")
@@ -209,6 +216,12 @@ def edit_batch(items: Sequence[tuple], model, vocoder, feature_extractor, num_st
     B = len(items)
     if seeds is not None:
         seeds, _ = check_keys(seeds, None, B)
+    by_rec = [isinstance(it[1], Recording) for it in items]
+    if any(by_rec):
+        if not all(by_rec):
+            raise ValueError("a batch is all (tokens, Recording, spans) items or all wavs, not a mix")
+        return _edit_recordings(items, model, vocoder, num_step, guidance_scale, t_shift, fade, seeds,
+                                keep_original_audio)
     sampling_rate = feature_extractor.config.sampling_rate
     hop = vocoder.cfg.hop_length
     with torch.inference_mode():
@@ -253,6 +266,60 @@ def edit_batch(items: Sequence[tuple], model, vocoder, feature_extractor, num_st
                                                     np.int32).reshape(-1, 4) for g in gen_lens], 4)
             gains = [output_gain(v, target_rms) for v in rms]
             out = model.engine.edit_splice(orig, Ns, gen, gen_lens, table, row_ptr, gains, fade)
+            torch.cuda.synchronize(dev)
+            t = (dt.datetime.now() - t0).total_seconds()
+            for r, i in enumerate(todo):
+                m = table_length(table[row_ptr[r]:row_ptr[r + 1]])
+                res[i] = out[r, :, :m]
+                gen_samples += (gen_lens[r] if not keep_original_audio else plan.generated(r) * hop)
+    secs = sum(w.shape[-1] for w in res) / sampling_rate
+    gsecs = gen_samples / sampling_rate
+    return res, {"t": t, "wav_seconds": secs, "gen_seconds": gsecs,
+                 "rtf": t / gsecs if gsecs else float("inf")}
+
+
+def _edit_recordings(items, model, vocoder, num_step, guidance_scale, t_shift, fade, seeds, keep_original_audio):
+    """``edit_batch`` over ``(tokens, Recording, spans)`` items: the steps from ``plan_edit_batch`` on, fed
+    from the store (features: one gather at the longest recording; gains: the store's, applied to the
+    generated waveform on the device before a splice with gains of 1, which evaluates the same product)."""
+    import torch
+
+    dev, B = model.device, len(items)
+    store = items[0][1].store
+    recs = [store.check(it[1]) for it in items]
+    sampling_rate, hop = store.sampling_rate, vocoder.cfg.hop_length
+    with torch.inference_mode():
+        res: List[Optional[torch.Tensor]] = [None] * B
+        todo = [i for i, it in enumerate(items) if len(it[2]) > 0]
+        for i in range(B):
+            if i not in todo:
+                res[i] = store.waveform(recs[i]).clone().unsqueeze(0)
+        t = gen_samples = 0.0
+        if todo:
+            sub = [recs[i] for i in todo]
+            Ns, L = [r.samples for r in sub], [r.frames for r in sub]
+            spans = [items[i][2] for i in todo]
+            plan = plan_edit_batch(L, spans)                # (validates before any solve)
+            features, gains = store.gather(sub, max(L))
+            orig = torch.zeros((len(sub), max(Ns)), dtype=torch.float32, device=dev)
+            for r, rec in enumerate(sub):
+                orig[r, :Ns[r]] = store.waveform(rec)
+            torch.cuda.synchronize(dev)
+            t0 = dt.datetime.now()
+            x1, new_lens, _ = model.sample_edit(
+                tokens=[items[i][0] for i in todo], features=features, features_lens=L,
+                spans=spans, num_step=num_step, guidance_scale=guidance_scale, t_shift=t_shift,
+                seeds=None if seeds is None else [seeds[i] for i in todo])
+            gen = vocoder.decode_features(x1, new_lens, feat_scale=store.feat_scale, feat_bias=store.feat_bias,
+                                          clamp=True)
+            gen = gen * gains.reshape((-1,) + (1,) * (gen.dim() - 1))
+            gen_lens = [int(T) * hop for T in plan.new_lens]
+            if keep_original_audio:
+                table, row_ptr = sample_table_batch(plan, Ns, hop)
+            else:
+                table, row_ptr = _stack([np.asarray([(0, 0, g, GENERATED)] if g else [],
+                                                    np.int32).reshape(-1, 4) for g in gen_lens], 4)
+            out = model.engine.edit_splice(orig, Ns, gen, gen_lens, table, row_ptr, None, fade)
             torch.cuda.synchronize(dev)
             t = (dt.datetime.now() - t0).total_seconds()
             for r, i in enumerate(todo):

@@ -176,6 +176,15 @@ class ZvSessionCheckArgs(ctypes.Structure):
         ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
 
 
+class ZvSessionEditCheckArgs(ctypes.Structure):
+    """zv_session_edit_check_args (test infrastructure; tests/test_gpu_session_edit_kernels.py)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("kind", "guard", "slots", "max_frames", "n", "T_io", "Fx", "Ft",
+                                            "pool_rows", "keep_original")] + [
+        (n, ctypes.c_void_p) for n in ("slot", "offsets", "lens", "table", "row_ptr", "rows", "state_left",
+                                       "state_len", "x", "tc", "pool", "out", "out_tc", "out_sc", "mout")] + [
+        ("launch", ctypes.c_int * 8), ("num_cus", ctypes.c_int)]
+
+
 def row_schedule_array(schedule):
     """A sequence of rows with num_step / t_start / t_end / t_shift / guidance_scale attributes (or
     5-tuples in that order) as a ctypes array of zv_row_sched."""
@@ -254,6 +263,10 @@ SIGNATURES = {
     "zv_session_state": (_I, [_P, _P, _P]),
     "zv_session_plan": (_I, [_P, _P, _P, _I, _I, ctypes.POINTER(ZvSchedPlanOut), _P]),
     "zv_session_check": (_I, [ctypes.POINTER(ZvSessionCheckArgs)]),
+    # edit rows of a session (SolveSession.admit_edit / retire_edit)
+    "zv_session_admit_edit": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "zv_session_retire_edit": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P]),
+    "zv_session_edit_check": (_I, [ctypes.POINTER(ZvSessionEditCheckArgs)]),
     "zv_text_encode": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "zv_text_condition": (_I, [_P, _P, _I, _I, _P, _P, _I, _P, _P]),
     "zv_speech_condition": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
@@ -819,6 +832,65 @@ class SolveSession:
         for s in sl.tolist():
             self._lens[s] = 0
         return out
+
+    def _edit_tables(self, slots, pool, offsets, lens, table, row_ptr):
+        """The host arrays of an edit request, shaped and typed for the C ABI, and each row's new length."""
+        sl = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        n = int(sl.size)
+        if pool.dim() != 2 or pool.shape[1] != self.Fx:
+            raise ValueError(f"pool: expected (rows, {self.Fx}), got {tuple(pool.shape)}")
+        if pool.dtype != torch.float32 or not pool.is_contiguous() or pool.device != self.device:
+            raise ValueError("pool must be a contiguous fp32 tensor on the session's device")
+        off = HipEngine._host_i32(offsets, (n,), "offsets")
+        ln = HipEngine._host_i32(lens, (n,), "lens")
+        rp = HipEngine._host_i32(row_ptr, (n + 1,), "row_ptr")
+        tab = HipEngine._host_i32(np.asarray(table).reshape(-1, 3), (max(int(rp[-1]), 0) if n else 0, 3), "table")
+        new = [int(tab[rp[i + 1] - 1, 0] + tab[rp[i + 1] - 1, 2]) if 0 <= rp[i] < rp[i + 1] <= len(tab) else 0
+               for i in range(n)]
+        return sl, off, ln, tab, rp, new
+
+    def admit_edit(self, slots, x0, text_c, pool, offsets, lens, table, row_ptr, schedule) -> None:
+        """Rows of a speech edit into free slots, their speech condition straight from ``pool`` (rows, Fx)
+        (zv_session_admit_edit): row i's original frames are pool rows ``offsets[i] + [0, lens[i])`` and its
+        frame table (``edit.plan_edit_batch``: ``table`` (m, 3) rows (dst, src, len), ``row_ptr`` (n + 1,),
+        host arrays) says which of them the new row keeps; ``x0`` (n, T_in, Fx) and ``text_c`` (n, T_in,
+        feat_dim) are read up to each row's new length.  A bad request is a ValueError, changes nothing and
+        launches nothing."""
+        n, T_in, _ = x0.shape
+        if not (len(slots) == len(schedule) == n):
+            raise ValueError(f"admit_edit: expected {n} slots and schedule rows, got {len(slots)}, {len(schedule)}")
+        x0 = self.eng._f32(x0, "x0", (n, T_in, self.Fx))
+        text_c = self.eng._f32(text_c, "text_condition", (n, T_in, self.eng.cfg.feat_dim))
+        sl, off, ln, tab, rp, new = self._edit_tables(slots, pool, offsets, lens, table, row_ptr)
+        rows = row_schedule_array(list(schedule))
+        with torch.cuda.device(self.device):
+            self._check(self.lib.zv_session_admit_edit(
+                self._handle(), n, sl.ctypes.data, ctypes.cast(rows, ctypes.c_void_p), _ptr(x0), _ptr(text_c), T_in,
+                _ptr(pool), pool.shape[0], off.ctypes.data, ln.ctypes.data, tab.ctypes.data, rp.ctypes.data,
+                _stream()))
+        for s, l in zip(sl.tolist(), new):
+            self._lens[s] = l
+
+    def retire_edit(self, slots, pool, offsets, lens, table, row_ptr, T_out: Optional[int] = None,
+                    keep_original: bool = True):
+        """The finished edit rows of ``slots`` (zv_session_retire_edit) -> (x1 (n, T_out, Fx), mask (n, T_out)
+        bool): kept frames are the pool's, bitwise, generated ones the solver's (``mask`` True), zero past
+        each row's new length; ``keep_original=False`` returns the solver's frames everywhere.  The tables
+        are those of the admission.  The slots are free afterwards."""
+        sl, off, ln, tab, rp, new = self._edit_tables(slots, pool, offsets, lens, table, row_ptr)
+        n = int(sl.size)
+        if T_out is None:
+            T_out = max(new + [1])
+        out = torch.empty((n, int(T_out), self.Fx), dtype=torch.float32, device=self.device)
+        mask = torch.empty((n, int(T_out)), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.zv_session_retire_edit(
+                self._handle(), n, sl.ctypes.data, _ptr(pool), pool.shape[0], off.ctypes.data, ln.ctypes.data,
+                tab.ctypes.data, rp.ctypes.data, int(bool(keep_original)), _ptr(out), _ptr(mask), int(T_out),
+                _stream()))
+        for s in sl.tolist():
+            self._lens[s] = 0
+        return out, mask.bool()
 
     def _state(self):
         left = (ctypes.c_int32 * self.slots)()

@@ -85,6 +85,18 @@ class Voice:
     store: "VoiceStore" = field(repr=False)
 
 
+@dataclass(frozen=True, eq=False)
+class Recording:
+    """One registered recording to edit: ``frames`` feature frames (``compute_num_frames(samples, hop)``, the
+    ``L`` of ``edit.sample_table``) at arena row ``offset`` of ``store`` and ``samples`` samples at the
+    model's rate, whose un-normalised waveform the store keeps on the device (``VoiceStore.waveform``)."""
+    id: int
+    offset: int
+    frames: int
+    samples: int
+    store: "VoiceStore" = field(repr=False)
+
+
 def _check_rc(lib, rc: int):
     if rc != 0 and "voice table:" in lib.zv_last_error().decode():
         raise ValueError(lib.zv_last_error().decode())
@@ -191,6 +203,7 @@ class VoiceStore:
         self._gather = VoiceGather(self.device)
         self._live = {}                       # voice id -> Voice
         self._uses = {}                       # voice id -> requests a batcher has queued
+        self._wavs = {}                       # recording id -> its waveform at the model's rate, (samples,)
         self._ids = itertools.count()
         self.serial = next(VoiceStore._serial)
 
@@ -204,21 +217,18 @@ class VoiceStore:
             n = _resampler(int(prompt_sampling_rate), self.sampling_rate).plan.out_len(n)
         return n, compute_num_frames(n, self.fx._hop)
 
-    @torch.inference_mode()
-    def register_batch(self, prompts: Sequence[tuple]) -> List[Voice]:
-        """``prompts`` = [(prompt_wav, prompt_tokens[, prompt_sampling_rate]), ...] -> their voices.
-        A prompt the fbank cannot frame or a full arena is a ValueError and registers none."""
+    def _front(self, waves: Sequence, rates: Sequence[Optional[int]], what: str, keep_wav: bool = False):
+        """The front of a registration: waveforms -> (arena offsets, frames, samples at the model's rate[,
+        the resampled un-normalised waveforms on the device]).  Nothing is registered on an error."""
         from .infer import _prompts_at_rate
-        dev, B = self.device, len(prompts)
-        if B == 0:
-            return []
-        wavs = [torch.as_tensor(np.asarray(p[0]), dtype=torch.float32).reshape(-1) for p in prompts]
-        rates = [self.sampling_rate if len(p) < 3 or p[2] is None else int(p[2]) for p in prompts]
+        dev, B = self.device, len(waves)
+        wavs = [torch.as_tensor(np.asarray(w), dtype=torch.float32).reshape(-1) for w in waves]
+        rates = [self.sampling_rate if r is None else int(r) for r in rates]
         sizes = [self.frames_of(len(w), r) for w, r in zip(wavs, rates)]
         lens, frames = [s[0] for s in sizes], [s[1] for s in sizes]
         pad = self.fx._n_fft // 2 if self.fx._frame_offset is None else self.fx._frame_offset
         if min(lens) <= pad:
-            raise ValueError(f"reflect padding needs more than {pad} samples per prompt")
+            raise ValueError(f"reflect padding needs more than {pad} samples per {what}")
         offsets: List[int] = []
         try:
             for f in frames:
@@ -227,12 +237,15 @@ class VoiceStore:
             for o in offsets:
                 self.alloc.free(o)
             raise
+        kept = []
         try:
             ld = (max(lens) + 3) // 4 * 4                 # (a multiple of 4: the 16-byte form of the scale pass)
             wb = torch.zeros((B, ld), dtype=torch.float32, device=dev)
             # (one upload and one resample per other rate; a prompt at the model's rate goes up here)
             for i, w in enumerate(_prompts_at_rate(wavs, rates, self.sampling_rate, dev)):
                 wb[i, :lens[i]] = w
+            if keep_wav:                                  # (before the normalisation below, which is in place)
+                kept = [wb[i, :lens[i]].clone() for i in range(B)]
             rms, _, gain_out, ln = prompt_rms(wb, lens, self.target_rms)
             prompt_scale(wb, lens, ln, rms, self.target_rms, out=wb)
             feats, _ = self.fx.extract_batch(wb, torch.tensor(lens))
@@ -244,6 +257,16 @@ class VoiceStore:
             for o in offsets:
                 self.alloc.free(o)
             raise
+        return offsets, frames, lens, kept
+
+    @torch.inference_mode()
+    def register_batch(self, prompts: Sequence[tuple]) -> List[Voice]:
+        """``prompts`` = [(prompt_wav, prompt_tokens[, prompt_sampling_rate]), ...] -> their voices.
+        A prompt the fbank cannot frame or a full arena is a ValueError and registers none."""
+        if len(prompts) == 0:
+            return []
+        offsets, frames, lens, _ = self._front([p[0] for p in prompts],
+                                               [None if len(p) < 3 else p[2] for p in prompts], "prompt")
         out = []
         for i, (o, f) in enumerate(zip(offsets, frames)):
             v = Voice(next(self._ids), o, f, lens[i], tuple(int(t) for t in prompts[i][1]), self)
@@ -254,33 +277,70 @@ class VoiceStore:
     def register(self, prompt_wav, prompt_tokens, prompt_sampling_rate: Optional[int] = None) -> Voice:
         return self.register_batch([(prompt_wav, prompt_tokens, prompt_sampling_rate)])[0]
 
+    @torch.inference_mode()
+    def register_recording_batch(self, recordings: Sequence) -> List[Recording]:
+        """``recordings`` = [wav or (wav, sampling_rate), ...] -> their ``Recording`` handles: the voices'
+        front into the same arena (a range of whole rows each, the output gain at its first row), and the
+        resampled, un-normalised waveform kept on the device for the splice (one tensor per recording).
+        A recording the fbank cannot frame or a full arena is a ValueError and registers none."""
+        if len(recordings) == 0:
+            return []
+        pairs = [r if isinstance(r, tuple) else (r, None) for r in recordings]
+        offsets, frames, lens, kept = self._front([p[0] for p in pairs], [p[1] for p in pairs], "recording",
+                                                  keep_wav=True)
+        out = []
+        for i, (o, f) in enumerate(zip(offsets, frames)):
+            r = Recording(next(self._ids), o, f, lens[i], self)
+            self._live[r.id], self._uses[r.id], self._wavs[r.id] = r, 0, kept[i]
+            out.append(r)
+        return out
+
+    def register_recording(self, wav, sampling_rate: Optional[int] = None) -> Recording:
+        return self.register_recording_batch([(wav, sampling_rate)])[0]
+
+    def waveform(self, recording: Recording) -> torch.Tensor:
+        """The recording at the model's rate, un-normalised, (samples,) on the device."""
+        return self._wavs[self.check(recording).id]
+
     # ------------------------------------------------------------------ handles
-    def check(self, voice) -> Voice:
-        """``voice`` if it is a live voice of this store; a ValueError otherwise."""
-        if not isinstance(voice, Voice):
+    def check(self, voice):
+        """``voice`` if it is a live voice (or recording) of this store; a ValueError otherwise."""
+        if not isinstance(voice, (Voice, Recording)):
             raise ValueError(f"expected a Voice, got {type(voice).__name__}")
+        kind = "recording" if isinstance(voice, Recording) else "voice"
         if voice.store is not self:
-            raise ValueError(f"voice {voice.id} belongs to another store")
+            raise ValueError(f"{kind} {voice.id} belongs to another store")
         if self._live.get(voice.id) is not voice:
-            raise ValueError(f"voice {voice.id} has been dropped")
+            raise ValueError(f"{kind} {voice.id} has been dropped")
         return voice
 
     def hold(self, voice) -> None:
-        """One more queued request uses ``voice`` (``ContinuousBatcher.submit``)."""
+        """One more request uses ``voice``: a voice while the request is queued (``ContinuousBatcher.submit``),
+        a recording from ``submit_edit`` until its row has been retired (retirement reads the arena again)."""
         self._uses[self.check(voice).id] += 1
 
     def release(self, voice) -> None:
         self._uses[voice.id] -= 1
 
+    def uses(self, voice) -> int:
+        """The requests that hold ``voice`` now."""
+        return self._uses[self.check(voice).id]
+
     def drop(self, voice) -> None:
         self.check(voice)
         if self._uses[voice.id]:
-            raise ValueError(f"voice {voice.id} is still used by {self._uses[voice.id]} queued request(s)")
+            kind = "recording" if isinstance(voice, Recording) else "voice"
+            raise ValueError(f"{kind} {voice.id} is still used by {self._uses[voice.id]} queued request(s)"
+                             if kind == "voice" else
+                             f"recording {voice.id} is still used by {self._uses[voice.id]} queued or in-flight "
+                             f"request(s)")
         del self._live[voice.id], self._uses[voice.id]
+        self._wavs.pop(voice.id, None)
         self.alloc.free(voice.offset)
 
     def device_bytes(self) -> int:
-        return self.arena.numel() * 4 + self.gains.numel() * 4 + self._gather.device_bytes()
+        return (self.arena.numel() * 4 + self.gains.numel() * 4 + self._gather.device_bytes()
+                + sum(w.numel() * 4 for w in self._wavs.values()))
 
     # ------------------------------------------------------------------ the hot path
     def gather(self, voices: Sequence[Voice], T: int):
